@@ -8,7 +8,11 @@ backward, gradient all-reduce, global-norm clip and AdamW update.  Synthetic SAM
 (input 1024 / target 128 tokens, the ref/train-accelerator.py:114-133 shapes) and random-init
 weights with HF's initialisation (no network).  Weak scaling: fixed per-GPU micro-batch.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs when ``--dump-outputs`` is
+given (dump_outputs) and prints the result line; measurements that are not needed for the headline figure go behind
+``--full``.
 
 ``--gpus N > 1`` without a launcher (no WORLD_SIZE in the environment) starts its own: the same command line under
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`` as a CHILD process (no exec,
@@ -100,6 +104,15 @@ def parse():
                          "launched between the segments), split (after backward) or capture (RCCL inside the graph)")
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp32"],
                     help="weights/activations dtype (default bf16; fp32 on a CPU rehearsal)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "its loss, its pre-clip gradient norm, and a fixed seeded sample of the updated weights and "
+                         "of AdamW's first moment (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks that are not part of the headline figure.  A --gpus 1 "
+                         "run has none today (its result line is arithmetic on the timed steps), so the flag changes "
+                         "nothing yet; anything added later that takes runs of its own belongs behind it.  The N > 1 "
+                         "self-diagnosis (module docstring) is part of every multi-GPU run")
     a = ap.parse_args()
     a.bucket_mb = "auto" if str(a.bucket_mb).lower() == "auto" else float(a.bucket_mb)
     if a.comm_stress and "--batch-per-gpu" not in " ".join(sys.argv):
@@ -226,6 +239,40 @@ def comm_probe(env, eng, sizes_mb=(1.0, 32.0, 128.0), iters: int = 5) -> dict:
     return out
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept of each flat buffer (4 MiB as float32)
+
+
+def dump_outputs(path: str, eng, loss, norm, seed: int) -> dict:
+    """``--dump-outputs``: what the last timed step handed back and left behind, as ``<path>/<name>.npy`` (float32), so
+    two builds run with the same arguments can be compared output for output (inputs and initial weights are seeded).
+
+    * ``loss``: the step's mean loss over its micro-batches; ``grad_norm``: its pre-clip global gradient norm;
+    * ``params_sample`` / ``exp_avg_sample``: the updated weights (the fp32 master copy when there is one) and AdamW's
+      first moment at DUMP_SAMPLE flat offsets drawn once from ``seed`` (sorted; the whole buffer if it is smaller).
+      The buffers are hundreds of MB at t5-base, the sample keeps the dump at ~8 MiB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    opt = eng.optimizer
+    weights = opt.master if opt.master is not None else eng.flat.param_buf
+    n = weights.numel()
+    if n > DUMP_SAMPLE:
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values.to(weights.device)
+        pick = lambda x: x.index_select(0, idx)  # noqa: E731
+    else:
+        pick = lambda x: x  # noqa: E731
+    arrays = {"loss": loss.reshape(1), "grad_norm": norm.reshape(1) if norm is not None else None,
+              "params_sample": pick(weights), "exp_avg_sample": pick(opt.exp_avg)}
+    written = {}
+    for name, x in arrays.items():
+        if x is None:
+            continue
+        arr = x.detach().to(device="cpu", dtype=torch.float32).numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        written[name] = list(arr.shape)
+    return written
+
+
 def build(a, env):
     from distributed_llms_example_amd.models import build_model, resolve_config
     from distributed_llms_example_amd.ops.rng import manual_seed
@@ -310,14 +357,17 @@ def main():
             torch.cuda.empty_cache()
             cfg, eng, dtype_name = build(a, env)
 
+    last = [None, None]  # what the last step returned: loss (eager: one per micro-batch), pre-clip grad norm
+
     def step(i):
         mbs = [batches[(i * GA + k) % len(batches)] for k in range(GA)]
         if graphed is not None:
             graphed.replay(mbs)
+            last[:] = [graphed.loss, graphed.norm]
             return
-        for k in range(GA):  # GA micro-batches, gradient sync (and the all-reduce) on the last only
-            eng.forward_backward(mbs[k], grad_accum=GA, sync=k == GA - 1)
-        eng.step()
+        # GA micro-batches, gradient sync (and the all-reduce) on the last only
+        losses = [eng.forward_backward(mbs[k], grad_accum=GA, sync=k == GA - 1) for k in range(GA)]
+        last[:] = [losses, eng.step()]
 
     for i in range(a.warmup):
         step(i)
@@ -333,6 +383,10 @@ def main():
     env.barrier()
     _sync(env.device)
     dt = time.perf_counter() - t0
+    if a.dump_outputs and env.is_main_process and a.steps > 0:  # before anything else moves the engine's state
+        loss = torch.stack(list(last[0])).mean() if isinstance(last[0], (list, tuple)) else last[0]
+        dumped = dump_outputs(a.dump_outputs, eng, loss, last[1], a.seed)
+        print(f"[bench] wrote {sorted(dumped)} to {a.dump_outputs}", file=sys.stderr, flush=True)
     if os.environ.get("DLLM_TORCH_PROFILE") and env.rank == 0 and graphed is None:
         _torch_profile(step, os.environ["DLLM_TORCH_PROFILE"])  # after timing: attributes kernels to call sites
     comm = None
