@@ -1,0 +1,510 @@
+// bf16 flash attention (forward + backward) for head dims 32 .. 128 other than 64 (head dim 64 runs csrc/attn.hip):
+// the bf16 sibling of csrc/attn_f32.hip, templated on the padded head dim DP in {32, 64, 96, 128}.  bf16 in, bf16 out,
+// fp32 accumulation on v_mfma_f32_16x16x32_bf16.  Same op and semantics as csrc/attn.hip / csrc/attn_f32.hip: softmax
+// scale, T5 relative-position bias LUT [H, Sq + Sk - 1] (+ its fp32 gradient), key-padding mask, causal mask with
+// causal_off = Sk - Sq, and attention-probability dropout with the exact keep decisions of ops/rng.py
+// attention_keep_mask.  O(S) memory.  LSE convention of csrc/attn.hip: log2 units, +inf for a row without a valid key
+// (its output row is 0) — parallel/context.py _merge combines blocks by it.
+//
+// The real head dim D (D % 8 == 0, 32 <= D <= DP) is a runtime field: columns D .. DP-1 are staged as zeros and never
+// stored.  bias / kpm / causal are runtime flags; only DP and DROP are template parameters (24 kernel instantiations).
+//
+// Layout trick of csrc/attn_f32.hip, carried over to the 16x16x32 bf16 MFMA: its C/D map puts rows 4g .. 4g+3
+// (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction indices k = 8g + j
+// (j = 0 .. 7) from lane group g.  S^T = K Q^T leaves each lane with keys 16t + 4g + i of ONE query row; two such
+// 16-key tiles (t = 2u, 2u+1) packed to bf16 are the B operand of the next product as they stand, reducing over keys
+// {32u + 4g + j, 32u + 16 + 4g + j : j < 4} — the other operand is read in the same key order by two hardware-
+// transposed LDS reads (ds_read_b64_tr_b16) of the row-major image.  No LDS round trip for P or dS, and one image per
+// staged tensor.
+//
+//   forward    grid (Sq/64, B*H), 4 waves x 16 query rows; per 64-key block: K and V staged row-major in LDS,
+//              S^T = K Q^T, online softmax + dropout in registers, O^T += V^T P^T.
+//   delta      rowsum(dO * O), one 16-lane group per row.
+//   dQ         grid (Sq/64, B*H): S^T, dP^T = V dO^T, dS = P (dP_kept - delta), dQ^T += K^T dS^T; the bias gradient is
+//              summed per diagonal of the block's dS tile in LDS and added to dlut once per block (fp32 atomics).
+//   dK / dV    grid (Sk/64, B*H), 4 waves x 16 keys: S = Q K^T, dP = dO V^T, dV^T += dO^T P_kept, dK^T += Q^T dS.
+#include "common.h"
+
+#include "attn_hd_params.h"
+
+using namespace dllm;
+
+DLLM_SEED_STEP_TU(attn_hd)
+
+namespace {
+
+constexpr int BQ = 64, BKY = 64, NT = 256;
+constexpr uint32_t C24 = 0x9E3779u, C24B = 0x85EBCBu, HG = 0x9E3779B1u;  // ops/rng.py attention_keep_mask
+constexpr float LOG2E = 1.4426950408889634f;
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8v;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+
+DLLM_DEVICE f32x4 mma(bf16x8v a, bf16x8v b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+// keep decision of key j of the row whose hash is rh (ops/rng.py attention_keep_mask, bit-exact; as csrc/attn_f32.hip)
+DLLM_DEVICE bool keep_key(uint32_t rh, int j, uint32_t thr) {
+  const uint32_t g = __umul24(rh, C24) + (uint32_t)(j >> 1) * HG;
+  const uint32_t hh = __umul24(g ^ (g >> 15), C24B);
+  const uint32_t y = hh ^ (hh >> 16);
+  const uint32_t half = (j & 1) ? (y >> 16) : (y & 0xFFFFu);
+  return (half ^ 0x8000u) >= thr;
+}
+// keep bits of keys j0 .. j0 + 3 (j0 % 4 == 0): bit i <-> key j0 + i; two hashes (one per key pair)
+DLLM_DEVICE uint32_t keep4(uint32_t rh, int j0, uint32_t thr) {
+  const uint32_t g0 = __umul24(rh, C24) + (uint32_t)(j0 >> 1) * HG;
+  uint32_t bits = 0;
+#pragma unroll
+  for (int pp = 0; pp < 2; ++pp) {
+    const uint32_t g = g0 + (uint32_t)pp * HG;
+    const uint32_t hh = __umul24(g ^ (g >> 15), C24B);
+    const uint32_t y = hh ^ (hh >> 16);
+    bits |= (((y & 0xFFFFu) ^ 0x8000u) >= thr ? 1u : 0u) << (2 * pp);
+    bits |= (((y >> 16) ^ 0x8000u) >= thr ? 1u : 0u) << (2 * pp + 1);
+  }
+  return bits;
+}
+
+DLLM_DEVICE float ex2(float x) { return __builtin_amdgcn_exp2f(x); }  // v_exp_f32: exp2(-inf) = 0
+
+// LDS image of a 64-row tile: [64][DP + 8] bf16, row-major.  The 16-B pad per row spreads the 16 rows of one
+// ds_read_b128 fragment read over all banks (row stride = DP / 2 + 4 dwords: 4 r mod 64 distinct for r < 16).
+template <int DP> struct Img {
+  static constexpr int LD = DP + 8, CPR = DP / 8, SIZE = 64 * LD;
+};
+
+// stage rows [r0, r0 + 64) of a [*, S, H, D] view (row stride ss) into the image: rows >= S and columns >= D as zeros.
+// 256 threads, DP / 32 16-B chunks each.
+template <int DP>
+DLLM_DEVICE void stage(const uint16_t* base, long ss, int r0, int S, int D, uint16_t* img, int tid) {
+  constexpr int LD = Img<DP>::LD, CPR = Img<DP>::CPR;
+#pragma unroll
+  for (int j = 0; j < DP / 32; ++j) {
+    const int idx = tid + NT * j, r = idx / CPR, ch = idx % CPR;
+    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (r0 + r < S && 8 * ch < D) v = *reinterpret_cast<const u16x8*>(base + (long)(r0 + r) * ss + 8 * ch);
+    *reinterpret_cast<u16x8*>(img + r * LD + 8 * ch) = v;
+  }
+}
+
+// the DP / 32 operand fragments of one row from global memory: fragment ks = columns 32 ks + 8 g .. + 7 (0 past D)
+template <int DP>
+DLLM_DEVICE void load_row_frags(const uint16_t* rowp, int g, int D, bf16x8v (&f)[DP / 32]) {
+#pragma unroll
+  for (int ks = 0; ks < DP / 32; ++ks) {
+    const int d0 = 32 * ks + 8 * g;
+    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (d0 < D) v = *reinterpret_cast<const u16x8*>(rowp + d0);
+    f[ks] = __builtin_bit_cast(bf16x8v, v);
+  }
+}
+
+// MFMA operand whose reduction index is the head dim: row r, columns 32 ks + 8 g .. + 7 of the image
+template <int DP>
+DLLM_DEVICE bf16x8v ld_row(const uint16_t* img, int r, int ks, int g) {
+  return __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u16x8*>(img + r * Img<DP>::LD + 32 * ks + 8 * g));
+}
+
+// MFMA operand whose reduction index is the tile row (sequence): for the lane (c, g), column c0 + c of rows
+// rb + 4 g + {0..3} (elements 0..3) and rb + 16 + 4 g + {0..3} (elements 4..7) — the key order of two packed
+// accumulator tiles.  ds_read_b64_tr_b16: a 16-lane group reads 4 rows x 16 columns, lane 4 q + p supplies the
+// address of row q, columns 4 p .. 4 p + 3, and group lane i receives column i of the 4 rows.  EXEC must be full.
+template <int DP>
+DLLM_DEVICE bf16x8v ld_tr2(const uint16_t* img, int rb, int c0, int c, int g) {
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+  const uint16_t* p = img + (rb + 4 * g + (c >> 2)) * Img<DP>::LD + c0 + 4 * (c & 3);
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 16 * Img<DP>::LD));
+  typedef __attribute__((ext_vector_type(8))) short s16x8;
+  const s16x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  return __builtin_bit_cast(bf16x8v, v);
+}
+
+// two accumulator tiles (t = 2u, 2u + 1) as one bf16 operand: element j <- a[j], element 4 + j <- b[j]
+DLLM_DEVICE bf16x8v pack8(f32x4 a, f32x4 b) {
+  const u32x4 r = {pack_bf16x2(a.x, a.y), pack_bf16x2(a.z, a.w), pack_bf16x2(b.x, b.y), pack_bf16x2(b.z, b.w)};
+  return __builtin_bit_cast(bf16x8v, r);
+}
+
+DLLM_DEVICE float grp_max(float v) {  // over the 4 lane groups (same lane & 15)
+  v = fmaxf(v, __shfl_xor(v, 16, 64));
+  return fmaxf(v, __shfl_xor(v, 32, 64));
+}
+DLLM_DEVICE float grp_sum(float v) {
+  v += __shfl_xor(v, 16, 64);
+  return v + __shfl_xor(v, 32, 64);
+}
+
+// key in range and not padding (the causal test is per (row, key), done by the callers)
+DLLM_DEVICE bool key_ok(const AttnHdParams& P, int b, int key) {
+  return key < P.Sk && (P.kpm == nullptr || P.kpm[(long)b * P.Sk + key] != 0);
+}
+
+// bias window of the (q0, k0) block in log2 units: bias of (key, row) at Ls[key - row - (k0 - q0 - 63)]
+DLLM_DEVICE void stage_bias(const AttnHdParams& P, int h, int q0, int k0, float* Ls, int tid) {
+  if (P.lut && tid < 2 * BKY - 1) {
+    const long L = (long)P.Sq + P.Sk - 1;
+    long idx = (long)k0 - q0 - 63 + tid + P.Sq - 1;
+    idx = idx < 0 ? 0 : (idx >= L ? L - 1 : idx);
+    Ls[tid] = P.lut[(long)h * L + idx] * LOG2E;
+  }
+}
+
+// 4 bf16 of an accumulator tile to columns d0 .. d0 + 3 of a row (8-B store)
+DLLM_DEVICE void st4(uint16_t* p, f32x4 v) { Elem<uint16_t>::store4(p, v); }
+
+// ================================================================================================ forward
+template <int DP, bool DROP>
+__global__ __launch_bounds__(NT) void attn_hd_fwd_kernel(AttnHdParams P) {
+  constexpr int KS = DP / 32, DT = DP / 16;
+  __shared__ __attribute__((aligned(16))) uint16_t Ks[Img<DP>::SIZE];
+  __shared__ __attribute__((aligned(16))) uint16_t Vs[Img<DP>::SIZE];
+  __shared__ float Ls[2 * BKY];
+  __shared__ uint8_t Mk[BKY];  // 1: key valid (in range, not padding)
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
+  const int bh = blockIdx.y, b = bh / P.H, h = bh % P.H;
+  const int q0 = blockIdx.x * BQ;
+  const int row = q0 + 16 * w + c;
+  const int rowc = min(row, P.Sq - 1);
+  bf16x8v qf[KS];
+  load_row_frags<DP>(P.q + (long)b * P.q_sb + (long)rowc * P.q_ss + (long)h * P.q_sh, g, P.D, qf);
+  const uint32_t rh = DROP ? mix32(eff_seed(P.seed), (uint32_t)((long)bh * P.Sq + rowc)) : 0u;
+  const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
+  const float scale2 = P.scale * LOG2E;
+  float m = -INFINITY, l = 0.f;
+  f32x4 acc[DT];
+#pragma unroll
+  for (int i = 0; i < DT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const uint16_t* kb = P.k + (long)b * P.k_sb + (long)h * P.k_sh;
+  const uint16_t* vb = P.v + (long)b * P.v_sb + (long)h * P.v_sh;
+  int kend = P.Sk;
+  if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
+  for (int k0 = 0; k0 < kend; k0 += BKY) {
+    __syncthreads();  // the previous block's LDS reads are done
+    stage<DP>(kb, P.k_ss, k0, P.Sk, P.D, Ks, tid);
+    stage<DP>(vb, P.v_ss, k0, P.Sk, P.D, Vs, tid);
+    stage_bias(P, h, q0, k0, Ls, tid);
+    if (tid < BKY) Mk[tid] = key_ok(P, b, k0 + tid);
+    __syncthreads();
+    f32x4 st[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) st[t] = mma(ld_row<DP>(Ks, 16 * t + c, ks, g), qf[ks], st[t]);
+    }
+    // st[t][i] = S[row][key = k0 + 16 t + 4 g + i]
+    float mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int key = k0 + 16 * t + 4 * g + i;
+        float x = st[t][i] * scale2;
+        if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
+        if (!Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off)) x = -INFINITY;
+        st[t][i] = x;
+        mx = fmaxf(mx, x);
+      }
+    }
+    mx = grp_max(mx);
+    const float mn = fmaxf(m, mx);
+    const float mu = mn == -INFINITY ? 0.f : mn;
+    const float alpha = ex2(m - mu);
+    float ls = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t kb4 = DROP ? keep4(rh, k0 + 16 * t + 4 * g, P.thr) : 0xFu;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float pr = ex2(st[t][i] - mu);
+        ls += pr;
+        st[t][i] = DROP ? (((kb4 >> i) & 1u) ? pr * dscale : 0.f) : pr;
+      }
+    }
+    ls = grp_sum(ls);
+    l = l * alpha + ls;
+    m = mn;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) acc[dt] *= alpha;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const bf16x8v pb = pack8(st[2 * u], st[2 * u + 1]);
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) acc[dt] = mma(ld_tr2<DP>(Vs, 32 * u, 16 * dt, c, g), pb, acc[dt]);
+    }
+  }
+  // acc[dt][i] = O[row][d = 16 dt + 4 g + i] (unnormalised)
+  if (row < P.Sq) {
+    const float inv = l > 0.f ? 1.f / l : 0.f;
+    uint16_t* op = P.o_out + (long)b * P.o_sb + (long)row * P.o_ss + (long)h * P.o_sh;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+      if (16 * dt + 4 * g < P.D) st4(op + 16 * dt + 4 * g, acc[dt] * inv);
+    if (g == 0) P.lse[(long)bh * P.Sq + row] = l > 0.f ? m + __log2f(l) : INFINITY;
+  }
+}
+
+// ================================================================================================ backward
+// delta[bh][row] = sum_d dO * O; one 16-lane group per row, lane j takes columns 8 j .. 8 j + 7 (D <= 128)
+__global__ __launch_bounds__(NT) void attn_hd_delta_kernel(AttnHdParams P) {
+  const long rows = (long)P.B * P.H * P.Sq;
+  const long r = (long)blockIdx.x * (NT / 16) + (threadIdx.x >> 4);
+  const int j = threadIdx.x & 15;
+  float s = 0.f;
+  if (r < rows && 8 * j < P.D) {
+    const int row = (int)(r % P.Sq);
+    const long bh = r / P.Sq;
+    const int b = (int)(bh / P.H), h = (int)(bh % P.H);
+    const u16x8 o = *reinterpret_cast<const u16x8*>(P.o + (long)b * P.o_sb + (long)row * P.o_ss + (long)h * P.o_sh + 8 * j);
+    const u16x8 d = *reinterpret_cast<const u16x8*>(P.dout + (long)b * P.do_sb + (long)row * P.do_ss +
+                                                    (long)h * P.do_sh + 8 * j);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s += bf2f(o[e]) * bf2f(d[e]);
+  }
+#pragma unroll
+  for (int mm = 8; mm >= 1; mm >>= 1) s += __shfl_xor(s, mm, 16);
+  if (r < rows && j == 0) P.delta[r] = s;
+}
+
+template <int DP, bool DROP>
+__global__ __launch_bounds__(NT) void attn_hd_dq_kernel(AttnHdParams P) {
+  constexpr int KS = DP / 32, DT = DP / 16;
+  __shared__ __attribute__((aligned(16))) uint16_t Ks[Img<DP>::SIZE];
+  __shared__ __attribute__((aligned(16))) uint16_t Vs[Img<DP>::SIZE];
+  __shared__ float Ls[2 * BKY];
+  __shared__ float Ds[BQ * (BKY + 1)];  // dS tile of the block, row stride 65: a diagonal walk is bank-conflict free
+  __shared__ uint8_t Mk[BKY];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
+  const int bh = blockIdx.y, b = bh / P.H, h = bh % P.H;
+  const int q0 = blockIdx.x * BQ;
+  const int row = q0 + 16 * w + c;
+  const int rowc = min(row, P.Sq - 1);
+  const bool row_ok = row < P.Sq;
+  const long L = (long)P.Sq + P.Sk - 1;
+  bf16x8v qf[KS], dof[KS];
+  load_row_frags<DP>(P.q + (long)b * P.q_sb + (long)rowc * P.q_ss + (long)h * P.q_sh, g, P.D, qf);
+  load_row_frags<DP>(P.dout + (long)b * P.do_sb + (long)rowc * P.do_ss + (long)h * P.do_sh, g, P.D, dof);
+  const float lse = row_ok ? P.lse[(long)bh * P.Sq + row] : INFINITY;
+  const float dlt = row_ok ? P.delta[(long)bh * P.Sq + row] : 0.f;
+  const uint32_t rh = DROP ? mix32(eff_seed(P.seed), (uint32_t)((long)bh * P.Sq + rowc)) : 0u;
+  const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
+  const float scale2 = P.scale * LOG2E;
+  const bool want_dlut = P.dlut != nullptr && P.lut != nullptr;
+  f32x4 acc[DT];
+#pragma unroll
+  for (int i = 0; i < DT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const uint16_t* kb = P.k + (long)b * P.k_sb + (long)h * P.k_sh;
+  const uint16_t* vb = P.v + (long)b * P.v_sb + (long)h * P.v_sh;
+  int kend = P.Sk;
+  if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
+  for (int k0 = 0; k0 < kend; k0 += BKY) {
+    __syncthreads();
+    stage<DP>(kb, P.k_ss, k0, P.Sk, P.D, Ks, tid);
+    stage<DP>(vb, P.v_ss, k0, P.Sk, P.D, Vs, tid);
+    stage_bias(P, h, q0, k0, Ls, tid);
+    if (tid < BKY) Mk[tid] = key_ok(P, b, k0 + tid);
+    __syncthreads();
+    f32x4 st[4], dpt[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      dpt[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        st[t] = mma(ld_row<DP>(Ks, 16 * t + c, ks, g), qf[ks], st[t]);
+        dpt[t] = mma(ld_row<DP>(Vs, 16 * t + c, ks, g), dof[ks], dpt[t]);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t kb4 = DROP ? keep4(rh, k0 + 16 * t + 4 * g, P.thr) : 0xFu;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int key = k0 + 16 * t + 4 * g + i;
+        const int di = key - row - (k0 - q0 - 63);
+        float x = st[t][i] * scale2;
+        if (P.lut) x += Ls[di];
+        const bool msk = !Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off);
+        const float pr = msk ? 0.f : ex2(x - lse);
+        const float dpk = DROP ? (((kb4 >> i) & 1u) ? dpt[t][i] * dscale : 0.f) : dpt[t][i];
+        const float ds = pr * (dpk - dlt);
+        st[t][i] = ds;
+        if (want_dlut) Ds[(16 * w + c) * (BKY + 1) + 16 * t + 4 * g + i] = ds;  // 0 for rows >= Sq (lse = inf)
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const bf16x8v sb = pack8(st[2 * u], st[2 * u + 1]);
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) acc[dt] = mma(ld_tr2<DP>(Ks, 32 * u, 16 * dt, c, g), sb, acc[dt]);
+    }
+    if (want_dlut) {
+      // bias gradient: per diagonal d = key - row + 63 of the 64x64 block, one thread walks its diagonal in the dS
+      // tile (LDS reads, no atomics) and adds the sum to dlut once
+      __syncthreads();
+      if (tid < 2 * BKY - 1) {
+        const int d = tid;
+        const int r0 = d < 63 ? 63 - d : 0, r1 = d < 63 ? 63 : 126 - d;
+        float v = 0.f;
+        for (int r = r0; r <= r1; ++r) v += Ds[r * (BKY + 1) + r + d - 63];
+        const long idx = (long)k0 - q0 - 63 + d + P.Sq - 1;
+        if (v != 0.f && idx >= 0 && idx < L) atomicAdd(&P.dlut[(long)h * L + idx], v);
+      }
+    }
+  }
+  // acc[dt][i] = dQ[row][d = 16 dt + 4 g + i] / scale
+  if (row_ok) {
+    uint16_t* dqp = P.dq + (long)b * P.dq_sb + (long)row * P.dq_ss + (long)h * P.dq_sh;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+      if (16 * dt + 4 * g < P.D) st4(dqp + 16 * dt + 4 * g, acc[dt] * P.scale);
+  }
+}
+
+template <int DP, bool DROP>
+__global__ __launch_bounds__(NT) void attn_hd_dkdv_kernel(AttnHdParams P) {
+  constexpr int KS = DP / 32, DT = DP / 16;
+  __shared__ __attribute__((aligned(16))) uint16_t Qs[Img<DP>::SIZE];
+  __shared__ __attribute__((aligned(16))) uint16_t Os[Img<DP>::SIZE];  // dO
+  __shared__ float Ls[2 * BQ];
+  __shared__ float Rl[BQ], Rd[BQ];
+  __shared__ uint32_t Rh[BQ];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
+  const int bh = blockIdx.y, b = bh / P.H, h = bh % P.H;
+  const int k0 = blockIdx.x * BKY;
+  const int key = k0 + 16 * w + c;
+  const int keyc = min(key, P.Sk - 1);
+  bf16x8v kf[KS], vf[KS];
+  load_row_frags<DP>(P.k + (long)b * P.k_sb + (long)keyc * P.k_ss + (long)h * P.k_sh, g, P.D, kf);
+  load_row_frags<DP>(P.v + (long)b * P.v_sb + (long)keyc * P.v_ss + (long)h * P.v_sh, g, P.D, vf);
+  const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
+  const float scale2 = P.scale * LOG2E;
+  const uint32_t seed = DROP ? eff_seed(P.seed) : 0u;
+  const bool kok = key_ok(P, b, key);
+  f32x4 dk[DT], dv[DT];
+#pragma unroll
+  for (int i = 0; i < DT; ++i) {
+    dk[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    dv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const uint16_t* qb = P.q + (long)b * P.q_sb + (long)h * P.q_sh;
+  const uint16_t* ob = P.dout + (long)b * P.do_sb + (long)h * P.do_sh;
+  int qstart = 0;
+  if (P.causal) qstart = max(0, (k0 - P.causal_off) / BQ * BQ);
+  for (int q0 = qstart; q0 < P.Sq; q0 += BQ) {
+    __syncthreads();
+    stage<DP>(qb, P.q_ss, q0, P.Sq, P.D, Qs, tid);
+    stage<DP>(ob, P.do_ss, q0, P.Sq, P.D, Os, tid);
+    stage_bias(P, h, q0, k0, Ls, tid);
+    if (tid < BQ) {
+      const int r = q0 + tid;
+      const bool ok = r < P.Sq;
+      Rl[tid] = ok ? P.lse[(long)bh * P.Sq + r] : INFINITY;
+      Rd[tid] = ok ? P.delta[(long)bh * P.Sq + r] : 0.f;
+      if (DROP) Rh[tid] = mix32(seed, (uint32_t)((long)bh * P.Sq + min(r, P.Sq - 1)));
+    }
+    __syncthreads();
+    f32x4 sc[4], dp[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        sc[t] = mma(ld_row<DP>(Qs, 16 * t + c, ks, g), kf[ks], sc[t]);
+        dp[t] = mma(ld_row<DP>(Os, 16 * t + c, ks, g), vf[ks], dp[t]);
+      }
+    }
+    // sc[t][i] = S[row = q0 + 16 t + 4 g + i][key]; pd = kept P, sc <- dS
+    f32x4 pd[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int rl = 16 * t + 4 * g + i, row = q0 + rl;
+        float x = sc[t][i] * scale2;
+        if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
+        const bool msk = !kok || (P.causal && key > row + P.causal_off);
+        const float pr = msk ? 0.f : ex2(x - Rl[rl]);
+        const bool kp = DROP ? keep_key(Rh[rl], key, P.thr) : true;
+        const float dpk = kp ? dp[t][i] * dscale : 0.f;
+        pd[t][i] = kp ? pr * dscale : 0.f;
+        sc[t][i] = pr * (dpk - Rd[rl]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const bf16x8v pb = pack8(pd[2 * u], pd[2 * u + 1]);
+      const bf16x8v sb = pack8(sc[2 * u], sc[2 * u + 1]);
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        dv[dt] = mma(ld_tr2<DP>(Os, 32 * u, 16 * dt, c, g), pb, dv[dt]);
+        dk[dt] = mma(ld_tr2<DP>(Qs, 32 * u, 16 * dt, c, g), sb, dk[dt]);
+      }
+    }
+  }
+  // dk[dt][i] = dK[key][d = 16 dt + 4 g + i] / scale
+  if (key < P.Sk) {
+    uint16_t* dkp = P.dk + (long)b * P.dk_sb + (long)key * P.dk_ss + (long)h * P.dk_sh;
+    uint16_t* dvp = P.dv + (long)b * P.dv_sb + (long)key * P.dv_ss + (long)h * P.dv_sh;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      if (16 * dt + 4 * g < P.D) {
+        st4(dkp + 16 * dt + 4 * g, dk[dt] * P.scale);
+        st4(dvp + 16 * dt + 4 * g, dv[dt]);
+      }
+    }
+  }
+}
+
+template <int DP>
+int launch_fwd(const AttnHdParams& P, hipStream_t st) {
+  dim3 grid((P.Sq + BQ - 1) / BQ, P.B * P.H);
+  if (P.p_drop > 0.f) hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, true>), grid, dim3(NT), 0, st, P);
+  else hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, false>), grid, dim3(NT), 0, st, P);
+  DLLM_CHECK_LAUNCH();
+  return 0;
+}
+
+template <int DP>
+int launch_bwd(const AttnHdParams& P, hipStream_t st) {
+  dim3 gq((P.Sq + BQ - 1) / BQ, P.B * P.H), gk((P.Sk + BKY - 1) / BKY, P.B * P.H);
+  if (P.p_drop > 0.f) {
+    hipLaunchKernelGGL((attn_hd_dq_kernel<DP, true>), gq, dim3(NT), 0, st, P);
+    hipLaunchKernelGGL((attn_hd_dkdv_kernel<DP, true>), gk, dim3(NT), 0, st, P);
+  } else {
+    hipLaunchKernelGGL((attn_hd_dq_kernel<DP, false>), gq, dim3(NT), 0, st, P);
+    hipLaunchKernelGGL((attn_hd_dkdv_kernel<DP, false>), gk, dim3(NT), 0, st, P);
+  }
+  DLLM_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+// -1: head dim outside the kernels' range (the binding checks it first)
+extern "C" int dllm_attn_hd_fwd(AttnHdParams* pp, hipStream_t st) {
+  const AttnHdParams& P = *pp;
+  if (P.D < 32 || P.D > 128 || P.D % 8) return -1;
+  switch ((P.D + 31) / 32) {
+    case 1: return launch_fwd<32>(P, st);
+    case 2: return launch_fwd<64>(P, st);
+    case 3: return launch_fwd<96>(P, st);
+    default: return launch_fwd<128>(P, st);
+  }
+}
+
+extern "C" int dllm_attn_hd_bwd(AttnHdParams* pp, hipStream_t st) {
+  const AttnHdParams& P = *pp;
+  if (P.D < 32 || P.D > 128 || P.D % 8) return -1;
+  const long rows = (long)P.B * P.H * P.Sq;
+  hipLaunchKernelGGL(attn_hd_delta_kernel, dim3((unsigned)((rows + NT / 16 - 1) / (NT / 16))), dim3(NT), 0, st, P);
+  DLLM_CHECK_LAUNCH();
+  switch ((P.D + 31) / 32) {
+    case 1: return launch_bwd<32>(P, st);
+    case 2: return launch_bwd<64>(P, st);
+    case 3: return launch_bwd<96>(P, st);
+    default: return launch_bwd<128>(P, st);
+  }
+}

@@ -11,6 +11,7 @@
 #include <c10/hip/HIPStream.h>
 
 #include "attn_f32_params.h"
+#include "attn_hd_params.h"
 #include "attn_params.h"
 #include "gemm_params.h"
 #include "route.h"
@@ -42,6 +43,9 @@ int dllm_attn_dropout_mask(AttnParams*, hipStream_t);
 int dllm_attn_f32_fwd(AttnF32Params*, hipStream_t);
 int dllm_attn_f32_bwd(AttnF32Params*, hipStream_t);
 int dllm_set_seed_step_attn_f32(const uint32_t*);
+int dllm_attn_hd_fwd(AttnHdParams*, hipStream_t);
+int dllm_attn_hd_bwd(AttnHdParams*, hipStream_t);
+int dllm_set_seed_step_attn_hd(const uint32_t*);
 int dllm_wgrad_reduce(const GemmWgradParams*, hipStream_t);
 int dllm_gemm_fused(const GemmFusedParams*, int, int, hipStream_t);
 int dllm_gemm_w4(const GemmW4Params*, int, int, int, hipStream_t);
@@ -537,6 +541,115 @@ std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tens
   P.dv = dv.data_ptr<float>();
   P.dv_sb = dv.stride(0); P.dv_ss = dv.stride(1); P.dv_sh = dv.stride(2);
   check_rc(dllm_attn_f32_bwd(&P, stream()), "attn_f32_bwd");
+  return {dq, dk, dv, dlut};
+}
+
+// ------------------------------------------------------------------------------------------- bf16 attention, any head dim
+// csrc/attn_hd.hip: the same op for bf16 head dims 32 .. 128 other than 64 (64 runs csrc/attn.hip).
+void check_bshd_hd(const Tensor& t, const char* n, int64_t B, int64_t S, int64_t H, int64_t D) {
+  check_gpu(t, n);
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, n, ": attn_hd kernels take bf16");
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == S && t.size(2) == H && t.size(3) == D, n,
+              ": expected [B, S, H, ", D, "], got ", t.sizes());
+  TORCH_CHECK(t.stride(3) == 1, n, ": head dim must be contiguous");
+  TORCH_CHECK(t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 && t.stride(2) % 8 == 0, n,
+              ": strides must be multiples of 8 elements (16-B vector loads)");
+  check_aligned(t, 16, n);
+}
+
+void fill_hd(AttnHdParams& P, const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
+             const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "attn_hd: q / k / v must be [B, S, H, D]");
+  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3), Sk = k.size(1);
+  TORCH_CHECK(D >= 32 && D <= 128 && D % 8 == 0, "attn_hd: head dim must be in 32 .. 128 and a multiple of 8, got ", D);
+  check_bshd_hd(q, "q", B, Sq, H, D);
+  check_bshd_hd(k, "k", B, Sk, H, D);
+  check_bshd_hd(v, "v", B, Sk, H, D);
+  TORCH_CHECK(Sq > 0 && Sk > 0, "empty attention");
+  TORCH_CHECK(B * H <= 65535, "attention: B * H > 65535 unsupported (grid y)");
+  TORCH_CHECK(B * H * Sq < (int64_t)1 << 31 && (Sq + Sk) < (1 << 30), "attention too large");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p must be in [0, 1)");
+  P.q = reinterpret_cast<const uint16_t*>(q.data_ptr());
+  P.k = reinterpret_cast<const uint16_t*>(k.data_ptr());
+  P.v = reinterpret_cast<const uint16_t*>(v.data_ptr());
+  P.q_sb = q.stride(0); P.q_ss = q.stride(1); P.q_sh = q.stride(2);
+  P.k_sb = k.stride(0); P.k_ss = k.stride(1); P.k_sh = k.stride(2);
+  P.v_sb = v.stride(0); P.v_ss = v.stride(1); P.v_sh = v.stride(2);
+  P.B = B; P.H = H; P.Sq = Sq; P.Sk = Sk; P.D = D;
+  P.scale = (float)scale;
+  P.causal = causal ? 1 : 0;
+  P.causal_off = Sk - Sq;
+  P.p_drop = (float)p;
+  P.seed = (uint32_t)seed;
+  P.thr = p > 0.0 ? (uint32_t)std::min(65535.0, p * 65536.0) : 0u;  // ops/rng.py threshold16
+  if (kpm.has_value() && kpm->defined()) {
+    TORCH_CHECK(kpm->scalar_type() == at::kByte && kpm->is_contiguous() && kpm->dim() == 2 && kpm->size(0) == B &&
+                    kpm->size(1) == Sk && kpm->is_cuda(),
+                "key_padding_mask must be uint8 [B, Sk] contiguous on GPU");
+    P.kpm = kpm->data_ptr<uint8_t>();
+  }
+  if (lut.has_value() && lut->defined()) {
+    TORCH_CHECK(lut->scalar_type() == at::kFloat && lut->is_contiguous() && lut->dim() == 2 && lut->size(0) == H &&
+                    lut->size(1) == Sq + Sk - 1 && lut->is_cuda(),
+                "bias_lut must be fp32 [H, Sq + Sk - 1] contiguous on GPU");
+    P.lut = lut->data_ptr<float>();
+  }
+}
+
+std::vector<Tensor> attn_hd_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
+                                const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
+  AttnHdParams P{};
+  fill_hd(P, q, k, v, kpm, lut, scale, causal, p, seed);
+  auto o = at::empty({P.B, P.Sq, P.H, P.D}, q.options());
+  auto lse = at::empty({P.B, P.H, P.Sq}, q.options().dtype(at::kFloat));
+  P.o_out = reinterpret_cast<uint16_t*>(o.data_ptr());
+  P.o_sb = o.stride(0); P.o_ss = o.stride(1); P.o_sh = o.stride(2);
+  P.lse = lse.data_ptr<float>();
+  check_rc(dllm_attn_hd_fwd(&P, stream()), "attn_hd_fwd");
+  return {o, lse};
+}
+
+std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
+                                const Tensor& o, const Tensor& lse, const optional<Tensor>& kpm,
+                                const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
+                                bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
+                                const optional<Tensor>& dv_out) {
+  AttnHdParams P{};
+  fill_hd(P, q, k, v, kpm, lut, scale, causal, p, seed);
+  check_bshd_hd(o, "o", P.B, P.Sq, P.H, P.D);
+  check_bshd_hd(dout, "dout", P.B, P.Sq, P.H, P.D);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (int64_t)P.B * P.H * P.Sq && lse.is_contiguous() &&
+                  lse.is_cuda(),
+              "lse mismatch");
+  auto pick = [&](const optional<Tensor>& t, int64_t S, const char* n) {
+    if (t.has_value() && t->defined()) {
+      check_bshd_hd(*t, n, P.B, S, P.H, P.D);
+      return *t;
+    }
+    return at::empty({P.B, S, P.H, P.D}, q.options());
+  };
+  Tensor dq = pick(dq_out, P.Sq, "dq_out");
+  Tensor dk = pick(dk_out, P.Sk, "dk_out");
+  Tensor dv = pick(dv_out, P.Sk, "dv_out");
+  auto delta = at::empty({P.B, P.H, P.Sq}, q.options().dtype(at::kFloat));
+  Tensor dlut;
+  if (need_dlut && P.lut) {
+    dlut = at::zeros({P.H, P.Sq + P.Sk - 1}, q.options().dtype(at::kFloat));
+    P.dlut = dlut.data_ptr<float>();
+  }
+  P.o = reinterpret_cast<const uint16_t*>(o.data_ptr());
+  P.o_sb = o.stride(0); P.o_ss = o.stride(1); P.o_sh = o.stride(2);
+  P.dout = reinterpret_cast<const uint16_t*>(dout.data_ptr());
+  P.do_sb = dout.stride(0); P.do_ss = dout.stride(1); P.do_sh = dout.stride(2);
+  P.lse = lse.data_ptr<float>();
+  P.delta = delta.data_ptr<float>();
+  P.dq = reinterpret_cast<uint16_t*>(dq.data_ptr());
+  P.dq_sb = dq.stride(0); P.dq_ss = dq.stride(1); P.dq_sh = dq.stride(2);
+  P.dk = reinterpret_cast<uint16_t*>(dk.data_ptr());
+  P.dk_sb = dk.stride(0); P.dk_ss = dk.stride(1); P.dk_sh = dk.stride(2);
+  P.dv = reinterpret_cast<uint16_t*>(dv.data_ptr());
+  P.dv_sb = dv.stride(0); P.dv_ss = dv.stride(1); P.dv_sh = dv.stride(2);
+  check_rc(dllm_attn_hd_bwd(&P, stream()), "attn_hd_bwd");
   return {dq, dk, dv, dlut};
 }
 
@@ -1278,6 +1391,7 @@ void set_seed_step(const optional<Tensor>& step) {
   check_rc(dllm_set_seed_step_act(p), "set_seed_step(act)");
   check_rc(dllm_set_seed_step_attn(p), "set_seed_step(attn)");
   check_rc(dllm_set_seed_step_attn_f32(p), "set_seed_step(attn_f32)");
+  check_rc(dllm_set_seed_step_attn_hd(p), "set_seed_step(attn_hd)");
   check_rc(dllm_set_seed_step_gemm_fused(p), "set_seed_step(gemm_fused)");
   check_rc(dllm_set_seed_step_gemm_w4(p), "set_seed_step(gemm_w4)");
 }
@@ -1320,6 +1434,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_f32_fwd", &attn_f32_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
         py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"));
   m.def("attn_f32_bwd", &attn_f32_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+        py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
+        py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
+        py::arg("dv_out") = py::none());
+  m.def("attn_hd_fwd", &attn_hd_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
+        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"));
+  m.def("attn_hd_bwd", &attn_hd_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
         py::arg("dv_out") = py::none());

@@ -17,8 +17,10 @@ One op covers every attention variant the reference's models run (SURVEY.md §2.
 Layout: q ``[B, Sq, H, D]``, k/v ``[B, Sk, H, D]`` — the natural output of the fused QKV GEMM
 viewed without any transpose copy (only the last dim must be contiguous).  Output ``[B, Sq, H, D]``.
 
-Kernels: csrc/attn.hip (bf16: forward; backward = dQ kernel + dK/dV kernel, no atomics except the bias LUT) and
-csrc/attn_f32.hip (fp32, the reference's own precision: the same op on the f32-input matrix cores, O(S) memory).
+Kernels: csrc/attn.hip (bf16, head dim 64: forward; backward = dQ kernel + dK/dV kernel, no atomics except the bias
+LUT), csrc/attn_hd.hip (bf16, every other head dim 32 .. 128 that is a multiple of 8: the same op templated on the
+padded head dim) and csrc/attn_f32.hip (fp32 at head dim 64, the reference's own precision: the same op on the
+f32-input matrix cores).  All are O(S) memory.  ``_route`` picks one; what none serves takes the O(Sq·Sk) composite.
 """
 from __future__ import annotations
 
@@ -28,6 +30,7 @@ import math
 import torch
 
 from .. import _ext
+from ..utils.logging import get_logger
 from . import routing
 from . import streams
 from .gemm import colsum_record
@@ -139,10 +142,14 @@ class _AttnFn(torch.autograd.Function):
     def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed, pre=None):
         C = _ext.native()
         q, k, v = _split(mode, a, b, c)
-        if q.dtype == torch.float32:  # csrc/attn_f32.hip
-            o, lse = C.attn_f32_fwd(q, k, v, kpm, lut, float(scale), bool(causal), float(p), int(seed))
+        if q.dtype == torch.float32 or q.shape[-1] != 64:  # csrc/attn_f32.hip / csrc/attn_hd.hip (bf16, D != 64)
+            fwd = C.attn_f32_fwd if q.dtype == torch.float32 else C.attn_hd_fwd
+            o, lse = fwd(q, k, v, kpm, lut, float(scale), bool(causal), float(p), int(seed))
             ctx.save_for_backward(a, b, c, o, lse, lut, kpm, None)
             ctx.cfg = (mode, scale, causal, p, seed, lut is not None and lut.requires_grad, -1, -1)
+            # no column-sum partials off csrc/attn.hip (they hard-code H * 64): the bias gradients of biased
+            # projections come from the separate reduction, as with BIAS_COLSUM = False
+            ctx.cs = (False, False)
             ctx.grad_into = getattr(b, "_dllm_grad_into", None) if mode == "q_kv" else None
             return o
         dmask_in = None
@@ -201,9 +208,10 @@ class _AttnFn(torch.autograd.Function):
                 if ctx.cs[1]:
                     pkv = torch.empty(nk, 2 * HD, **f32)
                     csk, csv = pkv[:, :HD], pkv[:, HD:]
-        if q.dtype == torch.float32:
-            rq, rk, rv, dlut = C.attn_f32_bwd(do.contiguous(), q, k, v, o, lse, kpm, lut, float(scale), bool(causal),
-                                              float(p), int(seed), bool(need_dlut), dq, dk, dv)
+        if q.dtype == torch.float32 or q.shape[-1] != 64:
+            bwd = C.attn_f32_bwd if q.dtype == torch.float32 else C.attn_hd_bwd
+            rq, rk, rv, dlut = bwd(do.contiguous(), q, k, v, o, lse, kpm, lut, float(scale), bool(causal),
+                                   float(p), int(seed), bool(need_dlut), dq, dk, dv)
         else:
             rq, rk, rv, dlut = C.attn_bwd(do.contiguous(), q, k, v, o, lse, kpm, lut, float(scale), bool(causal),
                                           float(p), int(seed), bool(need_dlut), dq, dk, dv, dmask, sat_lo, sat_hi,
@@ -241,24 +249,66 @@ def _prep_kpm(kpm):
     return kpm.contiguous() if kpm is not None else None
 
 
-def _native(t) -> bool:
-    """bf16 -> csrc/attn.hip; fp32 — the reference's own precision (ref/train-torchrun.py:115-128 sets neither bf16
-    nor fp16; Accelerate's default mixed_precision is 'no') — -> csrc/attn_f32.hip (f32-input MFMA, exact f32
-    products).  Head dim 64 (every model this framework builds).  Anything else (CPU, other head dims) takes the
-    composite ``_reference`` below, the exact-math oracle the kernels are tested against.  ops/routing.py ``attn_f32``
-    = 0 sends fp32 to the composite (A/B)."""
-    if not _ext.use_native(t) or t.shape[-1] != 64:
-        return False
-    if t.dtype == torch.bfloat16:
-        return True
-    return t.dtype == torch.float32 and bool(routing.get("attn_f32"))
+_warned: set = set()
+
+
+def _warn_composite(reason: str, t) -> None:
+    """One warning per process and reason when a GPU tensor takes the composite: it is the test oracle, not a kernel."""
+    if reason in _warned:
+        return
+    _warned.add(reason)
+    get_logger().warning(
+        "attention: no HIP kernel for %s (head dim %d, %s); running the composite, which materialises fp32 "
+        "[B, H, Sq, Sk] scores, masks and probabilities: O(Sq*Sk) memory and time.  The kernels take bf16 at head dims "
+        "32 .. 128 that are multiples of 8 with 16-byte aligned rows, and fp32 at head dim 64.",
+        reason, t.shape[-1], str(t.dtype).replace("torch.", ""))
+
+
+def _aligned(t) -> bool:
+    """Row starts of a [..., D] view on 16 bytes (bf16): last dim contiguous, every other stride % 8, base aligned."""
+    return t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
+
+
+def _route(t, *rest):
+    """Which kernel family serves a call whose q (or packed qkv) is ``t`` — by ops/routing.py ``attention_route``:
+
+    * ``"attn.hip"``: bf16, head dim 64 (csrc/attn.hip, the tuned kernels);
+    * ``"attn_hd.hip"``: bf16, any other head dim 32 .. 128 with ``D % 8 == 0`` and 16-byte aligned rows in ``t`` and
+      ``rest`` (csrc/attn_hd.hip; blenderbot-400m has 40, t5-3b / t5-11b / nllb-3.3B 128, blenderbot-3B 80; ``attn_hd``
+      = 0 sends them to the composite, A/B);
+    * ``"attn_f32.hip"``: fp32 at head dim 64 — the reference's own precision (ref/train-torchrun.py:115-128 sets
+      neither bf16 nor fp16; Accelerate's default mixed_precision is 'no') — on the f32-input MFMA (``attn_f32`` = 0
+      sends it to the composite, A/B);
+    * ``None``: the composite ``_reference``, the exact-math oracle the kernels are tested against: CPU tensors,
+      ``DLLM_REFERENCE_OPS=1``, head dims below 32, above 128 or not a multiple of 8, fp32 at head dims other than 64,
+      other dtypes.  On a GPU tensor that is logged once per reason."""
+    if not _ext.use_native(t):
+        return None
+    D = t.shape[-1]
+    bf16 = t.dtype == torch.bfloat16
+    if not bf16 and t.dtype != torch.float32:
+        _warn_composite("this dtype", t)
+        return None
+    r = routing.attention_route(D, bf16)
+    if r == "attn_hd.hip" and not all(_aligned(x) for x in (t,) + rest if x is not None):
+        _warn_composite("unaligned rows", t)
+        return None
+    if r == "composite":
+        if D != 64 and not (bf16 and 32 <= D <= 128 and D % 8 == 0):  # (else: switched off by DLLM_ROUTE)
+            _warn_composite("this head dim" if bf16 else "fp32 at this head dim", t)
+        return None
+    return r
+
+
+def _native(t, *rest) -> bool:
+    return _route(t, *rest) is not None
 
 
 def attention(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_mask=None, bias_lut=None,
               dropout_p: float = 0.0, seed: int = 0):
     """Multi-head attention.  q ``[B,Sq,H,D]``, k/v ``[B,Sk,H,D]``; ``key_padding_mask`` bool
     ``[B,Sk]`` (True = attend); ``bias_lut`` from :func:`relative_bias_lut`."""
-    if _native(q):
+    if _native(q, k, v):
         return _AttnFn.apply("sep", q, k, v, bias_lut, _prep_kpm(key_padding_mask), scale, causal, dropout_p, seed)
     return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed)
 
@@ -280,7 +330,7 @@ def prefetch_dropout_mask(like: torch.Tensor, B: int, H: int, Sq: int, Sk: int, 
     overlapping a projection GEMM issued meanwhile on the compute stream).  Returns a handle for
     ``attention_qkv(pre=...)`` or None.  Not used by the models: the forward hashing the bits itself measured faster
     (profiles/r3_attn_dropout_packed_ab.txt); kept as an API, tested equal to the in-kernel bits."""
-    if p <= 0.0 or not _native(like) or like.dtype != torch.bfloat16:
+    if p <= 0.0 or like.shape[-1] != 64 or like.dtype != torch.bfloat16 or not _native(like):
         return None
     dev = like.device
     side = _SIDE.get(dev)
@@ -295,7 +345,7 @@ def prefetch_dropout_mask(like: torch.Tensor, B: int, H: int, Sq: int, Sk: int, 
 
 def attention_q_kv(q, kv, **kw):
     """Cross-attention with q = [B, Sq, H, D] and the fused key/value projection kv = [B, Sk, 2, H, D]."""
-    if _native(q):
+    if _native(q, kv):
         return _AttnFn.apply("q_kv", q, kv, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
                              kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0))
     return attention(q, kv[:, :, 0], kv[:, :, 1], **kw)

@@ -35,6 +35,9 @@ LM head + cross-entropy        full logits while they fit ``lmhead_full_mb`` (16
                                (auto) when the logits would exceed the budget
 attention                      csrc/attn.hip bf16 flash kernels; fp32 inputs on the fp32      r4_t5base_fp32_b16_summary.txt
                                MFMA kernels of csrc/attn_f32.hip (``attn_f32`` = 1)
+attention, head dim != 64      bf16 at head dims 32 .. 128 (% 8 == 0): csrc/attn_hd.hip      attn_hd_vs_composite.txt
+                               (``attn_hd`` = 1; 0: the O(Sq·Sk) composite); anything
+                               else: the composite, with a one-time warning
 long-context attention         query chunks of ``attn_chunk`` rows from ``attn_chunk_min``   (parallel/context.py)
 weight gradients, small        side stream for micro-batches <= ``wgrad_stream_max_tokens``  r4_wgrad_stream_ab.txt
 micro-batches                  (``wgrad_stream`` = auto | 1 | 0)
@@ -79,6 +82,7 @@ DEFAULTS: dict = {
     "lmhead_chunk_mb": 128.0,
     # attention (ops/attention.py, parallel/context.py)
     "attn_f32": 1,
+    "attn_hd": 1,                 # bf16 head dims 32 .. 128 other than 64 on csrc/attn_hd.hip (0: composite)
     "attn_chunk": 0,              # 0: 8192 rows for < 32 rows per head, else 4096
     "attn_chunk_min": 8192,
     # weight-gradient side stream (ops/streams.py)
@@ -145,9 +149,21 @@ def get(key: str):
     return ov[key] if key in ov else DEFAULTS[key]
 
 
-def plan(model: str, tokens_enc: int, tokens_dec: int, d_model: int, d_ff: int, act: str, vocab: int) -> dict:
+def attention_route(head_dim: int, bf16: bool = True) -> str:
+    """Kernel family of an attention call on the GPU by head dim and dtype (bf16, else fp32): ``"attn.hip"``,
+    ``"attn_hd.hip"``, ``"attn_f32.hip"`` or ``"composite"`` — the rule ops/attention.py ``_route`` applies."""
+    if head_dim == 64:
+        return "attn.hip" if bf16 else ("attn_f32.hip" if get("attn_f32") else "composite")
+    if bf16 and 32 <= head_dim <= 128 and head_dim % 8 == 0 and get("attn_hd"):
+        return "attn_hd.hip"
+    return "composite"
+
+
+def plan(model: str, tokens_enc: int, tokens_dec: int, d_model: int, d_ff: int, act: str, vocab: int, *,
+         head_dim: int = 64) -> dict:
     """What the table routes for one training step of an encoder-decoder model with these shapes (per micro-batch
-    token rows): a dict op -> kernel family, as the tests and docs/ARCHITECTURE.md read it."""
+    token rows): a dict op -> kernel family, as the tests and docs/ARCHITECTURE.md read it.  ``head_dim``: the
+    model's attention head dim (bf16 step)."""
     rows = {"enc": tokens_enc, "dec": tokens_dec}
     out = {}
     dmode = get("proj_dgrad")
@@ -176,5 +192,5 @@ def plan(model: str, tokens_enc: int, tokens_dec: int, d_model: int, d_ff: int, 
     lm = get("lmhead")
     out["lm_head"] = ("w4-fused-ce" if lm == "fused" or (lm == "auto" and logits_mb > get("lmhead_full_mb"))
                       else "hipblaslt+ce")
-    out["attention"] = "attn.hip"
+    out["attention"] = attention_route(head_dim)
     return out

@@ -98,23 +98,41 @@ def _ref_block_bwd(do, q, k, v, o, lse2, kpm, lut, scale, p, seed, need_dlut):
     return dq, dk, dv, dlut
 
 
+def _block_route(q, *rest):
+    """Kernel family of a block call (ops/attention.py ``_route``): csrc/attn.hip at bf16 head dim 64 — the calls
+    this module has always made —, csrc/attn_hd.hip at the other head dims it serves, else None: the plain-torch
+    block functions above (CPU tensors; on the GPU what no block kernel serves, fp32 included)."""
+    from ..ops.attention import _route
+    r = _route(q, *rest)
+    return r if r in ("attn.hip", "attn_hd.hip") else None
+
+
 def _block_fwd(q, k, v, kpm, lut, sat, scale, p, seed):
-    if _ext.use_native(q):
+    r = _block_route(q, k, v)
+    if r == "attn.hip":
         C = _ext.native()
         lo, hi = sat if sat is not None else (-1, -1)
         o, lse, dmask = C.attn_fwd(q, k, v, kpm, lut, float(scale), False, float(p), int(seed), None, lo, hi)
         return o, lse, dmask  # bf16: the fp32 merge promotes (no separate conversion kernels)
+    if r == "attn_hd.hip":  # same LSE units; the backward regenerates the dropout decisions (no keep-bit planes)
+        o, lse = _ext.native().attn_hd_fwd(q, k, v, kpm, lut, float(scale), False, float(p), int(seed))
+        return o, lse, None
     o, lse = _ref_block_fwd(q, k, v, kpm, lut, scale, p, seed)
     return o, lse, None
 
 
 def _block_bwd(do, q, k, v, o, lse, kpm, lut, sat, scale, p, seed, need_dlut, dmask):
-    if _ext.use_native(q):
+    r = _block_route(q, k, v, do, o)
+    if r == "attn.hip":
         C = _ext.native()
         lo, hi = sat if sat is not None else (-1, -1)
         dq, dk, dv, dlut = C.attn_bwd(do, q, k, v, o, lse, kpm, lut, float(scale), False, float(p), int(seed),
                                       bool(need_dlut), None, None, None, dmask, lo, hi)
         return dq, dk, dv, dlut  # bf16; accumulated into fp32 buffers by promoting in-place adds
+    if r == "attn_hd.hip":
+        dq, dk, dv, dlut = _ext.native().attn_hd_bwd(do, q, k, v, o, lse, kpm, lut, float(scale), False, float(p),
+                                                     int(seed), bool(need_dlut))
+        return dq, dk, dv, dlut
     return _ref_block_bwd(do, q, k, v, o, lse, kpm, lut, scale, p, seed, need_dlut)
 
 

@@ -1,4 +1,8 @@
-"""Microbenchmark of the attention kernels at T5/BART training shapes (fwd, bwd, TFLOP/s)."""
+"""Microbenchmark of the attention kernels at T5/BART training shapes (fwd, bwd, TFLOP/s).
+
+``--head-dim D`` runs the cases at another head dim (default 64: csrc/attn.hip; others: csrc/attn_hd.hip).
+``--vs-composite B,H,S,bias,kpm,causal,p`` times forward + backward of the kernel and of the composite
+(``A._reference`` on the same bf16 inputs) interleaved in one process, at ``--head-dim``."""
 import argparse
 import json
 import time
@@ -12,8 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distributed_llms_example_amd.ops import attention as A
 
 
-def run(B, H, Sq, Sk, bias, kpm, causal, p, iters=20, sat=True):
-    D = 64
+def run(B, H, Sq, Sk, bias, kpm, causal, p, iters=20, sat=True, D=64):
     dev = "cuda"
     q = torch.randn(B, Sq, H, D, device=dev, dtype=torch.bfloat16, requires_grad=True)
     k = torch.randn(B, Sk, H, D, device=dev, dtype=torch.bfloat16, requires_grad=True)
@@ -55,15 +58,66 @@ def run(B, H, Sq, Sk, bias, kpm, causal, p, iters=20, sat=True):
     tb = (time.perf_counter() - t0) / iters - tf
     fl = 4 * B * H * Sq * Sk * D * (0.5 if causal else 1.0)
     return {"B": B, "H": H, "Sq": Sq, "Sk": Sk, "bias": bias, "sat": bool(bias and sat), "kpm": kpm,
-            "causal": causal, "p": p,
+            "causal": causal, "p": p, **({"D": D} if D != 64 else {}),
             "fwd_ms": tf * 1e3, "bwd_ms": tb * 1e3, "fwd_tflops": fl / tf / 1e12, "bwd_tflops": 2.5 * fl / tb / 1e12}
+
+
+def vs_composite(B, H, S, bias, kpm, causal, p, D, reps=3, iters=5):
+    """Forward + backward time of ``A.attention`` (the kernel the route picks) and of the composite on the same bf16
+    inputs, interleaved: warm-up, then ``reps`` rounds of ``iters`` calls each, timed with device events."""
+    dev = "cuda"
+    q, k, v = (torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16, requires_grad=True) for _ in range(3))
+    tab = torch.randn(32, H, device=dev) if bias else None
+    lut = A.relative_bias_lut(tab, S, S, not causal, 32, 128) if bias else None
+    mask = torch.ones(B, S, dtype=torch.bool, device=dev) if kpm else None
+    if kpm:
+        mask[:, S - S // 8:] = False
+    scale = 1.0 if bias else D ** -0.5
+    g = torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16)
+
+    def kern():
+        A.attention(q, k, v, scale=scale, causal=causal, key_padding_mask=mask, bias_lut=lut, dropout_p=p,
+                    seed=1).backward(g)
+
+    def comp():
+        A._reference(q, k, v, scale, causal, mask, lut, p, 1).backward(g)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    for fn in (kern, comp, kern, comp):
+        fn()
+    torch.cuda.synchronize()
+    tk, tc = [], []
+    for _ in range(reps):
+        tk.append(timed(kern))
+        tc.append(timed(comp))
+    fl = 3.5 * 4 * B * H * S * S * D * (0.5 if causal else 1.0)
+    route = A._route(q, k, v)
+    return {"B": B, "H": H, "S": S, "D": D, "bias": bias, "kpm": kpm, "causal": causal, "p": p, "route": route,
+            "kernel_ms": [round(t, 4) for t in tk], "composite_ms": [round(t, 4) for t in tc],
+            "kernel_tflops": fl / (sorted(tk)[len(tk) // 2] * 1e-3) / 1e12,
+            "composite_tflops": fl / (sorted(tc)[len(tc) // 2] * 1e-3) / 1e12}
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--ab", action="store_true", help="repeat every case 3x")
+    ap.add_argument("--head-dim", type=int, default=64)
+    ap.add_argument("--vs-composite", default="", help="B,H,S,bias,kpm,causal,p: kernel against the composite")
     a = ap.parse_args()
+    if a.vs_composite:
+        f = a.vs_composite.split(",")
+        print(json.dumps(vs_composite(int(f[0]), int(f[1]), int(f[2]), f[3] == "1", f[4] == "1", f[5] == "1",
+                                      float(f[6]), a.head_dim)), flush=True)
+        sys.exit(0)
     cases = [(32, 12, 1024, 1024, True, True, False, 0.1), (32, 12, 1024, 1024, True, True, False, 0.0),
              (32, 12, 1024, 1024, False, False, False, 0.0), (32, 12, 128, 128, True, False, True, 0.1),
              (32, 12, 128, 1024, False, True, False, 0.1), (16, 16, 1024, 1024, False, True, False, 0.0)]
@@ -72,4 +126,4 @@ if __name__ == "__main__":
     ap2 = a
     for c in cases:
         for rep in range(3 if ap2.ab else 1):
-            print(json.dumps(run(*c)), flush=True)
+            print(json.dumps(run(*c, D=a.head_dim)), flush=True)

@@ -35,8 +35,9 @@ CXX = os.environ.get("CXX", "g++")
 
 # Per-source flags.  attn.hip: no SLP vectorisation — packing independent f32 adds / FMAs into v_pk_* beside MFMAs
 # costs more issue cycles than the scalar ops (MI355X_MICROARCH.md, per-instruction constants) and the compiler adds
-# v_mov shuffles to form the register pairs.
-EXTRA_FLAGS = {"attn.hip": ["-fno-slp-vectorize"]}
+# v_mov shuffles to form the register pairs.  attn_hd.hip: the same, for the same reason — its softmax / dS stage is
+# 16 independent f32 element chains per lane that sit between two MFMA groups.
+EXTRA_FLAGS = {"attn.hip": ["-fno-slp-vectorize"], "attn_hd.hip": ["-fno-slp-vectorize"]}
 # DLLM_HIPFLAGS_EXTRA: extra flags for every HIP source (A/B builds of a kernel variant, e.g. "-DDKDV_PIPE=0"); part
 # of the object key, so switching it back rebuilds the default objects
 _ENV_FLAGS = os.environ.get("DLLM_HIPFLAGS_EXTRA", "").split()
