@@ -138,8 +138,14 @@ std::vector<Tensor> norm_bwd(const optional<Tensor>& dout_o, const optional<Tens
     dse = ds->contiguous();
     TORCH_CHECK(dse.sizes() == s.sizes() && dse.scalar_type() == s.scalar_type(), "ds mismatch");
   }
-  TORCH_CHECK(rstd.numel() == N, "rstd mismatch");
-  if (kind == 1) TORCH_CHECK(mean.has_value() && mean->numel() == N, "mean required for LayerNorm");
+  TORCH_CHECK(d % 4 == 0 && d <= 2048, "norm: d must be a multiple of 4 and <= 2048, got ", d);
+  TORCH_CHECK(w.is_cuda() && w.numel() == d && w.is_contiguous() && w.scalar_type() == s.scalar_type(),
+              "norm weight mismatch");
+  TORCH_CHECK(rstd.is_cuda() && rstd.numel() == N && rstd.is_contiguous() && rstd.scalar_type() == at::kFloat,
+              "rstd mismatch");
+  if (kind == 1)
+    TORCH_CHECK(mean.has_value() && mean->defined() && mean->is_cuda() && mean->numel() == N && mean->is_contiguous() &&
+                    mean->scalar_type() == at::kFloat, "mean required for LayerNorm (fp32 [N])");
   auto dx = at::empty_like(s);
   Tensor dstream = want_stream ? at::empty_like(s) : Tensor();
   const int G = dllm_norm_bwd_grid(N > 0 ? N : 1);
@@ -194,6 +200,7 @@ Tensor act_fwd(const Tensor& x, int64_t act, bool gated, double p, int64_t seed)
 
 Tensor act_bwd(const Tensor& dy_, const Tensor& x, int64_t act, bool gated, double p, int64_t seed) {
   check_gpu(x, "x");
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous(), "act_bwd: x must be contiguous [N, F or 2F]");
   Tensor dy = dy_.contiguous();
   const long N = x.size(0);
   const int F = gated ? x.size(1) / 2 : x.size(1);
@@ -243,10 +250,18 @@ Tensor ce_bwd(const Tensor& scale, Tensor logits, const Tensor& labels, const Te
               const optional<Tensor>& bias, double eps, int64_t ignore, bool inplace) {
   check_gpu(logits, "logits");
   TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.numel() >= 1 && scale.is_cuda(), "ce: scale");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "ce: logits must be contiguous [N, V]");
   const long N = logits.size(0);
   const int V = logits.size(1);
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == N && labels.is_contiguous(),
+              "ce: labels must be int64 [N]");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.numel() == N && lse.is_contiguous(),
+              "ce: lse must be fp32 [N]");
   Tensor bf;
-  if (bias.has_value() && bias->defined()) bf = bias->to(at::kFloat).contiguous();
+  if (bias.has_value() && bias->defined()) {
+    bf = bias->to(at::kFloat).contiguous();
+    TORCH_CHECK(bf.is_cuda() && bf.numel() == V, "ce: bias must have V entries");
+  }
   Tensor out = inplace ? logits : at::empty_like(logits);
   if (N > 0)
     check_rc(dllm_ce_bwd(scale.data_ptr<float>(), logits.data_ptr(), labels.data_ptr<int64_t>(),
@@ -322,10 +337,19 @@ void adamw_step(Tensor param, const optional<Tensor>& master, const Tensor& grad
               "adamw: grad dtype must be the param dtype or fp32");
   check_aligned(grad, 16, "adamw grad");
   TORCH_CHECK(m.scalar_type() == at::kFloat && v.scalar_type() == at::kFloat, "adamw: moments fp32");
-  if (master.has_value() && master->defined())
-    TORCH_CHECK(master->numel() == n && master->scalar_type() == at::kFloat, "adamw: master fp32 [n]");
-  if (wd_mask.has_value() && wd_mask->defined())
-    TORCH_CHECK(wd_mask->numel() == n && wd_mask->scalar_type() == at::kByte, "adamw: wd_mask u8 [n]");
+  // the kernels walk every buffer as one flat array with 16-B (8-B: the mask) vector accesses
+  TORCH_CHECK(grad.is_cuda() && grad.is_contiguous() && m.is_cuda() && m.is_contiguous() && v.is_cuda() &&
+                  v.is_contiguous(), "adamw: grad / moments must be contiguous GPU tensors");
+  if (master.has_value() && master->defined()) {
+    TORCH_CHECK(master->numel() == n && master->scalar_type() == at::kFloat && master->is_cuda() &&
+                    master->is_contiguous(), "adamw: master must be a contiguous fp32 GPU tensor [n]");
+    check_aligned(*master, 16, "adamw master");
+  }
+  if (wd_mask.has_value() && wd_mask->defined()) {
+    TORCH_CHECK(wd_mask->numel() == n && wd_mask->scalar_type() == at::kByte && wd_mask->is_cuda() &&
+                    wd_mask->is_contiguous(), "adamw: wd_mask must be a contiguous u8 GPU tensor [n]");
+    check_aligned(*wd_mask, 8, "adamw wd_mask");
+  }
   TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.is_cuda(), "adamw: coef fp32 device scalar");
   const bool has_hyper = hyper.has_value() && hyper->defined();
   if (has_hyper)
