@@ -43,14 +43,6 @@ using namespace dllm;
 
 DLLM_SEED_STEP_TU(attn)
 
-// output tiles staged through LDS and stored as whole rows (store_rows_staged): forward O, dQ (A/B: -D..._STAGE=0)
-#ifndef FWD_STAGE
-#define FWD_STAGE 1
-#endif
-#ifndef DQ_STAGE
-#define DQ_STAGE 1
-#endif
-
 namespace {
 
 // attention dropout (ops/rng.py attention_keep_mask): the row-Weyl hash of common.h (rw_*) with one row per (b, h,
@@ -145,8 +137,8 @@ DLLM_DEVICE void store_rows_staged(unsigned char* scr, const f32x16& a0, const f
 
 // ================================================================================== dropout bit planes
 // All keep decisions of one attention call, [B*H][n_ktiles][2][sq_pad] words, one thread per word (q fastest:
-// coalesced stores).  Pure VALU + streaming stores, for generating the planes ahead of the forward on a side
-// stream (ops/attention.py prefetch_dropout_mask) where they overlap the projection GEMM.
+// coalesced stores).  Pure VALU + streaming stores: the planes the forward would store, for a caller that runs
+// attn_bwd without that forward (tests/test_kernels_gpu.py checks the ring-attention backward block by block with them).
 __global__ __launch_bounds__(256) void attn_dropout_mask_kernel(AttnParams P, long nwords) {
   for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < nwords; w += (long)gridDim.x * blockDim.x) {
     const int q = (int)(w % P.sq_pad);
@@ -161,17 +153,21 @@ __global__ __launch_bounds__(256) void attn_dropout_mask_kernel(AttnParams P, lo
 }
 
 // ================================================================================== forward
-// DROP_IN: dropout keep bits are read from precomputed planes (attn_dropout_mask_kernel on a side stream);
-// otherwise the forward hashes them itself (hidden in its MFMA/LDS latency) and stores the planes for backward.
+// DROP: the forward hashes the dropout keep bits itself (hidden in its MFMA/LDS latency) and stores the planes for
+// the backward kernels.
 // FNB = K/V ring depth: 3 (two tiles in flight, 2 workgroups per CU) or 2 (one tile in flight, a 2/3-size LDS
 // footprint and a 168-VGPR budget so 3 workgroups share a CU: more waves to hide latency with).
-template <bool HAS_BIAS, bool HAS_KPM, bool CAUSAL, bool DROP, bool DROP_IN, int FNB>
+constexpr int FWD_PAD = 256;  // unused fp32 words per ring slot after the K/V ring (see the kernel's LDS map)
+template <bool HAS_BIAS, bool HAS_KPM, bool CAUSAL, bool DROP, int FNB>
 __global__ __launch_bounds__(256, FNB == 3 ? 2 : 3) void attn_fwd_kernel(AttnParams P) {
   static_assert(FNB == 2 || FNB == 3, "K/V ring depth");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint16_t* KV = reinterpret_cast<uint16_t*>(smem);            // [FNB buffers][K tile | V tile]
-  uint32_t* mwl = reinterpret_cast<uint32_t*>(KV + 2 * FNB * TILE64); // [FNB][4 waves][2 halves][32 rows] keep bits
-  float* kmask = reinterpret_cast<float*>(mwl + FNB * 256);     // [ntiles * 64]: 0 or -inf per key
+  // FWD_PAD: 1 KB per ring slot between the K/V ring and the key mask that nothing reads (it staged keep words read
+  // from precomputed planes, a path that is gone).  It stays because the launcher's choice between the 2- and the
+  // 3-deep ring goes by the LDS footprint (launch_fwd_t): closing the gap moves that threshold and every LDS offset
+  // below, a routing and code change to be made and measured on its own.
+  float* kmask = reinterpret_cast<float*>(KV + 2 * FNB * TILE64) + FNB * FWD_PAD;  // [ntiles * 64]: 0 or -inf per key
   int* tflag = reinterpret_cast<int*>(kmask + P.n_ktiles * FWD_BN);  // [ntiles]: tile has a masked key
   float* lut_s = reinterpret_cast<float*>(tflag + P.n_ktiles);   // [Sk + FWD_BM + FWD_BN], log2-scaled
 
@@ -199,7 +195,6 @@ __global__ __launch_bounds__(256, FNB == 3 ? 2 : 3) void attn_fwd_kernel(AttnPar
   // lane L of DMA j lands at row 8j + L/8, physical chunk L%8 and fetches logical chunk (L%8) ^ swz(row).
   // Keys past Sk re-read row Sk-1 (finite values; masked to -inf / P = 0).  No staging VGPRs, no ds_write.
   const uint32_t kv_lds = lds_addr(KV);
-  const uint32_t mw_lds = lds_addr(mwl);
   // buffer-descriptor DMA: wave-uniform (b, h) bases in SGPRs, per-lane 32-bit byte offsets from one v_mad_u32_u24
   // (the launcher checks strides and lengths fit), instead of 64-bit address arithmetic per DMA
   const uint16_t* kbase_p = P.k + b * P.k_sb + h * P.k_sh;
@@ -221,9 +216,6 @@ __global__ __launch_bounds__(256, FNB == 3 ? 2 : 3) void attn_fwd_kernel(AttnPar
       bld16(kbase_p, __umul24(kk, kss2) + dc16[i], __builtin_amdgcn_readfirstlane(dst));
       bld16(vbase_p, __umul24(kk, vss2) + dc16[i], __builtin_amdgcn_readfirstlane(dst + TILE64 * 2));
     }
-    if (DROP && DROP_IN)  // this wave's 32 rows x 2 lane halves of keep bits: lane L -> half L/32, row qw0 + L%32
-      glds4(P.dmask + ((long)bh * P.n_ktiles * 2 + 2 * kt + hh) * P.sq_pad + qrow,
-            __builtin_amdgcn_readfirstlane(mw_lds + (uint32_t)((buf * 256 + w * 64) * 4)));
   };
   // the first FNB - 1 tiles are issued before the prologue's global reads (bias LUT, Q fragments, key mask) so their
   // latencies overlap instead of adding up
@@ -281,7 +273,6 @@ __global__ __launch_bounds__(256, FNB == 3 ? 2 : 3) void attn_fwd_kernel(AttnPar
   };
   // online softmax of tile kt's scores (in s0/s1) and O^T += V^T P^T with V from buffer `buf`
   auto softmax_pv = [&](int kt, int buf, f32x16& s0, f32x16& s1) __attribute__((always_inline)) {
-    const uint32_t mword = (DROP && DROP_IN) ? mwl[buf * 256 + w * 64 + hh * 32 + r] : 0u;
     const int kbase = kt * FWD_BN;
     const uint16_t* Vb = KV + buf * 2 * TILE64 + TILE64;
     const bool tile_causal = CAUSAL && (kbase + FWD_BN - 1 > qw0 + P.causal_off);
@@ -371,17 +362,10 @@ __global__ __launch_bounds__(256, FNB == 3 ? 2 : 3) void attn_fwd_kernel(AttnPar
         o1[i] *= alpha;
       }
     }
-    if (DROP && DROP_IN) {  // precomputed keep bits; the 1/(1-p) scale is applied once to O at the end
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        s0[i] = __uint_as_float(__float_as_uint(s0[i]) & (uint32_t)__builtin_amdgcn_sbfe((int)mword, keep_bit(0, i), 1));
-        s1[i] = __uint_as_float(__float_as_uint(s1[i]) & (uint32_t)__builtin_amdgcn_sbfe((int)mword, keep_bit(1, i), 1));
-      }
-    }
     // P as bf16 pairs: pk[2 t + half] holds registers 8 half .. 8 half + 7 of s_t; its dword j is one adjacent key pair,
     // pair slot 4 (2 t + half) + j of the keep_bit layout
     bf16x8v pk[4] = {pack8(s0, 0), pack8(s0, 8), pack8(s1, 0), pack8(s1, 8)};
-    if (DROP && !DROP_IN) {
+    if (DROP) {
       // keep decisions applied to the packed pairs (the 1/(1-p) scale is applied once to O at the end) and recorded as
       // one bit word per lane and tile for the backward kernels, which never re-hash.  Per key pair: one add (the
       // Weyl step is a constant), two 24-bit multiplies, two shift-xors, the two-key signed compare (drop_mask2: 2),
@@ -424,8 +408,8 @@ __global__ __launch_bounds__(256, FNB == 3 ? 2 : 3) void attn_fwd_kernel(AttnPar
   auto step = [&](int kt, auto buf_c) __attribute__((always_inline)) {
     constexpr int BUF = decltype(buf_c)::value;
     if (kt > 0) {
-      // tile kt landed (FNB = 3: this wave's 4 DMAs of tile kt+1, issued one tile later, and then either its keep-word
-      // DMA (DROP_IN) or tile kt-1's keep-word store (vmcnt counts stores too) may stay in flight)
+      // tile kt landed (FNB = 3: this wave's 4 DMAs of tile kt+1, issued one tile later, and with dropout tile kt-1's
+      // keep-word store (vmcnt counts stores too) may stay in flight)
       if (FNB == 3 && kt + 1 < ntiles) wait_vm<(DROP ? 5 : 4)>();
       else wait_vm<0>();
       __syncthreads();
@@ -446,30 +430,13 @@ __global__ __launch_bounds__(256, FNB == 3 ? 2 : 3) void attn_fwd_kernel(AttnPar
 
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = l_tot > 0.f ? dscale / l_tot : 0.f;  // dropout's 1/(1-p) folded in
-#if FWD_STAGE
   // every wave is done with the K/V ring (the last tile's DMAs were waited for): its first 16 KB stage the O tiles
   __syncthreads();
   store_rows_staged(smem + w * 4096, o0, o1, inv, r, hh, lane, P.o_out + b * P.o_sb + (long)qw0 * P.o_ss + h * P.o_sh,
                     P.o_ss, P.Sq - qw0);
-#endif
-  if (qvalid) {
-#if !FWD_STAGE
-    uint16_t* op = P.o_out + b * P.o_sb + (long)qrow * P.o_ss + h * P.o_sh;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const f32x16& acc = t == 0 ? o0 : o1;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        u16x4 pk = {f2bf(acc[4 * g] * inv), f2bf(acc[4 * g + 1] * inv), f2bf(acc[4 * g + 2] * inv),
-                    f2bf(acc[4 * g + 3] * inv)};
-        *reinterpret_cast<u16x4*>(op + 32 * t + 8 * g + 4 * hh) = pk;
-      }
-    }
-#endif
-    if (hh == 0) {
-      const float m_use = m_run == -INFINITY ? 0.f : m_run;
-      P.lse[row_g] = l_tot > 0.f ? m_use + log2f(l_tot) : INFINITY;  // log2 units
-    }
+  if (qvalid && hh == 0) {
+    const float m_use = m_run == -INFINITY ? 0.f : m_run;
+    P.lse[row_g] = l_tot > 0.f ? m_use + log2f(l_tot) : INFINITY;  // log2 units
   }
 }
 
@@ -673,7 +640,6 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_kernel(AttnParams P) {
     step(kt, std::integral_constant<int, 0>{});
     if (kt + 1 < ntiles) step(kt + 1, std::integral_constant<int, 1>{});
   }
-#if DQ_STAGE
   // every wave is done with the K/V buffers (the last tile's DMAs were waited for): they stage the dQ tiles
   __syncthreads();
   // column sums: the 4 waves' 64 sums at smem + 16 KB (past the 4 staging tiles, still inside the K/V buffers)
@@ -687,21 +653,6 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_kernel(AttnParams P) {
       P.csq[(long)(b * P.n_tiles + qt) * P.csq_ld + h * 64 + tid] = red[tid] + red[64 + tid] + red[128 + tid] +
                                                                      red[192 + tid];
   }
-#else
-  if (qvalid) {
-    uint16_t* dqp = P.dq + b * P.dq_sb + (long)qrow * P.dq_ss + h * P.dq_sh;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const f32x16& acc = t == 0 ? dq0 : dq1;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        u16x4 pk = {f2bf(acc[4 * g] * P.scale), f2bf(acc[4 * g + 1] * P.scale), f2bf(acc[4 * g + 2] * P.scale),
-                    f2bf(acc[4 * g + 3] * P.scale)};
-        *reinterpret_cast<u16x4*>(dqp + 32 * t + 8 * g + 4 * hh) = pk;
-      }
-    }
-  }
-#endif
 }
 
 // ================================================================================== backward: dK, dV (v2)
@@ -711,23 +662,10 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_kernel(AttnParams P) {
 // 64 rows; v1 moved 32 rows per barrier through registers one tile ahead, and its waves sat parked on the barrier
 // and on the per-score lse / delta arithmetic half the time, profiles/r1_attn_pmc.txt).  Per score (saturated /
 // bias-free tile): P = exp2(fma(s, sl2, rt)), keep = sbfe & dscale bits, Pd = P keep, dS = P fma(dP, keep, -delta).
+// Where the kernel's time goes was measured by ablation builds (no diagonal sums, no LUT reads, no barrier, no MFMAs,
+// no keep bits, no row terms, no exp): profiles/r4_dkdv_ablations.txt.
 constexpr int K2_QT = 64;
-#ifndef DKDV_OPERANDS_AHEAD
-#define DKDV_OPERANDS_AHEAD 1
-#endif
 constexpr int K2_NBUF = 3;
-// timing ablations of the dK/dV kernel (A/B builds only, results are wrong; profiles/r4_dkdv_ablations.txt): 1 no
-// bias-gradient diagonal sums, 2 no LUT bias reads, 4 no stage barrier, 8 no dV/dK MFMAs, 16 no dropout keep bits,
-// 32 no row-term reads, 64 no exp
-#ifndef DKDV_ABLATE
-#define DKDV_ABLATE 0
-#endif
-#ifndef DKDV_SQ_STAGE
-#define DKDV_SQ_STAGE 1
-#endif
-#ifndef DKDV2_STAGE
-#define DKDV2_STAGE 1
-#endif
 constexpr int K2_STAGE = 2 * 64 * D * 2 + 1024 + 1024;  // Q, dO [64][64] bf16 + rowrec [4][64] f32 + keep [4][64] u32
 
 // NB = stage ring depth: 3 (two stages in flight, 2 workgroups per CU) or 2 (one in flight, a 168-VGPR budget so 3
@@ -848,8 +786,7 @@ __global__ __launch_bounds__(256, NB == 3 ? 2 : 3) void attn_bwd_dkdv2_kernel(At
     constexpr int SLOT = decltype(slot_c)::value;
     if (NB == 3 && qt + 1 < nqt) wait_vm<DPT>();
     else wait_vm<0>();
-    if constexpr ((DKDV_ABLATE & 4) == 0)
-      __syncthreads();  // stage qt landed for every wave; every wave is done with stage qt - 1 (the slot refilled next)
+    __syncthreads();  // stage qt landed for every wave; every wave is done with stage qt - 1 (the slot refilled next)
     if (qt + NB - 1 < nqt) issue((SLOT + NB - 1) % NB, qt + NB - 1);
     const unsigned char* stg = smem + SLOT * K2_STAGE;
     const uint16_t* Qb = reinterpret_cast<const uint16_t*>(stg);
@@ -860,8 +797,9 @@ __global__ __launch_bounds__(256, NB == 3 ? 2 : 3) void attn_bwd_dkdv2_kernel(At
     for (int u = 0; u < 2; ++u) {
       const int q0 = qt * K2_QT + 32 * u;
       f32x16 sacc = {}, dpacc = {};
-      if constexpr (NB == 3 && DKDV_OPERANDS_AHEAD) {
-        // all 8 operand rows in flight before the first MFMA (one LDS round trip; hipcc otherwise waits before each)
+      if constexpr (NB == 3) {
+        // all 8 operand rows in flight before the first MFMA (one LDS round trip; hipcc otherwise waits before each);
+        // the 2-deep ring has no registers to hold them ahead
         bf16x8v qa[4], da[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -883,7 +821,7 @@ __global__ __launch_bounds__(256, NB == 3 ? 2 : 3) void attn_bwd_dkdv2_kernel(At
       }
       const int sat = !HAS_BIAS ? 0
                       : (kw0 + 31 - q0 + P.Sq - 1 <= P.sat_lo ? 1 : (kw0 - q0 - 31 + P.Sq - 1 >= P.sat_hi ? 2 : 0));
-      const bool use_lut = HAS_BIAS && sat == 0 && (DKDV_ABLATE & 2) == 0;
+      const bool use_lut = HAS_BIAS && sat == 0;
       f32x16 pd, ds;
       if constexpr (NB == 3) {  // all 16 row terms read up front: their LDS latency hides under the MFMAs
         // rows 32u + crow(i, hh): four consecutive rows per 16-B read
@@ -893,17 +831,14 @@ __global__ __launch_bounds__(256, NB == 3 ? 2 : 3) void attn_bwd_dkdv2_kernel(At
         uint32_t mw[16];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          f32x4 a = {0.f, -1.f, 0.5f, 0.25f}, c = a;
-          if constexpr ((DKDV_ABLATE & 32) == 0) {
-            a = *reinterpret_cast<const f32x4*>(rt_row + 8 * g);
-            c = *reinterpret_cast<const f32x4*>(nd_row + 8 * g);
-          }
+          const f32x4 a = *reinterpret_cast<const f32x4*>(rt_row + 8 * g);
+          const f32x4 c = *reinterpret_cast<const f32x4*>(nd_row + 8 * g);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             rt[4 * g + e] = a[e];
             nd[4 * g + e] = c[e];
           }
-          if (DROP && (DKDV_ABLATE & 16) == 0) {
+          if (DROP) {
             const u32x4 v = *reinterpret_cast<const u32x4*>(mwd + mcol * 64 + 32 * u + 8 * g + 4 * hh);
 #pragma unroll
             for (int e = 0; e < 4; ++e) mw[4 * g + e] = v[e];
@@ -928,10 +863,10 @@ __global__ __launch_bounds__(256, NB == 3 ? 2 : 3) void attn_bwd_dkdv2_kernel(At
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const float x = fmaf(sacc[i], sl2, rt[i]);
-          float pr = (DKDV_ABLATE & 64) ? x : fast_exp2(x);  // rows >= Sq: rt = -inf -> 0
+          float pr = fast_exp2(x);  // rows >= Sq: rt = -inf -> 0
           if (CAUSAL && tile_causal && key > q0 + crow(i, hh) + P.causal_off) pr = 0.f;
           float keepf = 1.f;
-          if (DROP && (DKDV_ABLATE & 16) == 0) keepf = __uint_as_float((uint32_t)__builtin_amdgcn_sbfe((int)mw[i], mbit, 1) & dsbits);
+          if (DROP) keepf = __uint_as_float((uint32_t)__builtin_amdgcn_sbfe((int)mw[i], mbit, 1) & dsbits);
           pd[i] = pr * keepf;
           ds[i] = pr * fmaf(dpacc[i], keepf, nd[i]);
         }
@@ -971,7 +906,7 @@ __global__ __launch_bounds__(256, NB == 3 ? 2 : 3) void attn_bwd_dkdv2_kernel(At
         for (int i = 0; i < 16; ++i) t += ds[i];
         if (sat == 1) sat_acc_lo += t;
         else sat_acc_hi += t;
-      } else if (HAS_BIAS && (DKDV_ABLATE & 1) == 0) {
+      } else if (HAS_BIAS) {
         // diagonal sums of the wave's 32x32 dS tile: rotate register i (row rho = crow(i, hh)) left by rho
         // lanes so lane r receives element (rho, (r + rho) & 31) whose diagonal (col - row) is r or r - 32.
         // The rotations go out in batches of 8 before any is consumed (one LDS round trip per batch: issued one by one,
@@ -998,9 +933,7 @@ __global__ __launch_bounds__(256, NB == 3 ? 2 : 3) void attn_bwd_dkdv2_kernel(At
         atomicAdd(&dlut_s[la < 0 ? 0 : la], va);  // la < 0: rows past Sq only (dS = 0)
       }
       const bf16x8v pf0 = pack8(pd, 0), pf1 = pack8(pd, 8), sf0 = pack8(ds, 0), sf1 = pack8(ds, 8);
-      if constexpr ((DKDV_ABLATE & 8) != 0) {
-        asm volatile("" ::"v"(pf0), "v"(pf1), "v"(sf0), "v"(sf1));
-      } else if constexpr (NB == 3 && DKDV_OPERANDS_AHEAD) {  // the 8 transposed operands (16 reads) in flight together
+      if constexpr (NB == 3) {  // the 8 transposed operands (16 reads) in flight together
         bf16x8v ot[2][2], qtr[2][2];
 #pragma unroll
         for (int sp = 0; sp < 2; ++sp) {
@@ -1041,7 +974,6 @@ __global__ __launch_bounds__(256, NB == 3 ? 2 : 3) void attn_bwd_dkdv2_kernel(At
     }
   }
 
-#if DKDV2_STAGE
   {
     // every wave is done with the stage ring (its last stage drained the DMAs): reuse it to stage the wave's 32 x 64 dK
     // and dV tiles (16-B chunks XOR-swizzled by row) and store whole 128-B key rows, 8 full-line stores per wave
@@ -1095,25 +1027,6 @@ __global__ __launch_bounds__(256, NB == 3 ? 2 : 3) void attn_bwd_dkdv2_kernel(At
       }
     }
   }
-#else
-  if (kvalid) {
-    uint16_t* dkp = P.dk + b * P.dk_sb + (long)key * P.dk_ss + h * P.dk_sh;
-    uint16_t* dvp = P.dv + b * P.dv_sb + (long)key * P.dv_ss + h * P.dv_sh;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const f32x16& ak = t == 0 ? dk0 : dk1;
-      const f32x16& av = t == 0 ? dv0 : dv1;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        u16x4 pk = {f2bf(ak[4 * g] * P.scale), f2bf(ak[4 * g + 1] * P.scale), f2bf(ak[4 * g + 2] * P.scale),
-                    f2bf(ak[4 * g + 3] * P.scale)};
-        u16x4 pv = {f2bf(av[4 * g]), f2bf(av[4 * g + 1]), f2bf(av[4 * g + 2]), f2bf(av[4 * g + 3])};
-        *reinterpret_cast<u16x4*>(dkp + 32 * t + 8 * g + 4 * hh) = pk;
-        *reinterpret_cast<u16x4*>(dvp + 32 * t + 8 * g + 4 * hh) = pv;
-      }
-    }
-  }
-#endif
   if (HAS_BIAS) {
     __syncthreads();
     float* grow = P.dlut + (long)h * L;
@@ -1141,7 +1054,7 @@ template <bool HAS_KPM, bool DROP, int MB, bool CS = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // [2 stages of K2_STAGE: Q | dO | row terms (1 KB) | unused], keep words [2 parities][2 stages][1 KB], key mask [128],
-  // (DKDV_SQ_STAGE) per-wave 8 KB store staging
+  // per-wave 8 KB store staging, column-sum scratch (2 KB)
   const uint32_t* keepb = reinterpret_cast<const uint32_t*>(smem + 2 * K2_STAGE);
   float* kmask = reinterpret_cast<float*>(smem + 2 * K2_STAGE + 4096);
 
@@ -1229,7 +1142,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
   __syncthreads();
   for (int kb = kb_begin; kb < kb_end; ++kb) {
     const int par = (kb - kb_begin) & 1;
-    const int key = kb * BWD_BK + kl;
     if (tid < BWD_BK) kmask[tid] = key_ok ? 0.f : -INFINITY;
     const bool block_live = !HAS_KPM || __syncthreads_or(key_ok ? 1 : 0);
     const bool block_masked = __syncthreads_or((tid < BWD_BK && !key_ok) ? 1 : 0);
@@ -1290,7 +1202,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
     }
     wait_vm<0>();
     __syncthreads();
-#if DKDV_SQ_STAGE
     {
       // the wave's 32 x 64 dK and dV tiles through its LDS scratch (16-B chunks XOR-swizzled by row), then whole
       // 128-B key rows: 8 full-line stores per wave instead of 16 stores of 16 B into 32 lines each
@@ -1342,25 +1253,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
         }
       }
     }
-#else
-    if (key < P.Sk) {
-      uint16_t* dkp = P.dk + b * P.dk_sb + (long)key * P.dk_ss + h * P.dk_sh;
-      uint16_t* dvp = P.dv + b * P.dv_sb + (long)key * P.dv_ss + h * P.dv_sh;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const f32x16& ak = t == 0 ? dk0 : dk1;
-        const f32x16& av = t == 0 ? dv0 : dv1;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          u16x4 pk = {f2bf(ak[4 * g] * P.scale), f2bf(ak[4 * g + 1] * P.scale), f2bf(ak[4 * g + 2] * P.scale),
-                      f2bf(ak[4 * g + 3] * P.scale)};
-          u16x4 pv = {f2bf(av[4 * g]), f2bf(av[4 * g + 1]), f2bf(av[4 * g + 2]), f2bf(av[4 * g + 3])};
-          *reinterpret_cast<u16x4*>(dkp + 32 * t + 8 * g + 4 * hh) = pk;
-          *reinterpret_cast<u16x4*>(dvp + 32 * t + 8 * g + 4 * hh) = pv;
-        }
-      }
-    }
-#endif
     if (more) {
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
@@ -1388,20 +1280,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
 
 template <bool HB, bool HK, bool CA, bool DR>
 void launch_fwd_t(const AttnParams& p, int nblk, size_t lds, hipStream_t st) {
-  // lds was sized for the 3-deep ring; the 2-deep one drops one K/V buffer pair and one keep-bit slot
-  const size_t lds2 = lds - (size_t)2 * TILE64 * 2 - 256 * 4;
+  // lds was sized for the 3-deep ring; the 2-deep one drops one K/V buffer pair and one pad slot
+  const size_t lds2 = lds - (size_t)2 * TILE64 * 2 - FWD_PAD * 4;
   // 3 workgroups per CU on the 2-deep ring: t5-base encoder forward -10 % (profiles/r2_attn_fwd_occ3.txt)
-  if (3 * lds2 <= 160 * 1024) {
-    if (DR && p.dmask_ready)
-      hipLaunchKernelGGL((attn_fwd_kernel<HB, HK, CA, DR, true, 2>), dim3(nblk), dim3(256), lds2, st, p);
-    else
-      hipLaunchKernelGGL((attn_fwd_kernel<HB, HK, CA, DR, false, 2>), dim3(nblk), dim3(256), lds2, st, p);
-    return;
-  }
-  if (DR && p.dmask_ready)
-    hipLaunchKernelGGL((attn_fwd_kernel<HB, HK, CA, DR, true, 3>), dim3(nblk), dim3(256), lds, st, p);
+  if (3 * lds2 <= 160 * 1024)
+    hipLaunchKernelGGL((attn_fwd_kernel<HB, HK, CA, DR, 2>), dim3(nblk), dim3(256), lds2, st, p);
   else
-    hipLaunchKernelGGL((attn_fwd_kernel<HB, HK, CA, DR, false, 3>), dim3(nblk), dim3(256), lds, st, p);
+    hipLaunchKernelGGL((attn_fwd_kernel<HB, HK, CA, DR, 3>), dim3(nblk), dim3(256), lds, st, p);
 }
 template <bool HB, bool HK, bool CA, bool DR>
 void launch_bwd_dq_t(const AttnParams& p, int nblk, size_t lds, hipStream_t st) {
@@ -1490,8 +1375,8 @@ extern "C" int dllm_attn_fwd(AttnParams* pp, hipStream_t st) {
   p.n_ktiles = (p.Sk + FWD_BN - 1) / FWD_BN;
   p.sq_pad = p.n_tiles * FWD_BM;
   if (p.p_drop > 0.f && p.dmask == nullptr) return -5;  // the caller allocates the dropout bit planes
-  // 3 K/V buffers + per-key mask + bias LUT window
-  size_t lds = (size_t)6 * TILE64 * 2 + 3 * 256 * 4 + (size_t)p.n_ktiles * (FWD_BN + 1) * 4;
+  // 3 K/V buffers (+ pad) + per-key mask + bias LUT window
+  size_t lds = (size_t)6 * TILE64 * 2 + 3 * FWD_PAD * 4 + (size_t)p.n_ktiles * (FWD_BN + 1) * 4;
   if (p.lut) lds += (size_t)(p.Sk + FWD_BM + FWD_BN) * 4;
   if (nblk <= 0 || nblk > 0x7fffffff || lds > 160 * 1024) return -4;
   DISPATCH4(launch_fwd_t, p.lut != nullptr, p.kpm != nullptr, p.causal != 0, p.p_drop > 0.f, p, (int)nblk, lds, st);
@@ -1508,11 +1393,9 @@ extern "C" int dllm_attn_bwd(AttnParams* pp, hipStream_t st) {
   p.n_ktiles = (p.Sk + FWD_BN - 1) / FWD_BN;
   p.sq_pad = p.n_tiles * FWD_BM;
   if (p.p_drop > 0.f && p.dmask == nullptr) return -5;
-  // column sums need the staged stores of all three kernels (and the v2 / short-query dK/dV kernels)
-  // (the column-sum variants are instantiated for the bias-LUT-free kernels only)
-  if ((p.csq != nullptr || p.csk != nullptr) &&
-      (!DQ_STAGE || !DKDV2_STAGE || !DKDV_SQ_STAGE || p.rowrec == nullptr || p.lut != nullptr))
-    return -7;
+  // column sums ride on the kernels' staged row stores; their variants are instantiated for the bias-LUT-free
+  // kernels only
+  if ((p.csq != nullptr || p.csk != nullptr) && (p.rowrec == nullptr || p.lut != nullptr)) return -7;
   if ((p.csk == nullptr) != (p.csv == nullptr)) return -7;
   long nblk = (long)p.n_tiles * p.H * p.B;
   // 2 K/V buffers + per-key mask + tile flags + bias LUT window
@@ -1543,7 +1426,7 @@ extern "C" int dllm_attn_bwd(AttnParams* pp, hipStream_t st) {
   for (int m = 8; m >= 2; m /= 2)
     if (m <= sq_cap && mb == 0 && (force || (long)((p.n_tiles + m - 1) / m) * p.H * p.B >= 6L * cus)) mb = m;
   if (p.rowrec != nullptr && p.lut == nullptr && !p.causal && p.Sq <= 2 * K2_QT && mb > 1 && p.n_tiles >= 2) {
-    const size_t lds_sq = (size_t)2 * K2_STAGE + 4096 + BWD_BK * 4 + (DKDV_SQ_STAGE ? 4 * 8192 + 2048 : 0);
+    const size_t lds_sq = (size_t)2 * K2_STAGE + 4096 + BWD_BK * 4 + 4 * 8192 + 2048;
     if ((long)((p.n_tiles + mb - 1) / mb) * p.H * p.B > 0x7fffffff) return -4;
     if (p.kpm != nullptr) {
       if (p.p_drop > 0.f) launch_bwd_dkdv_sq_t<true, true>(p, mb, lds_sq, st);
@@ -1580,5 +1463,3 @@ extern "C" int dllm_attn_dropout_mask(AttnParams* pp, hipStream_t st) {
   DLLM_CHECK_LAUNCH();
   return 0;
 }
-
-extern "C" int dllm_attn_params_size() { return (int)sizeof(AttnParams); }

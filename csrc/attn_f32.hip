@@ -18,8 +18,8 @@
 //              summed per diagonal of the block's dS tile in LDS and added to dlut once per block (fp32 atomics).
 //   dK / dV    grid (Sk/64, B*H), 4 waves x 16 keys: S = Q K^T, dP = dO V^T, dV += P_kept^T dO, dK += dS^T Q.
 #include "common.h"
-
-#include "attn_f32_params.h"
+#include "attn_params.h"
+#include "attn_small.h"
 
 using namespace dllm;
 
@@ -27,33 +27,9 @@ DLLM_SEED_STEP_TU(attn_f32)
 
 namespace {
 
-constexpr int D = 64, BQ = 64, BKY = 64, NT = 256;
-constexpr uint32_t C24 = 0x9E3779u, C24B = 0x85EBCBu, HG = 0x9E3779B1u;  // ops/rng.py attention_keep_mask
+constexpr int D = 64;
 
 DLLM_DEVICE f32x4 mma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// keep decision of key j of the row whose hash is rh (ops/rng.py attention_keep_mask, bit-exact)
-DLLM_DEVICE bool keep_key(uint32_t rh, int j, uint32_t thr) {
-  const uint32_t g = __umul24(rh, C24) + (uint32_t)(j >> 1) * HG;
-  const uint32_t hh = __umul24(g ^ (g >> 15), C24B);
-  const uint32_t y = hh ^ (hh >> 16);
-  const uint32_t half = (j & 1) ? (y >> 16) : (y & 0xFFFFu);
-  return (half ^ 0x8000u) >= thr;
-}
-// keep bits of keys j0 .. j0 + 3 (j0 % 4 == 0): bit i <-> key j0 + i; two hashes (one per key pair)
-DLLM_DEVICE uint32_t keep4(uint32_t rh, int j0, uint32_t thr) {
-  const uint32_t g0 = __umul24(rh, C24) + (uint32_t)(j0 >> 1) * HG;
-  uint32_t bits = 0;
-#pragma unroll
-  for (int pp = 0; pp < 2; ++pp) {
-    const uint32_t g = g0 + (uint32_t)pp * HG;
-    const uint32_t hh = __umul24(g ^ (g >> 15), C24B);
-    const uint32_t y = hh ^ (hh >> 16);
-    bits |= (((y & 0xFFFFu) ^ 0x8000u) >= thr ? 1u : 0u) << (2 * pp);
-    bits |= (((y >> 16) ^ 0x8000u) >= thr ? 1u : 0u) << (2 * pp + 1);
-  }
-  return bits;
-}
 
 // [64][64] fp32 image, row-major, 16-B chunks XOR-swizzled by (row & 15)
 DLLM_DEVICE int rm_off(int r, int c4) { return r * 64 + ((c4 ^ (r & 15)) << 2); }
@@ -95,20 +71,6 @@ DLLM_DEVICE f32x4 rd_col4(const float* tr, int col, int r4) {
   return *reinterpret_cast<const f32x4*>(tr + col * 64 + ((((r4 >> 2) ^ (col & 15))) << 2));
 }
 
-DLLM_DEVICE float grp_max(float v) {  // over the 4 lane groups (same lane & 15)
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-DLLM_DEVICE float grp_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-
-// key in range and not padding (the causal test is per (row, key), done by the callers)
-DLLM_DEVICE bool key_ok(const AttnF32Params& P, int b, int key) {
-  return key < P.Sk && (P.kpm == nullptr || P.kpm[(long)b * P.Sk + key] != 0);
-}
-
 // ================================================================================================ forward
 template <bool DROP>
 __global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(AttnF32Params P) {
@@ -121,7 +83,6 @@ __global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(AttnF32Params P) {
   const int q0 = blockIdx.x * BQ;
   const int row = q0 + 16 * w + c;
   const int rowc = min(row, P.Sq - 1);
-  const long L = (long)P.Sq + P.Sk - 1;
   float qf[16];
   {
     const float* qp = P.q + (long)b * P.q_sb + (long)rowc * P.q_ss + (long)h * P.q_sh + 16 * g;
@@ -148,11 +109,7 @@ __global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(AttnF32Params P) {
     __syncthreads();  // the previous block's LDS reads are done
     stage<true, false>(kb, P.k_ss, k0, P.Sk, Ks, nullptr, tid);
     stage<false, true>(vb, P.v_ss, k0, P.Sk, nullptr, Vt, tid);
-    if (P.lut && tid < 2 * BKY - 1) {  // bias of (key, row) at Ls[key - row - (k0 - q0 - 63)]
-      long idx = (long)k0 - q0 - 63 + tid + P.Sq - 1;
-      idx = idx < 0 ? 0 : (idx >= L ? L - 1 : idx);
-      Ls[tid] = P.lut[(long)h * L + idx];
-    }
+    stage_bias(P, h, q0, k0, Ls, tid, 1.f);
     if (tid < BKY) Mk[tid] = key_ok(P, b, k0 + tid);
     __syncthreads();
     f32x4 st[4];
@@ -254,7 +211,6 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(AttnF32Params P) {
   const int row = q0 + 16 * w + c;
   const int rowc = min(row, P.Sq - 1);
   const bool row_ok = row < P.Sq;
-  const long L = (long)P.Sq + P.Sk - 1;
   float qf[16], dof[16];
   {
     const float* qp = P.q + (long)b * P.q_sb + (long)rowc * P.q_ss + (long)h * P.q_sh + 16 * g;
@@ -283,11 +239,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(AttnF32Params P) {
     __syncthreads();
     stage<true, true>(kb, P.k_ss, k0, P.Sk, Ks, Kt, tid);
     stage<true, false>(vb, P.v_ss, k0, P.Sk, Vs, nullptr, tid);
-    if (P.lut && tid < 2 * BKY - 1) {
-      long idx = (long)k0 - q0 - 63 + tid + P.Sq - 1;
-      idx = idx < 0 ? 0 : (idx >= L ? L - 1 : idx);
-      Ls[tid] = P.lut[(long)h * L + idx];
-    }
+    stage_bias(P, h, q0, k0, Ls, tid, 1.f);
     if (tid < BKY) Mk[tid] = key_ok(P, b, k0 + tid);
     __syncthreads();
     f32x4 st[4], dpt[4];
@@ -333,17 +285,8 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(AttnF32Params P) {
       }
     }
     if (want_dlut) {
-      // bias gradient: per diagonal d = key - row + 63 of the 64x64 block, one thread walks its diagonal in the dS
-      // tile (LDS reads, no atomics) and adds the sum to dlut once
-      __syncthreads();
-      if (tid < 2 * BKY - 1) {
-        const int d = tid;
-        const int r0 = d < 63 ? 63 - d : 0, r1 = d < 63 ? 63 : 126 - d;
-        float v = 0.f;
-        for (int r = r0; r <= r1; ++r) v += Ds[r * (BKY + 1) + r + d - 63];
-        const long idx = (long)k0 - q0 - 63 + d + P.Sq - 1;
-        if (v != 0.f && idx >= 0 && idx < L) atomicAdd(&P.dlut[(long)h * L + idx], v);
-      }
+      __syncthreads();  // the block's dS tile is complete
+      dlut_add_diagonals(P, h, q0, k0, Ds, tid);
     }
   }
   if (row_ok) {
@@ -367,7 +310,6 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(AttnF32Params P) {
   const int k0 = blockIdx.x * BKY;
   const int key = k0 + 16 * w + c;
   const int keyc = min(key, P.Sk - 1);
-  const long L = (long)P.Sq + P.Sk - 1;
   float kf[16], vf[16];
   {
     const float* kp = P.k + (long)b * P.k_sb + (long)keyc * P.k_ss + (long)h * P.k_sh + 16 * g;
@@ -397,11 +339,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(AttnF32Params P) {
     __syncthreads();
     stage<true, true>(qb, P.q_ss, q0, P.Sq, Qs, Qt, tid);
     stage<true, true>(ob, P.do_ss, q0, P.Sq, Os, Ot, tid);
-    if (P.lut && tid < 2 * BQ - 1) {  // bias of (key, row) at Ls[key - row - (k0 - q0 - 63)]
-      long idx = (long)k0 - q0 - 63 + tid + P.Sq - 1;
-      idx = idx < 0 ? 0 : (idx >= L ? L - 1 : idx);
-      Ls[tid] = P.lut[(long)h * L + idx];
-    }
+    stage_bias(P, h, q0, k0, Ls, tid, 1.f);
     if (tid < BQ) {
       const int r = q0 + tid;
       const bool ok = r < P.Sq;

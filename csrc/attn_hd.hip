@@ -24,8 +24,8 @@
 //              summed per diagonal of the block's dS tile in LDS and added to dlut once per block (fp32 atomics).
 //   dK / dV    grid (Sk/64, B*H), 4 waves x 16 keys: S = Q K^T, dP = dO V^T, dV^T += dO^T P_kept, dK^T += Q^T dS.
 #include "common.h"
-
-#include "attn_hd_params.h"
+#include "attn_params.h"
+#include "attn_small.h"
 
 using namespace dllm;
 
@@ -33,37 +33,12 @@ DLLM_SEED_STEP_TU(attn_hd)
 
 namespace {
 
-constexpr int BQ = 64, BKY = 64, NT = 256;
-constexpr uint32_t C24 = 0x9E3779u, C24B = 0x85EBCBu, HG = 0x9E3779B1u;  // ops/rng.py attention_keep_mask
 constexpr float LOG2E = 1.4426950408889634f;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8v;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 DLLM_DEVICE f32x4 mma(bf16x8v a, bf16x8v b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
-// keep decision of key j of the row whose hash is rh (ops/rng.py attention_keep_mask, bit-exact; as csrc/attn_f32.hip)
-DLLM_DEVICE bool keep_key(uint32_t rh, int j, uint32_t thr) {
-  const uint32_t g = __umul24(rh, C24) + (uint32_t)(j >> 1) * HG;
-  const uint32_t hh = __umul24(g ^ (g >> 15), C24B);
-  const uint32_t y = hh ^ (hh >> 16);
-  const uint32_t half = (j & 1) ? (y >> 16) : (y & 0xFFFFu);
-  return (half ^ 0x8000u) >= thr;
-}
-// keep bits of keys j0 .. j0 + 3 (j0 % 4 == 0): bit i <-> key j0 + i; two hashes (one per key pair)
-DLLM_DEVICE uint32_t keep4(uint32_t rh, int j0, uint32_t thr) {
-  const uint32_t g0 = __umul24(rh, C24) + (uint32_t)(j0 >> 1) * HG;
-  uint32_t bits = 0;
-#pragma unroll
-  for (int pp = 0; pp < 2; ++pp) {
-    const uint32_t g = g0 + (uint32_t)pp * HG;
-    const uint32_t hh = __umul24(g ^ (g >> 15), C24B);
-    const uint32_t y = hh ^ (hh >> 16);
-    bits |= (((y & 0xFFFFu) ^ 0x8000u) >= thr ? 1u : 0u) << (2 * pp);
-    bits |= (((y >> 16) ^ 0x8000u) >= thr ? 1u : 0u) << (2 * pp + 1);
-  }
-  return bits;
-}
 
 DLLM_DEVICE float ex2(float x) { return __builtin_amdgcn_exp2f(x); }  // v_exp_f32: exp2(-inf) = 0
 
@@ -126,30 +101,6 @@ DLLM_DEVICE bf16x8v pack8(f32x4 a, f32x4 b) {
   return __builtin_bit_cast(bf16x8v, r);
 }
 
-DLLM_DEVICE float grp_max(float v) {  // over the 4 lane groups (same lane & 15)
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-DLLM_DEVICE float grp_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-
-// key in range and not padding (the causal test is per (row, key), done by the callers)
-DLLM_DEVICE bool key_ok(const AttnHdParams& P, int b, int key) {
-  return key < P.Sk && (P.kpm == nullptr || P.kpm[(long)b * P.Sk + key] != 0);
-}
-
-// bias window of the (q0, k0) block in log2 units: bias of (key, row) at Ls[key - row - (k0 - q0 - 63)]
-DLLM_DEVICE void stage_bias(const AttnHdParams& P, int h, int q0, int k0, float* Ls, int tid) {
-  if (P.lut && tid < 2 * BKY - 1) {
-    const long L = (long)P.Sq + P.Sk - 1;
-    long idx = (long)k0 - q0 - 63 + tid + P.Sq - 1;
-    idx = idx < 0 ? 0 : (idx >= L ? L - 1 : idx);
-    Ls[tid] = P.lut[(long)h * L + idx] * LOG2E;
-  }
-}
-
 // 4 bf16 of an accumulator tile to columns d0 .. d0 + 3 of a row (8-B store)
 DLLM_DEVICE void st4(uint16_t* p, f32x4 v) { Elem<uint16_t>::store4(p, v); }
 
@@ -183,7 +134,7 @@ __global__ __launch_bounds__(NT) void attn_hd_fwd_kernel(AttnHdParams P) {
     __syncthreads();  // the previous block's LDS reads are done
     stage<DP>(kb, P.k_ss, k0, P.Sk, P.D, Ks, tid);
     stage<DP>(vb, P.v_ss, k0, P.Sk, P.D, Vs, tid);
-    stage_bias(P, h, q0, k0, Ls, tid);
+    stage_bias(P, h, q0, k0, Ls, tid, LOG2E);
     if (tid < BKY) Mk[tid] = key_ok(P, b, k0 + tid);
     __syncthreads();
     f32x4 st[4];
@@ -281,7 +232,6 @@ __global__ __launch_bounds__(NT) void attn_hd_dq_kernel(AttnHdParams P) {
   const int row = q0 + 16 * w + c;
   const int rowc = min(row, P.Sq - 1);
   const bool row_ok = row < P.Sq;
-  const long L = (long)P.Sq + P.Sk - 1;
   bf16x8v qf[KS], dof[KS];
   load_row_frags<DP>(P.q + (long)b * P.q_sb + (long)rowc * P.q_ss + (long)h * P.q_sh, g, P.D, qf);
   load_row_frags<DP>(P.dout + (long)b * P.do_sb + (long)rowc * P.do_ss + (long)h * P.do_sh, g, P.D, dof);
@@ -302,7 +252,7 @@ __global__ __launch_bounds__(NT) void attn_hd_dq_kernel(AttnHdParams P) {
     __syncthreads();
     stage<DP>(kb, P.k_ss, k0, P.Sk, P.D, Ks, tid);
     stage<DP>(vb, P.v_ss, k0, P.Sk, P.D, Vs, tid);
-    stage_bias(P, h, q0, k0, Ls, tid);
+    stage_bias(P, h, q0, k0, Ls, tid, LOG2E);
     if (tid < BKY) Mk[tid] = key_ok(P, b, k0 + tid);
     __syncthreads();
     f32x4 st[4], dpt[4];
@@ -340,17 +290,8 @@ __global__ __launch_bounds__(NT) void attn_hd_dq_kernel(AttnHdParams P) {
       for (int dt = 0; dt < DT; ++dt) acc[dt] = mma(ld_tr2<DP>(Ks, 32 * u, 16 * dt, c, g), sb, acc[dt]);
     }
     if (want_dlut) {
-      // bias gradient: per diagonal d = key - row + 63 of the 64x64 block, one thread walks its diagonal in the dS
-      // tile (LDS reads, no atomics) and adds the sum to dlut once
-      __syncthreads();
-      if (tid < 2 * BKY - 1) {
-        const int d = tid;
-        const int r0 = d < 63 ? 63 - d : 0, r1 = d < 63 ? 63 : 126 - d;
-        float v = 0.f;
-        for (int r = r0; r <= r1; ++r) v += Ds[r * (BKY + 1) + r + d - 63];
-        const long idx = (long)k0 - q0 - 63 + d + P.Sq - 1;
-        if (v != 0.f && idx >= 0 && idx < L) atomicAdd(&P.dlut[(long)h * L + idx], v);
-      }
+      __syncthreads();  // the block's dS tile is complete
+      dlut_add_diagonals(P, h, q0, k0, Ds, tid);
     }
   }
   // acc[dt][i] = dQ[row][d = 16 dt + 4 g + i] / scale
@@ -396,7 +337,7 @@ __global__ __launch_bounds__(NT) void attn_hd_dkdv_kernel(AttnHdParams P) {
     __syncthreads();
     stage<DP>(qb, P.q_ss, q0, P.Sq, P.D, Qs, tid);
     stage<DP>(ob, P.do_ss, q0, P.Sq, P.D, Os, tid);
-    stage_bias(P, h, q0, k0, Ls, tid);
+    stage_bias(P, h, q0, k0, Ls, tid, LOG2E);
     if (tid < BQ) {
       const int r = q0 + tid;
       const bool ok = r < P.Sq;

@@ -1,44 +1,67 @@
-// Parameter block for the attention kernels (csrc/attn.hip), filled by the host binding.
+// The attention contract: one parameter block for the three kernel families, filled by the host binding
+// (csrc/bind.cpp fill_common / fill_bwd) and passed by value to every kernel.
+//
+//   AttnParamsT<float>     AttnF32Params   csrc/attn_f32.hip   fp32, head dim 64
+//   AttnParamsT<uint16_t>  AttnHdParams    csrc/attn_hd.hip    bf16, head dims 32 .. 128 other than 64
+//   AttnParams (+ extras)                  csrc/attn.hip       bf16, head dim 64 (the tuned kernels)
+//
+// Tensors: q, o, dout, dq are [B, Sq, H, D] views and k, v, dk, dv [B, Sk, H, D] views of element type T with the head
+// dim contiguous.  x_sb / x_ss / x_sh are the batch / sequence / head strides IN ELEMENTS, each a multiple of
+// 16 bytes, and every base pointer is 16-byte aligned (16-B vector loads of row starts).
+// Masks: key j is visible to query i iff kpm[b][j] != 0 (when given) and, if causal, j <= i + causal_off
+// (bottom-right aligned).  Bias: lut[h][(j - i) + Sq - 1] is added to the scaled score.
+// LSE: [B, H, Sq] fp32, forward writes and backward reads; +inf marks a row without a visible key (its output row is
+// 0).  The bf16 families store it in log2 units (scores are scaled by log2(e), softmax by exp2), fp32 in natural-log
+// units.
+// Dropout: probabilities are dropped by the counter-based hash of ops/rng.py attention_keep_mask with `seed`; a key is
+// kept iff its 16-bit hash half (sign bit flipped) >= thr, thr = min(65535, p_drop * 65536) (ops/rng.py threshold16).
 #pragma once
 #include <stdint.h>
 
-struct AttnParams {
-  const uint16_t* q;
-  const uint16_t* k;
-  const uint16_t* v;
-  const uint16_t* o;   // fwd output / bwd input
-  const uint16_t* dout;
-  uint16_t* o_out;
+template <class T>
+struct AttnParamsT {
+  typedef T elem;
+  const T* q;
+  const T* k;
+  const T* v;
+  const T* o;          // bwd: forward output
+  const T* dout;       // bwd: output gradient
+  T* o_out;            // fwd output
   float* lse;          // [B, H, Sq]
-  float* delta;        // [B, H, Sq] (bwd, written by the dQ kernel)
-  float* rowrec;       // [B*H][sq_pad / 64][4][64] per-row terms for dK/dV (written by the dQ kernel):
-                       // -lse2, c_lo - lse2, c_hi - lse2, -delta (rows >= Sq: -inf, -inf, -inf, 0)
-  uint16_t* dq;        // [B, Sq, H, D] strided (bwd)
-  uint16_t* dk;        // [B, Sk, H, D]
-  uint16_t* dv;
-  float* dlut;         // [H, Sq + Sk - 1] fp32 (bwd)
-  const uint8_t* kpm;  // [B, Sk] 1 = attend
-  const float* lut;    // [H, Sq + Sk - 1]
+  float* delta;        // [B, H, Sq]: rowsum(dO * O), written by the backward's first kernel
+  T* dq;
+  T* dk;
+  T* dv;
+  float* dlut;         // [H, Sq + Sk - 1] fp32 (bwd, accumulated with atomics; zeroed by the host); nullptr: not wanted
+                       // (csrc/attn.hip: always given with lut)
+  const uint8_t* kpm;  // [B, Sk] 1 = attend; nullptr: none
+  const float* lut;    // [H, Sq + Sk - 1]; nullptr: none
   long q_sb, q_ss, q_sh;
   long k_sb, k_ss, k_sh;
   long v_sb, v_ss, v_sh;
-  long o_sb, o_ss, o_sh;
+  long o_sb, o_ss, o_sh;  // o and o_out
   long do_sb, do_ss, do_sh;
   long dq_sb, dq_ss, dq_sh;
   long dk_sb, dk_ss, dk_sh;
   long dv_sb, dv_ss, dv_sh;
   int B, H, Sq, Sk;
+  int D;           // head dim: 64, or for csrc/attn_hd.hip 32 .. 128 (% 8 == 0; its kernels are instantiated for D
+                   // rounded up to 32)
   float scale;
   int causal;
   int causal_off;  // Sk - Sq
   float p_drop;
   uint32_t seed;
-  uint32_t thr;
-  int n_tiles;  // fwd: q tiles; bwd: key blocks
-  int n_ktiles;  // 64-key tiles (key-mask array length / 64)
-  int sq_pad;    // rows of the dropout bit-mask planes (query tiles x 128)
+  uint32_t thr;    // set by the host (csrc/attn.hip: by its launchers)
+};
+
+using AttnF32Params = AttnParamsT<float>;
+using AttnHdParams = AttnParamsT<uint16_t>;
+
+struct AttnParams : AttnParamsT<uint16_t> {
+  float* rowrec;    // [B*H][sq_pad / 64][4][64] per-row terms for dK/dV (written by the dQ kernel):
+                    // -lse2, c_lo - lse2, c_hi - lse2, -delta (rows >= Sq: -inf, -inf, -inf, 0)
   uint32_t* dmask;  // [B*H][n_ktiles][2][sq_pad] dropout keep bits written by fwd, read by bwd
-  int dmask_ready;  // fwd: planes already generated (attn_dropout_mask) -> read instead of hash
   // Saturated bias ranges (T5 relative buckets): LUT entries [0, sat_lo] all equal lut[0] and [sat_hi, L) all
   // equal lut[L-1], and the LUT gradient is only consumed per bucket.  A (forward, dQ, dK/dV) tile whose LUT
   // indices all fall in one range adds a scalar bias (no LDS lookups) and its dS sum is credited to lut[0] /
@@ -52,4 +75,8 @@ struct AttnParams {
   float* csk;
   float* csv;
   long csq_ld, cskv_ld;
+  // filled by the launchers
+  int n_tiles;   // fwd: q tiles; bwd: key blocks
+  int n_ktiles;  // 64-key tiles (key-mask array length / 64)
+  int sq_pad;    // rows of the dropout bit-mask planes (query tiles x 128)
 };

@@ -1,0 +1,79 @@
+// Device helpers shared by the two simple attention families, csrc/attn_f32.hip (fp32) and csrc/attn_hd.hip (bf16,
+// head dims other than 64).  Both walk 64 x 64 (query, key) blocks with 4 waves of 16 rows on a 16x16 MFMA whose C/D
+// map leaves a lane (c = lane & 15, g = lane >> 4) with keys 16 t + 4 g + i of one row, so the dropout decisions, the
+// reductions over the 4 lane groups, the key mask and the bias window read the same in both.  The kernels themselves
+// differ on purpose (MFMA shape, LDS images, LSE in natural-log units for fp32 and log2 units for bf16).
+#pragma once
+#include "common.h"
+
+namespace {
+
+using namespace dllm;
+
+constexpr int BQ = 64, BKY = 64, NT = 256;  // query rows / keys per block, threads per workgroup
+
+// Attention dropout (ops/rng.py attention_keep_mask, bit-exact): the row-Weyl hash of common.h with one row per
+// (b, h, query), rh = mix32(seed, row).
+// keep decision of key j of the row whose hash is rh
+DLLM_DEVICE bool keep_key(uint32_t rh, int j, uint32_t thr) {
+  const uint32_t y = rw_pair_y(rw_gbase(rh, (uint32_t)(j >> 1)));
+  const uint32_t half = (j & 1) ? (y >> 16) : (y & 0xFFFFu);
+  return (half ^ 0x8000u) >= thr;
+}
+// keep bits of keys j0 .. j0 + 3 (j0 % 4 == 0): bit i <-> key j0 + i; two hashes (one per key pair)
+DLLM_DEVICE uint32_t keep4(uint32_t rh, int j0, uint32_t thr) {
+  const uint32_t g0 = rw_gbase(rh, (uint32_t)(j0 >> 1));
+  uint32_t bits = 0;
+#pragma unroll
+  for (int pp = 0; pp < 2; ++pp) {
+    const uint32_t y = rw_pair_y(g0 + (uint32_t)pp * RW_G);
+    bits |= (((y & 0xFFFFu) ^ 0x8000u) >= thr ? 1u : 0u) << (2 * pp);
+    bits |= (((y >> 16) ^ 0x8000u) >= thr ? 1u : 0u) << (2 * pp + 1);
+  }
+  return bits;
+}
+
+DLLM_DEVICE float grp_max(float v) {  // over the 4 lane groups (same lane & 15)
+  v = fmaxf(v, __shfl_xor(v, 16, 64));
+  return fmaxf(v, __shfl_xor(v, 32, 64));
+}
+DLLM_DEVICE float grp_sum(float v) {
+  v += __shfl_xor(v, 16, 64);
+  return v + __shfl_xor(v, 32, 64);
+}
+
+// key in range and not padding (the causal test is per (row, key), done by the callers)
+template <class Params>
+DLLM_DEVICE bool key_ok(const Params& P, int b, int key) {
+  return key < P.Sk && (P.kpm == nullptr || P.kpm[(long)b * P.Sk + key] != 0);
+}
+
+// bias window of the (q0, k0) block, times `pre` (log2(e) where scores are in log2 units, 1.f where not): bias of
+// (key, row) at Ls[key - row - (k0 - q0 - 63)]
+template <class Params>
+DLLM_DEVICE void stage_bias(const Params& P, int h, int q0, int k0, float* Ls, int tid, float pre) {
+  if (P.lut && tid < 2 * BKY - 1) {
+    const long L = (long)P.Sq + P.Sk - 1;
+    long idx = (long)k0 - q0 - 63 + tid + P.Sq - 1;
+    idx = idx < 0 ? 0 : (idx >= L ? L - 1 : idx);
+    Ls[tid] = P.lut[(long)h * L + idx] * pre;
+  }
+}
+
+// bias gradient of the (q0, k0) block from its dS tile Ds (row stride BKY + 1: a diagonal walk is bank-conflict free):
+// per diagonal d = key - row + 63, one thread walks its diagonal (LDS reads, no atomics) and adds the sum to dlut once.
+// The caller has made the tile visible (barrier).
+template <class Params>
+DLLM_DEVICE void dlut_add_diagonals(const Params& P, int h, int q0, int k0, const float* Ds, int tid) {
+  if (tid < 2 * BKY - 1) {
+    const long L = (long)P.Sq + P.Sk - 1;
+    const int d = tid;
+    const int r0 = d < 63 ? 63 - d : 0, r1 = d < 63 ? 63 : 126 - d;
+    float v = 0.f;
+    for (int r = r0; r <= r1; ++r) v += Ds[r * (BKY + 1) + r + d - 63];
+    const long idx = (long)k0 - q0 - 63 + d + P.Sq - 1;
+    if (v != 0.f && idx >= 0 && idx < L) atomicAdd(&P.dlut[(long)h * L + idx], v);
+  }
+}
+
+}  // namespace

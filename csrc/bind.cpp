@@ -10,8 +10,6 @@
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>
 
-#include "attn_f32_params.h"
-#include "attn_hd_params.h"
 #include "attn_params.h"
 #include "gemm_params.h"
 #include "route.h"
@@ -38,7 +36,6 @@ int dllm_set_seed_step_attn(const uint32_t*);
 int dllm_set_seed_step_gemm_fused(const uint32_t*);
 int dllm_attn_fwd(AttnParams*, hipStream_t);
 int dllm_attn_bwd(AttnParams*, hipStream_t);
-int dllm_attn_params_size();
 int dllm_attn_dropout_mask(AttnParams*, hipStream_t);
 int dllm_attn_f32_fwd(AttnF32Params*, hipStream_t);
 int dllm_attn_f32_bwd(AttnF32Params*, hipStream_t);
@@ -367,59 +364,209 @@ void adamw_step(Tensor param, const optional<Tensor>& master, const Tensor& grad
 }
 
 // ------------------------------------------------------------------------------------------- attention
-void check_bshd(const Tensor& t, const char* n, int64_t B, int64_t S, int64_t H) {
+// One host path for the three kernel families (csrc/attn_params.h is the contract): csrc/attn.hip (bf16, head dim 64),
+// csrc/attn_f32.hip (the same op at the reference's precision: fp32 in, fp32 out, f32 MFMA) and csrc/attn_hd.hip (bf16,
+// head dims 32 .. 128 other than 64).  A family is its parameter block, its element type and its two launchers.
+template <class P>
+struct AttnFamily {
+  at::ScalarType dtype;
+  const char* takes;  // what a tensor of another dtype is told
+  int (*fwd)(P*, hipStream_t);
+  int (*bwd)(P*, hipStream_t);
+  const char* fwd_name;
+  const char* bwd_name;
+};
+const AttnFamily<AttnParams> kAttn{at::kBFloat16, "attention kernels take bf16", dllm_attn_fwd, dllm_attn_bwd,
+                                   "attn_fwd", "attn_bwd"};
+const AttnFamily<AttnF32Params> kAttnF32{at::kFloat, "fp32 attention kernels take fp32", dllm_attn_f32_fwd,
+                                         dllm_attn_f32_bwd, "attn_f32_fwd", "attn_f32_bwd"};
+const AttnFamily<AttnHdParams> kAttnHd{at::kBFloat16, "attn_hd kernels take bf16", dllm_attn_hd_fwd, dllm_attn_hd_bwd,
+                                       "attn_hd_fwd", "attn_hd_bwd"};
+
+template <class P>
+void check_bshd(const Tensor& t, const char* n, int64_t B, int64_t S, int64_t H, int64_t D, const AttnFamily<P>& f) {
   check_gpu(t, n);
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, n, ": attention kernels take bf16");
-  TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == S && t.size(2) == H && t.size(3) == 64, n,
-              ": expected [B, S, H, 64], got ", t.sizes());
+  TORCH_CHECK(t.scalar_type() == f.dtype, n, ": ", f.takes);
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == S && t.size(2) == H && t.size(3) == D, n,
+              ": expected [B, S, H, ", D, "], got ", t.sizes());
   TORCH_CHECK(t.stride(3) == 1, n, ": head dim must be contiguous");
-  TORCH_CHECK(t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 && t.stride(2) % 8 == 0, n,
-              ": strides must be multiples of 8 elements (16-B vector loads)");
+  const int64_t m = 16 / (int64_t)sizeof(typename P::elem);
+  TORCH_CHECK(t.stride(0) % m == 0 && t.stride(1) % m == 0 && t.stride(2) % m == 0, n,
+              ": strides must be multiples of ", m, " elements (16-B vector loads)");
   check_aligned(t, 16, n);
 }
 
-void fill_qkv(AttnParams& P, const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
-              const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
+// a checked [B, S, H, D] view into the block: base pointer + batch / sequence / head strides (elements)
+template <class U>
+void set_view(const Tensor& t, U*& ptr, long& sb, long& ss, long& sh) {
+  ptr = reinterpret_cast<U*>(t.data_ptr());
+  sb = t.stride(0); ss = t.stride(1); sh = t.stride(2);
+}
+
+// shapes from q / k, the q / k / v views, masks, bias and dropout: everything forward and backward share
+template <class P>
+void fill_common(P& p, const AttnFamily<P>& f, int64_t D, const Tensor& q, const Tensor& k, const Tensor& v,
+                 const optional<Tensor>& kpm, const optional<Tensor>& lut, double scale, bool causal, double drop,
+                 int64_t seed) {
   const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
-  check_bshd(q, "q", B, Sq, H);
-  check_bshd(k, "k", B, Sk, H);
-  check_bshd(v, "v", B, Sk, H);
+  check_bshd(q, "q", B, Sq, H, D, f);
+  check_bshd(k, "k", B, Sk, H, D, f);
+  check_bshd(v, "v", B, Sk, H, D, f);
   TORCH_CHECK(Sq > 0 && Sk > 0, "empty attention");
-  TORCH_CHECK(Sk <= 16384 && Sq <= 16384, "attention: sequence length > 16384 unsupported");
-  TORCH_CHECK(B * H * Sq * Sk < (int64_t)1 << 40, "attention too large");
-  P.q = reinterpret_cast<const uint16_t*>(q.data_ptr());
-  P.k = reinterpret_cast<const uint16_t*>(k.data_ptr());
-  P.v = reinterpret_cast<const uint16_t*>(v.data_ptr());
-  P.q_sb = q.stride(0); P.q_ss = q.stride(1); P.q_sh = q.stride(2);
-  P.k_sb = k.stride(0); P.k_ss = k.stride(1); P.k_sh = k.stride(2);
-  P.v_sb = v.stride(0); P.v_ss = v.stride(1); P.v_sh = v.stride(2);
-  P.B = B; P.H = H; P.Sq = Sq; P.Sk = Sk;
-  P.scale = (float)scale;
-  P.causal = causal ? 1 : 0;
-  P.causal_off = Sk - Sq;
-  P.p_drop = (float)p;
-  P.seed = (uint32_t)seed;
-  P.kpm = nullptr;
-  P.lut = nullptr;
+  TORCH_CHECK(drop >= 0.0 && drop < 1.0, "dropout p must be in [0, 1)");
+  set_view(q, p.q, p.q_sb, p.q_ss, p.q_sh);
+  set_view(k, p.k, p.k_sb, p.k_ss, p.k_sh);
+  set_view(v, p.v, p.v_sb, p.v_ss, p.v_sh);
+  p.B = B; p.H = H; p.Sq = Sq; p.Sk = Sk; p.D = D;
+  p.scale = (float)scale;
+  p.causal = causal ? 1 : 0;
+  p.causal_off = Sk - Sq;
+  p.p_drop = (float)drop;
+  p.seed = (uint32_t)seed;
+  p.thr = drop > 0.0 ? (uint32_t)std::min(65535.0, drop * 65536.0) : 0u;  // ops/rng.py threshold16
   if (kpm.has_value() && kpm->defined()) {
     TORCH_CHECK(kpm->scalar_type() == at::kByte && kpm->is_contiguous() && kpm->dim() == 2 && kpm->size(0) == B &&
                     kpm->size(1) == Sk && kpm->is_cuda(),
                 "key_padding_mask must be uint8 [B, Sk] contiguous on GPU");
-    P.kpm = kpm->data_ptr<uint8_t>();
+    p.kpm = kpm->data_ptr<uint8_t>();
   }
   if (lut.has_value() && lut->defined()) {
     TORCH_CHECK(lut->scalar_type() == at::kFloat && lut->is_contiguous() && lut->dim() == 2 && lut->size(0) == H &&
                     lut->size(1) == Sq + Sk - 1 && lut->is_cuda(),
                 "bias_lut must be fp32 [H, Sq + Sk - 1] contiguous on GPU");
-    P.lut = lut->data_ptr<float>();
+    p.lut = lut->data_ptr<float>();
   }
-  P.sat_lo = INT_MIN / 2;  // saturated-bias ranges off unless the caller declares them (set_sat)
-  P.sat_hi = INT_MAX / 2;
+}
+
+// forward outputs: o like q, lse fp32 [B, H, Sq]
+template <class P>
+std::vector<Tensor> fill_fwd(P& p, const Tensor& q) {
+  Tensor o = at::empty({p.B, p.Sq, p.H, p.D}, q.options());
+  Tensor lse = at::empty({p.B, p.H, p.Sq}, q.options().dtype(at::kFloat));
+  set_view(o, p.o_out, p.o_sb, p.o_ss, p.o_sh);
+  p.lse = lse.data_ptr<float>();
+  return {o, lse};
+}
+
+// backward inputs (o, dout, lse) and outputs: dq / dk / dv may be caller-provided strided views (e.g. slices of one
+// packed d(qkv) buffer), delta is scratch, dlut is zeroed for the kernels' atomics when wanted and there is a bias
+struct AttnBwdOut { Tensor dq, dk, dv, delta, dlut; };
+template <class P>
+AttnBwdOut fill_bwd(P& p, const AttnFamily<P>& f, const Tensor& q, const Tensor& o, const Tensor& dout,
+                    const Tensor& lse, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
+                    const optional<Tensor>& dv_out, bool want_dlut) {
+  check_bshd(o, "o", p.B, p.Sq, p.H, p.D, f);
+  check_bshd(dout, "dout", p.B, p.Sq, p.H, p.D, f);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (int64_t)p.B * p.H * p.Sq && lse.is_contiguous() &&
+                  lse.is_cuda(),
+              "lse mismatch");
+  auto pick = [&](const optional<Tensor>& t, int64_t S, const char* n) {
+    if (t.has_value() && t->defined()) {
+      check_bshd(*t, n, p.B, S, p.H, p.D, f);
+      return *t;
+    }
+    return at::empty({p.B, S, p.H, p.D}, q.options());
+  };
+  auto f32 = q.options().dtype(at::kFloat);
+  AttnBwdOut r{pick(dq_out, p.Sq, "dq_out"), pick(dk_out, p.Sk, "dk_out"), pick(dv_out, p.Sk, "dv_out"),
+               at::empty({p.B, p.H, p.Sq}, f32), Tensor()};
+  if (want_dlut && p.lut != nullptr) {
+    r.dlut = at::zeros({p.H, p.Sq + p.Sk - 1}, f32);
+    p.dlut = r.dlut.data_ptr<float>();
+  }
+  set_view(o, p.o, p.o_sb, p.o_ss, p.o_sh);
+  set_view(dout, p.dout, p.do_sb, p.do_ss, p.do_sh);
+  p.lse = lse.data_ptr<float>();
+  p.delta = r.delta.data_ptr<float>();
+  set_view(r.dq, p.dq, p.dq_sb, p.dq_ss, p.dq_sh);
+  set_view(r.dk, p.dk, p.dk_sb, p.dk_ss, p.dk_sh);
+  set_view(r.dv, p.dv, p.dv_sb, p.dv_ss, p.dv_sh);
+  return r;
+}
+
+// ---- csrc/attn_f32.hip and csrc/attn_hd.hip: a forward and a backward that differ by family and head dim only
+// their grids put B * H on the y axis, and they index rows (B * H * Sq) and the LUT (Sq + Sk) with 32 bits
+template <class P>
+void check_limits_small(const P& p) {
+  TORCH_CHECK((int64_t)p.B * p.H <= 65535, "attention: B * H > 65535 unsupported (grid y)");
+  TORCH_CHECK((int64_t)p.B * p.H * p.Sq < (int64_t)1 << 31 && ((int64_t)p.Sq + p.Sk) < (1 << 30),
+              "attention too large");
+}
+
+template <class P>
+std::vector<Tensor> attn_small_fwd(const AttnFamily<P>& f, int64_t D, const Tensor& q, const Tensor& k,
+                                   const Tensor& v, const optional<Tensor>& kpm, const optional<Tensor>& lut,
+                                   double scale, bool causal, double p, int64_t seed) {
+  P prm{};
+  fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
+  check_limits_small(prm);
+  auto out = fill_fwd(prm, q);
+  check_rc(f.fwd(&prm, stream()), f.fwd_name);
+  return out;
+}
+
+template <class P>
+std::vector<Tensor> attn_small_bwd(const AttnFamily<P>& f, int64_t D, const Tensor& dout, const Tensor& q,
+                                   const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& lse,
+                                   const optional<Tensor>& kpm, const optional<Tensor>& lut, double scale, bool causal,
+                                   double p, int64_t seed, bool need_dlut, const optional<Tensor>& dq_out,
+                                   const optional<Tensor>& dk_out, const optional<Tensor>& dv_out) {
+  P prm{};
+  fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
+  check_limits_small(prm);
+  auto r = fill_bwd(prm, f, q, o, dout, lse, dq_out, dk_out, dv_out, need_dlut);
+  check_rc(f.bwd(&prm, stream()), f.bwd_name);
+  return {r.dq, r.dk, r.dv, r.dlut};
+}
+
+std::vector<Tensor> attn_f32_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
+                                 const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
+  return attn_small_fwd(kAttnF32, 64, q, k, v, kpm, lut, scale, causal, p, seed);
+}
+
+std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
+                                 const Tensor& o, const Tensor& lse, const optional<Tensor>& kpm,
+                                 const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
+                                 bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
+                                 const optional<Tensor>& dv_out) {
+  return attn_small_bwd(kAttnF32, 64, dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed, need_dlut, dq_out,
+                        dk_out, dv_out);
+}
+
+// the head dim of an attn_hd call: what csrc/attn_hd.hip is instantiated for (padded to 32, 16-B rows)
+int64_t attn_hd_dim(const Tensor& q, const Tensor& k) {
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "attn_hd: q / k / v must be [B, S, H, D]");
+  const int64_t D = q.size(3);
+  TORCH_CHECK(D >= 32 && D <= 128 && D % 8 == 0, "attn_hd: head dim must be in 32 .. 128 and a multiple of 8, got ", D);
+  return D;
+}
+
+std::vector<Tensor> attn_hd_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
+                                const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
+  return attn_small_fwd(kAttnHd, attn_hd_dim(q, k), q, k, v, kpm, lut, scale, causal, p, seed);
+}
+
+std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
+                                const Tensor& o, const Tensor& lse, const optional<Tensor>& kpm,
+                                const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
+                                bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
+                                const optional<Tensor>& dv_out) {
+  return attn_small_bwd(kAttnHd, attn_hd_dim(q, k), dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed,
+                        need_dlut, dq_out, dk_out, dv_out);
+}
+
+// ---- csrc/attn.hip: the same helpers, plus its extras (dropout bit planes, saturated-bias ranges, rowrec, column sums)
+// its K/V tile rings and key masks live in LDS (sequence length) and its plane / rowrec indices are 64-bit products
+void check_limits_attn(const AttnParams& p) {
+  TORCH_CHECK(p.Sk <= 16384 && p.Sq <= 16384, "attention: sequence length > 16384 unsupported");
+  TORCH_CHECK((int64_t)p.B * p.H * p.Sq * p.Sk < (int64_t)1 << 40, "attention too large");
 }
 
 // sat_lo / sat_hi: LUT index ranges [0, sat_lo] and [sat_hi, L) of constant bias whose gradient is consumed per
 // bucket only (ops/attention.py relative_bias_lut); negative = off
 void set_sat(AttnParams& P, int64_t sat_lo, int64_t sat_hi) {
+  P.sat_lo = INT_MIN / 2;
+  P.sat_hi = INT_MAX / 2;
   if (P.lut == nullptr || sat_lo < 0 || sat_hi < 0) return;
   const int64_t L = (int64_t)P.Sq + P.Sk - 1;
   TORCH_CHECK(sat_lo < L && sat_hi > sat_lo && sat_hi <= L, "attention: bad saturated-bias bounds");
@@ -434,250 +581,23 @@ int64_t dmask_numel(const AttnParams& P) {
 
 std::vector<Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
                              const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
-                             const optional<Tensor>& dmask_in, int64_t sat_lo, int64_t sat_hi) {
+                             int64_t sat_lo, int64_t sat_hi) {
   AttnParams P{};
-  fill_qkv(P, q, k, v, kpm, lut, scale, causal, p, seed);
+  fill_common(P, kAttn, 64, q, k, v, kpm, lut, scale, causal, p, seed);
+  check_limits_attn(P);
   set_sat(P, sat_lo, sat_hi);
-  auto o = at::empty({P.B, P.Sq, P.H, 64}, q.options());
-  auto lse = at::empty({P.B, P.H, P.Sq}, q.options().dtype(at::kFloat));
-  P.o_out = reinterpret_cast<uint16_t*>(o.data_ptr());
-  P.o_sb = o.stride(0); P.o_ss = o.stride(1); P.o_sh = o.stride(2);
-  P.lse = lse.data_ptr<float>();
+  auto out = fill_fwd(P, q);
   // dropout keep bits: [B*H][ceil(Sk/64)][2][ceil(Sq/128)*128] uint32, written here, read by attn_bwd
   Tensor dmask;
   if (p > 0.0) {
-    if (dmask_in.has_value() && dmask_in->defined()) {  // planes from attn_dropout_mask (same seed and shapes)
-      TORCH_CHECK(dmask_in->scalar_type() == at::kInt && dmask_in->is_contiguous() && dmask_in->is_cuda() &&
-                      dmask_in->numel() == dmask_numel(P),
-                  "attn_fwd: dmask_in must come from attn_dropout_mask for the same shapes");
-      dmask = *dmask_in;
-      P.dmask_ready = 1;
-    } else {
-      dmask = at::empty({dmask_numel(P)}, q.options().dtype(at::kInt));
-    }
+    dmask = at::empty({dmask_numel(P)}, q.options().dtype(at::kInt));
     P.dmask = reinterpret_cast<uint32_t*>(dmask.data_ptr());
   }
-  check_rc(dllm_attn_fwd(&P, stream()), "attn_fwd");
-  return {o, lse, dmask};
+  check_rc(kAttn.fwd(&P, stream()), kAttn.fwd_name);
+  return {out[0], out[1], dmask};
 }
 
-// ------------------------------------------------------------------------------------------- fp32 attention
-// csrc/attn_f32.hip: the same op at the reference's precision (fp32 in, fp32 out, f32 MFMA).
-void check_bshd_f32(const Tensor& t, const char* n, int64_t B, int64_t S, int64_t H) {
-  check_gpu(t, n);
-  TORCH_CHECK(t.scalar_type() == at::kFloat, n, ": fp32 attention kernels take fp32");
-  TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == S && t.size(2) == H && t.size(3) == 64, n,
-              ": expected [B, S, H, 64], got ", t.sizes());
-  TORCH_CHECK(t.stride(3) == 1, n, ": head dim must be contiguous");
-  TORCH_CHECK(t.stride(0) % 4 == 0 && t.stride(1) % 4 == 0 && t.stride(2) % 4 == 0, n,
-              ": strides must be multiples of 4 elements (16-B vector loads)");
-  check_aligned(t, 16, n);
-}
-
-void fill_f32(AttnF32Params& P, const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
-              const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
-  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1);
-  check_bshd_f32(q, "q", B, Sq, H);
-  check_bshd_f32(k, "k", B, Sk, H);
-  check_bshd_f32(v, "v", B, Sk, H);
-  TORCH_CHECK(Sq > 0 && Sk > 0, "empty attention");
-  TORCH_CHECK(B * H <= 65535, "attention: B * H > 65535 unsupported (grid y)");
-  TORCH_CHECK(B * H * Sq < (int64_t)1 << 31 && (Sq + Sk) < (1 << 30), "attention too large");
-  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p must be in [0, 1)");
-  P.q = q.data_ptr<float>();
-  P.k = k.data_ptr<float>();
-  P.v = v.data_ptr<float>();
-  P.q_sb = q.stride(0); P.q_ss = q.stride(1); P.q_sh = q.stride(2);
-  P.k_sb = k.stride(0); P.k_ss = k.stride(1); P.k_sh = k.stride(2);
-  P.v_sb = v.stride(0); P.v_ss = v.stride(1); P.v_sh = v.stride(2);
-  P.B = B; P.H = H; P.Sq = Sq; P.Sk = Sk;
-  P.scale = (float)scale;
-  P.causal = causal ? 1 : 0;
-  P.causal_off = Sk - Sq;
-  P.p_drop = (float)p;
-  P.seed = (uint32_t)seed;
-  P.thr = p > 0.0 ? (uint32_t)std::min(65535.0, p * 65536.0) : 0u;  // ops/rng.py threshold16
-  if (kpm.has_value() && kpm->defined()) {
-    TORCH_CHECK(kpm->scalar_type() == at::kByte && kpm->is_contiguous() && kpm->dim() == 2 && kpm->size(0) == B &&
-                    kpm->size(1) == Sk && kpm->is_cuda(),
-                "key_padding_mask must be uint8 [B, Sk] contiguous on GPU");
-    P.kpm = kpm->data_ptr<uint8_t>();
-  }
-  if (lut.has_value() && lut->defined()) {
-    TORCH_CHECK(lut->scalar_type() == at::kFloat && lut->is_contiguous() && lut->dim() == 2 && lut->size(0) == H &&
-                    lut->size(1) == Sq + Sk - 1 && lut->is_cuda(),
-                "bias_lut must be fp32 [H, Sq + Sk - 1] contiguous on GPU");
-    P.lut = lut->data_ptr<float>();
-  }
-}
-
-std::vector<Tensor> attn_f32_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
-                                 const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
-  AttnF32Params P{};
-  fill_f32(P, q, k, v, kpm, lut, scale, causal, p, seed);
-  auto o = at::empty({P.B, P.Sq, P.H, 64}, q.options());
-  auto lse = at::empty({P.B, P.H, P.Sq}, q.options());
-  P.o_out = o.data_ptr<float>();
-  P.o_sb = o.stride(0); P.o_ss = o.stride(1); P.o_sh = o.stride(2);
-  P.lse = lse.data_ptr<float>();
-  check_rc(dllm_attn_f32_fwd(&P, stream()), "attn_f32_fwd");
-  return {o, lse};
-}
-
-std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
-                                 const Tensor& o, const Tensor& lse, const optional<Tensor>& kpm,
-                                 const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
-                                 bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
-                                 const optional<Tensor>& dv_out) {
-  AttnF32Params P{};
-  fill_f32(P, q, k, v, kpm, lut, scale, causal, p, seed);
-  check_bshd_f32(o, "o", P.B, P.Sq, P.H);
-  check_bshd_f32(dout, "dout", P.B, P.Sq, P.H);
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (int64_t)P.B * P.H * P.Sq && lse.is_contiguous() &&
-                  lse.is_cuda(),
-              "lse mismatch");
-  auto pick = [&](const optional<Tensor>& t, int64_t S, const char* n) {
-    if (t.has_value() && t->defined()) {
-      check_bshd_f32(*t, n, P.B, S, P.H);
-      return *t;
-    }
-    return at::empty({P.B, S, P.H, 64}, q.options());
-  };
-  Tensor dq = pick(dq_out, P.Sq, "dq_out");
-  Tensor dk = pick(dk_out, P.Sk, "dk_out");
-  Tensor dv = pick(dv_out, P.Sk, "dv_out");
-  auto delta = at::empty({P.B, P.H, P.Sq}, q.options());
-  Tensor dlut;
-  if (need_dlut && P.lut) {
-    dlut = at::zeros({P.H, P.Sq + P.Sk - 1}, q.options());
-    P.dlut = dlut.data_ptr<float>();
-  }
-  P.o = o.data_ptr<float>();
-  P.o_sb = o.stride(0); P.o_ss = o.stride(1); P.o_sh = o.stride(2);
-  P.dout = dout.data_ptr<float>();
-  P.do_sb = dout.stride(0); P.do_ss = dout.stride(1); P.do_sh = dout.stride(2);
-  P.lse = lse.data_ptr<float>();
-  P.delta = delta.data_ptr<float>();
-  P.dq = dq.data_ptr<float>();
-  P.dq_sb = dq.stride(0); P.dq_ss = dq.stride(1); P.dq_sh = dq.stride(2);
-  P.dk = dk.data_ptr<float>();
-  P.dk_sb = dk.stride(0); P.dk_ss = dk.stride(1); P.dk_sh = dk.stride(2);
-  P.dv = dv.data_ptr<float>();
-  P.dv_sb = dv.stride(0); P.dv_ss = dv.stride(1); P.dv_sh = dv.stride(2);
-  check_rc(dllm_attn_f32_bwd(&P, stream()), "attn_f32_bwd");
-  return {dq, dk, dv, dlut};
-}
-
-// ------------------------------------------------------------------------------------------- bf16 attention, any head dim
-// csrc/attn_hd.hip: the same op for bf16 head dims 32 .. 128 other than 64 (64 runs csrc/attn.hip).
-void check_bshd_hd(const Tensor& t, const char* n, int64_t B, int64_t S, int64_t H, int64_t D) {
-  check_gpu(t, n);
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, n, ": attn_hd kernels take bf16");
-  TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == S && t.size(2) == H && t.size(3) == D, n,
-              ": expected [B, S, H, ", D, "], got ", t.sizes());
-  TORCH_CHECK(t.stride(3) == 1, n, ": head dim must be contiguous");
-  TORCH_CHECK(t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 && t.stride(2) % 8 == 0, n,
-              ": strides must be multiples of 8 elements (16-B vector loads)");
-  check_aligned(t, 16, n);
-}
-
-void fill_hd(AttnHdParams& P, const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
-             const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
-  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "attn_hd: q / k / v must be [B, S, H, D]");
-  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3), Sk = k.size(1);
-  TORCH_CHECK(D >= 32 && D <= 128 && D % 8 == 0, "attn_hd: head dim must be in 32 .. 128 and a multiple of 8, got ", D);
-  check_bshd_hd(q, "q", B, Sq, H, D);
-  check_bshd_hd(k, "k", B, Sk, H, D);
-  check_bshd_hd(v, "v", B, Sk, H, D);
-  TORCH_CHECK(Sq > 0 && Sk > 0, "empty attention");
-  TORCH_CHECK(B * H <= 65535, "attention: B * H > 65535 unsupported (grid y)");
-  TORCH_CHECK(B * H * Sq < (int64_t)1 << 31 && (Sq + Sk) < (1 << 30), "attention too large");
-  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p must be in [0, 1)");
-  P.q = reinterpret_cast<const uint16_t*>(q.data_ptr());
-  P.k = reinterpret_cast<const uint16_t*>(k.data_ptr());
-  P.v = reinterpret_cast<const uint16_t*>(v.data_ptr());
-  P.q_sb = q.stride(0); P.q_ss = q.stride(1); P.q_sh = q.stride(2);
-  P.k_sb = k.stride(0); P.k_ss = k.stride(1); P.k_sh = k.stride(2);
-  P.v_sb = v.stride(0); P.v_ss = v.stride(1); P.v_sh = v.stride(2);
-  P.B = B; P.H = H; P.Sq = Sq; P.Sk = Sk; P.D = D;
-  P.scale = (float)scale;
-  P.causal = causal ? 1 : 0;
-  P.causal_off = Sk - Sq;
-  P.p_drop = (float)p;
-  P.seed = (uint32_t)seed;
-  P.thr = p > 0.0 ? (uint32_t)std::min(65535.0, p * 65536.0) : 0u;  // ops/rng.py threshold16
-  if (kpm.has_value() && kpm->defined()) {
-    TORCH_CHECK(kpm->scalar_type() == at::kByte && kpm->is_contiguous() && kpm->dim() == 2 && kpm->size(0) == B &&
-                    kpm->size(1) == Sk && kpm->is_cuda(),
-                "key_padding_mask must be uint8 [B, Sk] contiguous on GPU");
-    P.kpm = kpm->data_ptr<uint8_t>();
-  }
-  if (lut.has_value() && lut->defined()) {
-    TORCH_CHECK(lut->scalar_type() == at::kFloat && lut->is_contiguous() && lut->dim() == 2 && lut->size(0) == H &&
-                    lut->size(1) == Sq + Sk - 1 && lut->is_cuda(),
-                "bias_lut must be fp32 [H, Sq + Sk - 1] contiguous on GPU");
-    P.lut = lut->data_ptr<float>();
-  }
-}
-
-std::vector<Tensor> attn_hd_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
-                                const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
-  AttnHdParams P{};
-  fill_hd(P, q, k, v, kpm, lut, scale, causal, p, seed);
-  auto o = at::empty({P.B, P.Sq, P.H, P.D}, q.options());
-  auto lse = at::empty({P.B, P.H, P.Sq}, q.options().dtype(at::kFloat));
-  P.o_out = reinterpret_cast<uint16_t*>(o.data_ptr());
-  P.o_sb = o.stride(0); P.o_ss = o.stride(1); P.o_sh = o.stride(2);
-  P.lse = lse.data_ptr<float>();
-  check_rc(dllm_attn_hd_fwd(&P, stream()), "attn_hd_fwd");
-  return {o, lse};
-}
-
-std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
-                                const Tensor& o, const Tensor& lse, const optional<Tensor>& kpm,
-                                const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
-                                bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
-                                const optional<Tensor>& dv_out) {
-  AttnHdParams P{};
-  fill_hd(P, q, k, v, kpm, lut, scale, causal, p, seed);
-  check_bshd_hd(o, "o", P.B, P.Sq, P.H, P.D);
-  check_bshd_hd(dout, "dout", P.B, P.Sq, P.H, P.D);
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (int64_t)P.B * P.H * P.Sq && lse.is_contiguous() &&
-                  lse.is_cuda(),
-              "lse mismatch");
-  auto pick = [&](const optional<Tensor>& t, int64_t S, const char* n) {
-    if (t.has_value() && t->defined()) {
-      check_bshd_hd(*t, n, P.B, S, P.H, P.D);
-      return *t;
-    }
-    return at::empty({P.B, S, P.H, P.D}, q.options());
-  };
-  Tensor dq = pick(dq_out, P.Sq, "dq_out");
-  Tensor dk = pick(dk_out, P.Sk, "dk_out");
-  Tensor dv = pick(dv_out, P.Sk, "dv_out");
-  auto delta = at::empty({P.B, P.H, P.Sq}, q.options().dtype(at::kFloat));
-  Tensor dlut;
-  if (need_dlut && P.lut) {
-    dlut = at::zeros({P.H, P.Sq + P.Sk - 1}, q.options().dtype(at::kFloat));
-    P.dlut = dlut.data_ptr<float>();
-  }
-  P.o = reinterpret_cast<const uint16_t*>(o.data_ptr());
-  P.o_sb = o.stride(0); P.o_ss = o.stride(1); P.o_sh = o.stride(2);
-  P.dout = reinterpret_cast<const uint16_t*>(dout.data_ptr());
-  P.do_sb = dout.stride(0); P.do_ss = dout.stride(1); P.do_sh = dout.stride(2);
-  P.lse = lse.data_ptr<float>();
-  P.delta = delta.data_ptr<float>();
-  P.dq = reinterpret_cast<uint16_t*>(dq.data_ptr());
-  P.dq_sb = dq.stride(0); P.dq_ss = dq.stride(1); P.dq_sh = dq.stride(2);
-  P.dk = reinterpret_cast<uint16_t*>(dk.data_ptr());
-  P.dk_sb = dk.stride(0); P.dk_ss = dk.stride(1); P.dk_sh = dk.stride(2);
-  P.dv = reinterpret_cast<uint16_t*>(dv.data_ptr());
-  P.dv_sb = dv.stride(0); P.dv_ss = dv.stride(1); P.dv_sh = dv.stride(2);
-  check_rc(dllm_attn_hd_bwd(&P, stream()), "attn_hd_bwd");
-  return {dq, dk, dv, dlut};
-}
-
-// dropout keep-bit planes of an attention call (generated ahead, e.g. on a side stream)
+// the dropout keep-bit planes attn_fwd would return for these shapes, p and seed, without running it
 Tensor attn_dropout_mask(int64_t B, int64_t H, int64_t Sq, int64_t Sk, double p, int64_t seed, const Tensor& like) {
   TORCH_CHECK(p > 0.0 && B > 0 && H > 0 && Sq > 0 && Sk > 0 && like.is_cuda(), "attn_dropout_mask: bad arguments");
   AttnParams P{};
@@ -698,7 +618,8 @@ std::vector<Tensor> attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& 
                              int64_t sat_hi, const optional<Tensor>& csq, const optional<Tensor>& csk,
                              const optional<Tensor>& csv) {
   AttnParams P{};
-  fill_qkv(P, q, k, v, kpm, lut, scale, causal, p, seed);
+  fill_common(P, kAttn, 64, q, k, v, kpm, lut, scale, causal, p, seed);
+  check_limits_attn(P);
   set_sat(P, sat_lo, sat_hi);
   if (p > 0.0) {
     TORCH_CHECK(dmask.has_value() && dmask->defined() && dmask->scalar_type() == at::kInt && dmask->is_contiguous() &&
@@ -706,41 +627,11 @@ std::vector<Tensor> attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& 
                 "attn_bwd: dropout needs the bit planes attn_fwd returned");
     P.dmask = reinterpret_cast<uint32_t*>(dmask->data_ptr());
   }
-  check_bshd(o, "o", P.B, P.Sq, P.H);
-  check_bshd(dout, "dout", P.B, P.Sq, P.H);
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (int64_t)P.B * P.H * P.Sq && lse.is_contiguous(),
-              "lse mismatch");
-  auto f32 = q.options().dtype(at::kFloat);
-  // outputs may be caller-provided strided views (e.g. slices of one packed d(qkv) buffer)
-  auto pick = [&](const optional<Tensor>& t, int64_t S, const char* n) {
-    if (t.has_value() && t->defined()) {
-      check_bshd(*t, n, P.B, S, P.H);
-      return *t;
-    }
-    return at::empty({P.B, S, P.H, 64}, q.options());
-  };
-  Tensor dq = pick(dq_out, P.Sq, "dq_out");
-  Tensor dk = pick(dk_out, P.Sk, "dk_out");
-  Tensor dv = pick(dv_out, P.Sk, "dv_out");
-  auto delta = at::empty({P.B, P.H, P.Sq}, f32);
+  // the kernels accumulate the LUT gradient whenever there is a bias: always allocated, returned when wanted
+  auto r = fill_bwd(P, kAttn, q, o, dout, lse, dq_out, dk_out, dv_out, true);
   // per-row terms the dQ kernel hands to the dK/dV kernel ([B*H][sq_pad/64][4][64])
-  Tensor rowrec = at::empty({(int64_t)P.B * P.H * ((P.Sq + 127) / 128 * 128) * 4}, f32);
+  Tensor rowrec = at::empty({(int64_t)P.B * P.H * ((P.Sq + 127) / 128 * 128) * 4}, r.delta.options());
   P.rowrec = rowrec.data_ptr<float>();
-  Tensor dlut;
-  if (P.lut != nullptr) dlut = at::zeros({P.H, P.Sq + P.Sk - 1}, f32);
-  P.o = reinterpret_cast<const uint16_t*>(o.data_ptr());
-  P.o_sb = o.stride(0); P.o_ss = o.stride(1); P.o_sh = o.stride(2);
-  P.dout = reinterpret_cast<const uint16_t*>(dout.data_ptr());
-  P.do_sb = dout.stride(0); P.do_ss = dout.stride(1); P.do_sh = dout.stride(2);
-  P.lse = lse.data_ptr<float>();
-  P.delta = delta.data_ptr<float>();
-  P.dq = reinterpret_cast<uint16_t*>(dq.data_ptr());
-  P.dq_sb = dq.stride(0); P.dq_ss = dq.stride(1); P.dq_sh = dq.stride(2);
-  P.dk = reinterpret_cast<uint16_t*>(dk.data_ptr());
-  P.dk_sb = dk.stride(0); P.dk_ss = dk.stride(1); P.dk_sh = dk.stride(2);
-  P.dv = reinterpret_cast<uint16_t*>(dv.data_ptr());
-  P.dv_sb = dv.stride(0); P.dv_ss = dv.stride(1); P.dv_sh = dv.stride(2);
-  P.dlut = dlut.defined() ? dlut.data_ptr<float>() : nullptr;
   // optional per-block column sums ([B * ceil(S / 128)][H * 64] fp32 views, unit column stride; dK / dV share a row
   // stride): the bias gradients of the q / k / v projections, summed over blocks by the caller
   auto cs = [&](const optional<Tensor>& t, int64_t S, const char* n, long* ld) -> float* {
@@ -757,8 +648,8 @@ std::vector<Tensor> attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& 
   P.csv = cs(csv, P.Sk, "csv", &ldv);
   TORCH_CHECK((P.csk == nullptr) == (P.csv == nullptr) && ldk == ldv, "csk / csv: both or neither, one row stride");
   P.cskv_ld = ldk;
-  check_rc(dllm_attn_bwd(&P, stream()), "attn_bwd");
-  return {dq, dk, dv, need_dlut ? dlut : Tensor()};
+  check_rc(kAttn.bwd(&P, stream()), kAttn.bwd_name);
+  return {r.dq, r.dk, r.dv, need_dlut ? r.dlut : Tensor()};
 }
 
 }  // namespace
@@ -1445,8 +1336,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bc1"), py::arg("bc2"), py::arg("hyper") = py::none());
   m.def("set_seed_step", &set_seed_step, "device step counter mixed into every dropout site seed (None: off)");
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
-        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("dmask_in") = py::none(),
-        py::arg("sat_lo") = -1, py::arg("sat_hi") = -1);
+        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("sat_lo") = -1,
+        py::arg("sat_hi") = -1);
   m.def("attn_dropout_mask", &attn_dropout_mask);
   m.def("attn_bwd", &attn_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
@@ -1454,7 +1345,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dv_out") = py::none(), py::arg("dmask") = py::none(), py::arg("sat_lo") = -1,
         py::arg("sat_hi") = -1, py::arg("csq") = py::none(), py::arg("csk") = py::none(),
         py::arg("csv") = py::none());
-  m.def("attn_params_size", []() { return dllm_attn_params_size(); });
   m.def("attn_f32_fwd", &attn_f32_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
         py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"));
   m.def("attn_f32_bwd", &attn_f32_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),

@@ -133,42 +133,37 @@ def _split(mode, a, b, c):
     return a, b, c
 
 
+def _tuned(q) -> bool:
+    """csrc/attn.hip serves the call (bf16, head dim 64); else csrc/attn_f32.hip (fp32) or csrc/attn_hd.hip (bf16)."""
+    return q.dtype != torch.float32 and q.shape[-1] == 64
+
+
 class _AttnFn(torch.autograd.Function):
     """Inputs are packed the way the projections produce them (``qkv`` = one [B,S,3,H,D] tensor for
     self-attention, ``q`` + ``kv`` [B,Sk,2,H,D] for cross-attention) so backward writes ONE packed
     gradient buffer through strided views instead of three zero-padded slice gradients."""
 
     @staticmethod
-    def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed, pre=None):
+    def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed):
         C = _ext.native()
         q, k, v = _split(mode, a, b, c)
-        if q.dtype == torch.float32 or q.shape[-1] != 64:  # csrc/attn_f32.hip / csrc/attn_hd.hip (bf16, D != 64)
-            fwd = C.attn_f32_fwd if q.dtype == torch.float32 else C.attn_hd_fwd
-            o, lse = fwd(q, k, v, kpm, lut, float(scale), bool(causal), float(p), int(seed))
-            ctx.save_for_backward(a, b, c, o, lse, lut, kpm, None)
-            ctx.cfg = (mode, scale, causal, p, seed, lut is not None and lut.requires_grad, -1, -1)
-            # no column-sum partials off csrc/attn.hip (they hard-code H * 64): the bias gradients of biased
-            # projections come from the separate reduction, as with BIAS_COLSUM = False
-            ctx.cs = (False, False)
-            ctx.grad_into = getattr(b, "_dllm_grad_into", None) if mode == "q_kv" else None
-            return o
-        dmask_in = None
-        if pre is not None:  # keep-bit planes generated ahead on the side stream (prefetch_dropout_mask)
-            dmask_in, ev = pre
-            cur = torch.cuda.current_stream(q.device)
-            cur.wait_event(ev)
-            dmask_in.record_stream(cur)
-        sat = getattr(lut, "_dllm_sat", None) if lut is not None else None
-        sat_lo, sat_hi = sat if sat is not None else (-1, -1)
-        # saturated bias tiles add a scalar instead of reading the LUT (forward -2 %)
-        o, lse, dmask = C.attn_fwd(q, k, v, kpm, lut, float(scale), bool(causal), float(p), int(seed), dmask_in,
-                                   sat_lo, sat_hi)
+        args = (q, k, v, kpm, lut, float(scale), bool(causal), float(p), int(seed))
+        sat_lo = sat_hi = -1
+        dmask = None
+        if _tuned(q):
+            # saturated bias tiles add a scalar instead of reading the LUT (forward -2 %)
+            sat = getattr(lut, "_dllm_sat", None) if lut is not None else None
+            sat_lo, sat_hi = sat if sat is not None else (-1, -1)
+            o, lse, dmask = C.attn_fwd(*args, sat_lo, sat_hi)
+        else:
+            o, lse = (C.attn_f32_fwd if q.dtype == torch.float32 else C.attn_hd_fwd)(*args)
         ctx.save_for_backward(a, b, c, o, lse, lut, kpm, dmask)
         ctx.cfg = (mode, scale, causal, p, seed, lut is not None and lut.requires_grad, sat_lo, sat_hi)
         # packed inputs straight from a biased projection (ops/linear.py marks its output): the backward kernels also
-        # sum dQ / dK / dV over tokens for that projection's bias gradient (colsum_record)
-        # (bias-LUT-free calls only: the kernels' column-sum variants exist for those, csrc/attn.hip)
-        cs_ok = BIAS_COLSUM and lut is None
+        # sum dQ / dK / dV over tokens for that projection's bias gradient (colsum_record).  csrc/attn.hip only (the
+        # partials hard-code H * 64) and bias-LUT-free calls only (its column-sum variants exist for those); everything
+        # else takes the separate reduction, as with BIAS_COLSUM = False
+        cs_ok = BIAS_COLSUM and lut is None and _tuned(q)
         ctx.cs = (cs_ok and mode != "sep" and _bias_out(a), cs_ok and mode == "q_kv" and _bias_out(b))
         # ops/linear.py stacked_linear: the packed kv is a slice of a multi-layer projection and its
         # gradient has a home in the stacked gradient buffer — write dK/dV there directly
@@ -195,7 +190,7 @@ class _AttnFn(torch.autograd.Function):
             dq = dk = dv = None
         part = pq = pkv = None
         csq = csk = csv = None
-        if q.dtype != torch.float32 and (ctx.cs[0] or ctx.cs[1]):
+        if ctx.cs[0] or ctx.cs[1]:
             B, Sq, H = q.shape[0], q.shape[1], q.shape[2]
             HD, nq, nk = H * 64, B * ((Sq + 127) // 128), B * ((k.shape[1] + 127) // 128)
             f32 = dict(device=q.device, dtype=torch.float32)
@@ -208,14 +203,12 @@ class _AttnFn(torch.autograd.Function):
                 if ctx.cs[1]:
                     pkv = torch.empty(nk, 2 * HD, **f32)
                     csk, csv = pkv[:, :HD], pkv[:, HD:]
-        if q.dtype == torch.float32 or q.shape[-1] != 64:
-            bwd = C.attn_f32_bwd if q.dtype == torch.float32 else C.attn_hd_bwd
-            rq, rk, rv, dlut = bwd(do.contiguous(), q, k, v, o, lse, kpm, lut, float(scale), bool(causal),
-                                   float(p), int(seed), bool(need_dlut), dq, dk, dv)
+        args = (do.contiguous(), q, k, v, o, lse, kpm, lut, float(scale), bool(causal), float(p), int(seed),
+                bool(need_dlut), dq, dk, dv)
+        if _tuned(q):
+            rq, rk, rv, dlut = C.attn_bwd(*args, dmask, sat_lo, sat_hi, csq, csk, csv)
         else:
-            rq, rk, rv, dlut = C.attn_bwd(do.contiguous(), q, k, v, o, lse, kpm, lut, float(scale), bool(causal),
-                                          float(p), int(seed), bool(need_dlut), dq, dk, dv, dmask, sat_lo, sat_hi,
-                                          csq, csk, csv)
+            rq, rk, rv, dlut = (C.attn_f32_bwd if q.dtype == torch.float32 else C.attn_hd_bwd)(*args)
         if part is not None:  # per-block partials, reduced by the consumer into the bias gradient (ops/gemm.py)
             colsum_record(da, part)
         if pq is not None:
@@ -225,7 +218,7 @@ class _AttnFn(torch.autograd.Function):
         if mode == "sep":
             da, db, dc = rq, rk, rv
         streams.pair_join()  # side-stream weight gradients paired with these VALU-bound kernels (ops/streams.py)
-        return None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None, None
+        return None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None
 
 
 # False: the projections' bias gradients from a separate column reduction of dQKV (tests flip the module attribute)
@@ -313,34 +306,12 @@ def attention(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_
     return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed)
 
 
-def attention_qkv(qkv, pre=None, **kw):
+def attention_qkv(qkv, **kw):
     """Self-attention on the fused projection output ``qkv`` = [B, S, 3, H, D]."""
     if _native(qkv):
         return _AttnFn.apply("qkv", qkv, None, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
-                             kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
-                             pre)
+                             kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0))
     return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], **kw)
-
-
-_SIDE: dict = {}
-
-
-def prefetch_dropout_mask(like: torch.Tensor, B: int, H: int, Sq: int, Sk: int, p: float, seed: int):
-    """Generate the attention-dropout keep bits for an upcoming call on a side HIP stream (the VALU-only mask kernel
-    overlapping a projection GEMM issued meanwhile on the compute stream).  Returns a handle for
-    ``attention_qkv(pre=...)`` or None.  Not used by the models: the forward hashing the bits itself measured faster
-    (profiles/r3_attn_dropout_packed_ab.txt); kept as an API, tested equal to the in-kernel bits."""
-    if p <= 0.0 or like.shape[-1] != 64 or like.dtype != torch.bfloat16 or not _native(like):
-        return None
-    dev = like.device
-    side = _SIDE.get(dev)
-    if side is None:
-        side = _SIDE[dev] = torch.cuda.Stream(dev)
-    with torch.cuda.stream(side):
-        m = _ext.native().attn_dropout_mask(B, H, Sq, Sk, float(p), int(seed), like)
-        ev = torch.cuda.Event()
-        ev.record(side)
-    return m, ev
 
 
 def attention_q_kv(q, kv, **kw):

@@ -112,7 +112,7 @@ def _block_fwd(q, k, v, kpm, lut, sat, scale, p, seed):
     if r == "attn.hip":
         C = _ext.native()
         lo, hi = sat if sat is not None else (-1, -1)
-        o, lse, dmask = C.attn_fwd(q, k, v, kpm, lut, float(scale), False, float(p), int(seed), None, lo, hi)
+        o, lse, dmask = C.attn_fwd(q, k, v, kpm, lut, float(scale), False, float(p), int(seed), lo, hi)
         return o, lse, dmask  # bf16: the fp32 merge promotes (no separate conversion kernels)
     if r == "attn_hd.hip":  # same LSE units; the backward regenerates the dropout decisions (no keep-bit planes)
         o, lse = _ext.native().attn_hd_fwd(q, k, v, kpm, lut, float(scale), False, float(p), int(seed))

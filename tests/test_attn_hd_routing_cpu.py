@@ -39,4 +39,3 @@ def test_cpu_attention_head_dim_128_is_the_composite():
     o = A.attention(q, k, v, scale=128 ** -0.5, key_padding_mask=mask, dropout_p=0.1, seed=3)
     ref = A._reference(q, k, v, 128 ** -0.5, False, mask, None, 0.1, 3)
     assert torch.equal(o, ref)
-    assert A.prefetch_dropout_mask(q, 2, 2, 9, 13, 0.1, 3) is None

@@ -340,22 +340,58 @@ def test_colsum_acc_bias_grad(T, N, dt, aligned):
     _close(out, ref, rtol=1e-2, atol=1e-2 * (T ** 0.5) / 10 + 1e-2, msg="colsum")
 
 
-def test_attention_prefetched_dropout_planes_match(monkeypatch):
-    """Keep bits generated ahead on the side stream == bits hashed inside the forward (same seed)."""
-    B, S, H, D, p, seed = 2, 200, 3, 64, 0.1, 99
+def test_attention_prefetched_dropout_planes_match():
+    """Keep bits generated outside the forward (attn_dropout_mask) == the bits the forward hashes and returns, for the
+    same shapes, p and seed.  Non-causal: both hash all 32 key slots of every tile, so whole words compare."""
+    C = _ext.native()
+    B, H, D, p, seed = 2, 3, 64, 0.1, 99
     torch.manual_seed(0)
+    for Sq, Sk in ((200, 200), (130, 70)):  # ragged tiles on both axes; Sq != Sk
+        q = torch.randn(B, Sq, H, D, device=DEV).to(torch.bfloat16)
+        k = torch.randn(B, Sk, H, D, device=DEV).to(torch.bfloat16)
+        v = torch.randn(B, Sk, H, D, device=DEV).to(torch.bfloat16)
+        _, _, fwd_planes = C.attn_fwd(q, k, v, None, None, 0.125, False, p, seed)
+        planes = C.attn_dropout_mask(B, H, Sq, Sk, p, seed, q)
+        shape = (B * H, (Sk + 63) // 64, 2, (Sq + 127) // 128 * 128)
+        assert fwd_planes.numel() == planes.numel() == math.prod(shape)
+        assert torch.equal(fwd_planes.view(shape)[..., :Sq], planes.view(shape)[..., :Sq]), (Sq, Sk)
+    # the backward consumes the planes its forward returned: output and qkv.grad are bit-equal run to run
+    S = 200
     qkv = torch.randn(B, S, 3, H, D, device=DEV).to(torch.bfloat16)
     g = torch.randn(B, S, H, D, device=DEV).to(torch.bfloat16)
     outs = []
-    for use_pre in (False, True):
+    for _ in range(2):
         x = qkv.clone().requires_grad_(True)
-        pre = A.prefetch_dropout_mask(x, B, H, S, S, p, seed) if use_pre else None
-        assert (pre is not None) == use_pre
-        o = A.attention_qkv(x, pre=pre, scale=0.125, dropout_p=p, seed=seed)
+        o = A.attention_qkv(x, scale=0.125, dropout_p=p, seed=seed)
         o.backward(g)
         outs.append((o.detach(), x.grad))
     torch.testing.assert_close(outs[0][0], outs[1][0], rtol=0, atol=0)
     torch.testing.assert_close(outs[0][1], outs[1][1], rtol=0, atol=0)
+
+
+@pytest.mark.parametrize("fwd,dt,D,takes,mult", [
+    ("attn_fwd", torch.bfloat16, 64, "attention kernels take bf16", 8),
+    ("attn_f32_fwd", torch.float32, 64, "fp32 attention kernels take fp32", 4),
+    ("attn_hd_fwd", torch.bfloat16, 128, "attn_hd kernels take bf16", 8)])
+def test_attention_argument_checks(fwd, dt, D, takes, mult):
+    """The three forwards share one host checker: each refuses a wrong dtype, a key-padding mask of the wrong shape, a
+    stride that is not a multiple of 16 bytes and p = 1 with its message, before any kernel is launched."""
+    import re
+    f = getattr(_ext.native(), fwd)
+    B, H, S = 1, 2, 64
+    q, k, v = (torch.randn(B, S, H, D, device=DEV).to(dt) for _ in range(3))
+
+    def raises(msg, q=q, kpm=None, p=0.0):
+        with pytest.raises(RuntimeError, match=re.escape(msg)):
+            f(q, k, v, kpm, None, 1.0, False, p, 1)
+
+    raises("q: " + takes, q=q.to(torch.float16))
+    raises("key_padding_mask must be uint8 [B, Sk] contiguous on GPU",
+           kpm=torch.ones(B, S + 1, device=DEV, dtype=torch.uint8))
+    odd = torch.randn(B, S, H, D + 1, device=DEV).to(dt)[..., :D]  # head stride D + 1 elements
+    assert odd.stride(3) == 1 and odd.data_ptr() % 16 == 0
+    raises("q: strides must be multiples of %d elements (16-B vector loads)" % mult, q=odd)
+    raises("dropout p must be in [0, 1)", p=1.0)
 
 
 # ------------------------------------------------------------------------ fused-epilogue GEMM (csrc/gemm_fused.hip)
