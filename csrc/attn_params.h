@@ -9,7 +9,9 @@
 // dim contiguous.  x_sb / x_ss / x_sh are the batch / sequence / head strides IN ELEMENTS, each a multiple of
 // 16 bytes, and every base pointer is 16-byte aligned (16-B vector loads of row starts).
 // Masks: key j is visible to query i iff kpm[b][j] != 0 (when given) and, if causal, j <= i + causal_off
-// (bottom-right aligned).  Bias: lut[h][(j - i) + Sq - 1] is added to the scaled score.
+// (bottom-right aligned).  Causal with Sq > Sk is served, not rejected: causal_off < 0, so the first Sq - Sk query rows
+// see no key and are rows without a visible key (below); tests/test_attn_rows_gpu.py test_masks holds the kernels to it.
+// Bias: lut[h][(j - i) + Sq - 1] is added to the scaled score.
 // LSE: [B, H, Sq] fp32, forward writes and backward reads; +inf marks a row without a visible key (its output row is
 // 0).  The bf16 families store it in log2 units (scores are scaled by log2(e), softmax by exp2), fp32 in natural-log
 // units.
