@@ -28,6 +28,8 @@
 //   dK/dV kernel (key blocks of 128, key on the lane): P and dS accumulators are the B operands of
 //   dV^T += dO^T Pd and dK^T += Q^T dS (dO^T, Q^T by transposed reads); bias-LUT gradient = diagonal sums
 //   of dS via a register shear + 2 LDS atomics per lane per tile.
+//   Cross-attention (Sq <= 128, no bias, not causal) at full-chip launch sizes is ONE kernel: the short-query dK/dV
+//   kernel walks every key block of a (b, h) and keeps dQ in registers (attn_bwd_dkdv_sq_kernel, DQ arm).
 // Saturated T5 bias tiles (AttnParams::sat_lo / sat_hi): a wave tile whose relative distances all lie beyond the
 // last exact bucket (|j - i| >= 91 for bidirectional T5) sees one constant bias — it adds a scalar instead of
 // reading the LUT, and dK/dV credits its whole dS sum to the range's end entry instead of shearing diagonals (the
@@ -1050,25 +1052,42 @@ __global__ __launch_bounds__(256, NB == 3 ? 2 : 3) void attn_bwd_dkdv2_kernel(At
 // j computes.  attn_bwd_dkdv2_kernel starts one workgroup per key block instead, each re-staging the query side and
 // waiting on its own K / V loads before two short stages: prologue-latency bound at this shape.  Per score: the
 // bias-free body of attn_bwd_dkdv2_kernel (P = exp2(fma(s, sl2, rt)), Pd = P keep, dS = P fma(dP, keep, -delta)).
-template <bool HAS_KPM, bool DROP, int MB, bool CS = false>
+//
+// DQ (one pass: no attn_bwd_dq_kernel launch for this call): one workgroup walks EVERY key block of its (b, h) and
+// keeps dQ in registers from the first block to the last.  The prologue computes delta = rowsum(dO * O) and the row
+// terms itself (two threads per query row, the dQ kernel's summation order: dK / dV stay bit-identical).  Per key
+// block the wave's K fragments go to an LDS tile Kt [128 keys][64]; per 64-query stage each wave writes its dS (the
+// bf16 values the dK product takes) as [its 32 keys][64 queries] into the tile dSt, and after a barrier wave w adds
+// dQ^T[32 (w >> 1) .. + 31][queries 32 (w & 1) .. + 31 of the stage] += Kt^T dSt over the 128 keys (both operands by
+// transposed reads; 16 MFMAs per wave and block on top of the 64 of dK / dV).  Kt and dSt (16 KB each) share the 32 KB
+// of the dK / dV store staging, which is idle until the block's closing barrier: the LDS footprint is the split arm's.
+// After the last block the waves swap accumulator halves through the same 32 KB (fp32) so that wave w holds both
+// head-dim halves of query rows 32 w .. + 31, and dQ * scale leaves through store_rows_staged (+ csq column sums).
+template <bool HAS_KPM, bool DROP, int MB, bool CS = false, bool DQ = false, int NQT = 0>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // [2 stages of K2_STAGE: Q | dO | row terms (1 KB) | unused], keep words [2 parities][2 stages][1 KB], key mask [128],
-  // per-wave 8 KB store staging, column-sum scratch (2 KB)
+  // per-wave 8 KB store staging (DQ: also Kt | dSt, then the dQ exchange), column-sum scratch (2 KB)
   const uint32_t* keepb = reinterpret_cast<const uint32_t*>(smem + 2 * K2_STAGE);
   float* kmask = reinterpret_cast<float*>(smem + 2 * K2_STAGE + 4096);
+  unsigned char* stage_scr = smem + 2 * K2_STAGE + 4096 + BWD_BK * 4;
+  uint16_t* Kt = reinterpret_cast<uint16_t*>(stage_scr);
+  uint16_t* dSt = Kt + 2 * TILE64;
 
   const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31,
             hh = lane >> 5;
-  const int ngrp = (P.n_tiles + MB - 1) / MB;
+  int ngrp = 1;
+  if constexpr (!DQ) ngrp = (P.n_tiles + MB - 1) / MB;
   const int logical = xcd_remap(blockIdx.x, gridDim.x);
   const int grp = logical % ngrp;
   const int bh = logical / ngrp;
   const int h = bh % P.H, b = bh / P.H;
-  const int kb_begin = grp * MB;
-  const int kb_end = min(kb_begin + MB, P.n_tiles);
+  const int kb_begin = DQ ? 0 : grp * MB;
+  const int kb_end = DQ ? P.n_tiles : min(kb_begin + MB, P.n_tiles);
   const float sl2 = P.scale * LOG2E;
-  const int nqt = (P.Sq + K2_QT - 1) / K2_QT;  // 1 or 2: the launcher takes this kernel for Sq <= 128 only
+  // 1 or 2: the launcher takes this kernel for Sq <= 128 only (DQ: the template constant NQT, so that each stage is
+  // compiled once, with its own dQ accumulator)
+  const int nqt = DQ ? NQT : (P.Sq + K2_QT - 1) / K2_QT;
   const uint32_t st_lds = lds_addr(smem);
 
   // query side, once: Q / dO pieces and the row terms of every stage (the DMA pieces of attn_bwd_dkdv2_kernel)
@@ -1088,7 +1107,35 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
         bld16(qbase_p, __umul24(qq, qss2) + dc16, __builtin_amdgcn_readfirstlane(dst));
         bld16(dbase_p, __umul24(qq, dss2) + dc16, __builtin_amdgcn_readfirstlane(dst + TILE64 * 2));
       }
-      glds4(rec_src + (long)qt * 256, __builtin_amdgcn_readfirstlane(base + 4 * TILE64 + w * 256));
+      if constexpr (!DQ)
+        glds4(rec_src + (long)qt * 256, __builtin_amdgcn_readfirstlane(base + 4 * TILE64 + w * 256));
+    }
+  }
+  if constexpr (DQ) {
+    // the row terms attn_bwd_dq_kernel hands over as rowrec, computed here while the Q / dO pieces land: thread pair
+    // (2 row, 2 row + 1) sums the row's dO * O products in that kernel's lane-half order
+    const int row = tid >> 1, hp = tid & 1;
+    const bool qv = row < P.Sq;
+    const uint16_t* dp = P.dout + b * P.do_sb + (long)row * P.do_ss + h * P.do_sh;
+    const uint16_t* op = P.o + b * P.o_sb + (long)row * P.o_ss + h * P.o_sh;
+    float dpart = 0.f;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      u16x8 c = {0, 0, 0, 0, 0, 0, 0, 0}, o8 = c;
+      if (qv) {
+        c = *reinterpret_cast<const u16x8*>(dp + 16 * s + 8 * hp);
+        o8 = *reinterpret_cast<const u16x8*>(op + 16 * s + 8 * hp);
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dpart += bf2f(c[j]) * bf2f(o8[j]);
+    }
+    const float delta = dpart + __shfl_xor(dpart, 1, 64);
+    const long row_g = (long)bh * P.Sq + row;
+    const float lse2 = qv ? P.lse[row_g] : INFINITY;
+    if (qv && hp == 0) P.delta[row_g] = delta;
+    if ((row >> 6) < nqt) {  // -lse2 at 128.., -delta at 192.. of the row's stage (rows >= Sq: -inf, 0)
+      float* rec = reinterpret_cast<float*>(smem + (row >> 6) * K2_STAGE + 4 * TILE64);
+      rec[(hp == 0 ? 128 : 192) + (row & 63)] = hp == 0 ? -lse2 : (qv ? -delta : 0.f);
     }
   }
   // this lane's key inside a block and its dropout bit (the forward's lane half and register that held (q, key))
@@ -1135,12 +1182,27 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
   // barrier also retires every wave's reads of the key mask and keep slot the next block's writes reuse.  Waiting on
   // everything (not a counted vmcnt) keeps it correct when a wave skips loads or stores for keys past Sk.
   bf16x8v kf[4], vf[4], kfn[4], vfn[4];
+  f32x16 dqa0 = {}, dqa1 = {};  // DQ: the wave's dQ^T tiles of stage 0 / 1
+  // DQ: per-lane addresses of the dQ product's operands at keys 0 .. 15 (ld_tr_operand's rows 4 hh .. and 4 hh + 8 ..)
+  const int trc = 16 * ((r >> 4) & 1);
+  const uint16_t* kt_lo = tr_ptr(Kt, 4 * hh, 32 * (w >> 1) + trc, r & 15);
+  const uint16_t* kt_hi = tr_ptr(Kt, 4 * hh + 8, 32 * (w >> 1) + trc, r & 15);
+  const uint16_t* ds_lo = tr_ptr(dSt, 4 * hh, 32 * (w & 1) + trc, r & 15);
+  const uint16_t* ds_hi = tr_ptr(dSt, 4 * hh + 8, 32 * (w & 1) + trc, r & 15);
   issue_keep(kb_begin, 0);
   load_kv(kb_begin, kf, vf);
   bool key_ok = key_flag(kb_begin);
   wait_vm<0>();
   __syncthreads();
+  const int lane_o = lane, r_o = r, hh_o = hh, kl_o = kl, tid_o = tid;
   for (int kb = kb_begin; kb < kb_end; ++kb) {
+    // DQ: with the dQ accumulators there is no room for the few dozen per-lane LDS / global addresses hipcc would
+    // hoist out of this loop as invariants (and then spill); the lane index is made opaque per block so that they are
+    // formed where they are used (a few VALU operations per block)
+    int lane_v = lane_o;
+    if constexpr (DQ) asm volatile("" : "+v"(lane_v));
+    const int lane = lane_v, r = DQ ? lane_v & 31 : r_o, hh = DQ ? lane_v >> 5 : hh_o, kl = DQ ? w * 32 + r : kl_o;
+    const int tid = DQ ? w * 64 + lane_v : tid_o;
     const int par = (kb - kb_begin) & 1;
     if (tid < BWD_BK) kmask[tid] = key_ok ? 0.f : -INFINITY;
     const bool block_live = !HAS_KPM || __syncthreads_or(key_ok ? 1 : 0);
@@ -1149,12 +1211,37 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
     const bool more = kb + 1 < kb_end;
     if (more) {  // next block's inputs, in flight during this block's stages
       issue_keep(kb + 1, par ^ 1);
-      load_kv(kb + 1, kfn, vfn);
+      // DQ: no registers for a second K / V fragment set beside the dQ accumulators; the next block's fragments are
+      // loaded into kf / vf themselves once this block's last stage is done with them (load_kv_next)
+      if constexpr (!DQ) load_kv(kb + 1, kfn, vfn);
       key_ok = key_flag(kb + 1);
     }
     f32x16 dv0 = {}, dv1 = {}, dk0 = {}, dk1 = {};
-    if (block_live) {
-      for (int qt = 0; qt < nqt; ++qt) {
+    if constexpr (DQ) {
+      // this block's K rows as the dQ product's transposed operand (the staging area is free: the barriers above
+      // come after every wave's store reads of the previous block)
+      if (block_live) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) st_row(Kt, kl, 2 * s + hh, __builtin_bit_cast(u16x8, kf[s]));
+      }
+    }
+    // DQ: the next block's fragments straight into kf / vf.  Unconditional loads (no per-lane branch, no zero fill):
+    // a key past Sk reads row Sk - 1, finite values under a -inf key mask (P = dS = 0 exactly; its dK / dV rows are
+    // never stored)
+    auto load_kv_next = [&](int kbn) __attribute__((always_inline)) {
+      const int key = min(kbn * BWD_BK + kl, P.Sk - 1);
+      const uint16_t* kp = P.k + b * P.k_sb + (long)key * P.k_ss + h * P.k_sh;
+      const uint16_t* vp = P.v + b * P.v_sb + (long)key * P.v_ss + h * P.v_sh;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        kf[s] = as_frag(*reinterpret_cast<const u16x8*>(kp + 16 * s + 8 * hh));
+        vf[s] = as_frag(*reinterpret_cast<const u16x8*>(vp + 16 * s + 8 * hh));
+      }
+    };
+    // one 64-query stage of this key block (qt: an int, or a compile-time constant picking the DQ accumulator)
+    // (last_c: the block's last stage, a compile-time constant for DQ, which then loads the next block's K / V)
+    auto stage = [&](auto qt_c, auto last_c, f32x16& dqa) __attribute__((always_inline)) {
+        const int qt = qt_c;
         const unsigned char* stg = smem + qt * K2_STAGE;
         const uint16_t* Qb = reinterpret_cast<const uint16_t*>(stg);
         const uint16_t* dOb = Qb + TILE64;
@@ -1165,8 +1252,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
           f32x16 sacc = {}, dpacc = {};
 #pragma unroll
           for (int s = 0; s < 4; ++s) {
-            sacc = mfma32(as_frag(ld_row(Qb, 32 * u + r, 2 * s + hh)), kf[s], sacc);
-            dpacc = mfma32(as_frag(ld_row(dOb, 32 * u + r, 2 * s + hh)), vf[s], dpacc);
+            sacc = mfma32(as_frag(ld_row(Qb + u * TILE32, r, 2 * s + hh)), kf[s], sacc);
+            dpacc = mfma32(as_frag(ld_row(dOb + u * TILE32, r, 2 * s + hh)), vf[s], dpacc);
           }
           // row terms of rows 32 u + crow(i, hh): the bias-free -lse at 128.., -delta at 192..
           const float* rt_row = rec + 128 + 32 * u + 4 * hh;
@@ -1188,24 +1275,63 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
             }
           }
           const bf16x8v pf0 = pack8(sacc, 0), pf1 = pack8(sacc, 8), sf0 = pack8(dpacc, 0), sf1 = pack8(dpacc, 8);
+          if constexpr (DQ) {
+            // every wave has read the previous stage's dS tile (its dQ product) before this stage overwrites it
+            if (u == 0 && qt > 0) __syncthreads();
+            // dS of (key kl, queries 32 u + 8 g + 4 hh .. + 3) as 8-B pieces of row kl of the [128 keys][64 queries] tile
+            const u16x8 s0v = __builtin_bit_cast(u16x8, sf0), s1v = __builtin_bit_cast(u16x8, sf1);
+            uint16_t* drow = dSt + (kl << 6) + 4 * hh;
+            const int sw = swz(kl);
+            *reinterpret_cast<u16x4*>(drow + (((4 * u + 0) ^ sw) << 3)) = u16x4{s0v[0], s0v[1], s0v[2], s0v[3]};
+            *reinterpret_cast<u16x4*>(drow + (((4 * u + 1) ^ sw) << 3)) = u16x4{s0v[4], s0v[5], s0v[6], s0v[7]};
+            *reinterpret_cast<u16x4*>(drow + (((4 * u + 2) ^ sw) << 3)) = u16x4{s1v[0], s1v[1], s1v[2], s1v[3]};
+            *reinterpret_cast<u16x4*>(drow + (((4 * u + 3) ^ sw) << 3)) = u16x4{s1v[4], s1v[5], s1v[6], s1v[7]};
+          }
 #pragma unroll
           for (int sp = 0; sp < 2; ++sp) {
-            const int c0 = 32 * u + 16 * sp + 4 * hh;
+            // query rows 32 u + 16 sp + 4 hh ..: the multiple of 16 moves the tile pointer (an immediate offset of the
+            // reads; as a row index it costs an address register per (u, sp), see tr_ptr)
+            const int c0 = (32 * u + 16 * sp) * D;
             const bf16x8v pfv = sp == 0 ? pf0 : pf1, sfv = sp == 0 ? sf0 : sf1;
-            dv0 = mfma32(ld_tr_operand(dOb, c0, 0, r), pfv, dv0);
-            dv1 = mfma32(ld_tr_operand(dOb, c0, 1, r), pfv, dv1);
-            dk0 = mfma32(ld_tr_operand(Qb, c0, 0, r), sfv, dk0);
-            dk1 = mfma32(ld_tr_operand(Qb, c0, 1, r), sfv, dk1);
+            dv0 = mfma32(ld_tr_operand(dOb + c0, 4 * hh, 0, r), pfv, dv0);
+            dv1 = mfma32(ld_tr_operand(dOb + c0, 4 * hh, 1, r), pfv, dv1);
+            dk0 = mfma32(ld_tr_operand(Qb + c0, 4 * hh, 0, r), sfv, dk0);
+            dk1 = mfma32(ld_tr_operand(Qb + c0, 4 * hh, 1, r), sfv, dk1);
           }
         }
+        if constexpr (DQ) {
+          if (decltype(last_c)::value) {
+            // the block is done with kf / vf: the next block's fragments, in flight over the dQ product until the
+            // block's closing wait (issued right after the last S / dP products instead they are 32 more live registers
+            // at the kernel's peak, and hipcc spills them; a counted wait that keeps them in flight over the dK / dV
+            // stores too measured no different in the step, profiles/attn_sq_onepass_ab.txt)
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) load_kv_next(kb + 1);
+          }
+          __syncthreads();  // the stage's dS tile (and, at stage 0, Kt) is complete
+          // dQ^T[head dims 32 (w >> 1) ..][queries 32 (w & 1) ..] += Kt^T dSt over the block's 128 keys
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            dqa = mfma32(ld_tr_pair(kt_lo + j * 1024, kt_hi + j * 1024), ld_tr_pair(ds_lo + j * 1024, ds_hi + j * 1024),
+                         dqa);
+        }
+    };
+    if (block_live) {
+      if constexpr (DQ) {
+        stage(std::integral_constant<int, 0>{}, std::integral_constant<bool, NQT == 1>{}, dqa0);
+        if constexpr (NQT > 1) stage(std::integral_constant<int, 1>{}, std::true_type{}, dqa1);
+      } else {
+        for (int qt = 0; qt < nqt; ++qt) stage(qt, std::false_type{}, dqa0);
       }
+    } else if constexpr (DQ) {
+      if (more) load_kv_next(kb + 1);
     }
     wait_vm<0>();
     __syncthreads();
     {
       // the wave's 32 x 64 dK and dV tiles through its LDS scratch (16-B chunks XOR-swizzled by row), then whole
       // 128-B key rows: 8 full-line stores per wave instead of 16 stores of 16 B into 32 lines each
-      unsigned char* scr = smem + 2 * K2_STAGE + 4096 + BWD_BK * 4 + w * 8192;
+      unsigned char* scr = stage_scr + w * 8192;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const f32x16& ak = t == 0 ? dk0 : dk1;
@@ -1241,7 +1367,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
       if constexpr (CS) {
         // column sums (cs_wave): [wave][dK 64 | dV 64] in the 2 KB past the staging areas (lds_sq); the next key
         // block's writes come after its own barrier above
-        float* red = reinterpret_cast<float*>(smem + 2 * K2_STAGE + 4096 + BWD_BK * 4 + 4 * 8192);
+        float* red = reinterpret_cast<float*>(stage_scr + 4 * 8192);
         cs_wave(ak, lane, red + w * 128);
         cs_wave(av, lane, red + w * 128 + 64);
         __syncthreads();
@@ -1253,11 +1379,49 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_sq_kernel(AttnParams P) 
         }
       }
     }
-    if (more) {
+    if constexpr (!DQ) {
+      if (more) {
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        kf[s] = kfn[s];
-        vf[s] = vfn[s];
+        for (int s = 0; s < 4; ++s) {
+          kf[s] = kfn[s];
+          vf[s] = vfn[s];
+        }
+      }
+    }
+  }
+  if constexpr (DQ) {
+    // wave w holds head dims 32 (w >> 1) .. of query rows 64 qt + 32 (w & 1) .. (dqa0, dqa1); the row store wants both
+    // head-dim halves of rows 32 w ..: swap through the staging area as fp32 (each wave writes its own 8 KB, which no
+    // other wave has touched since the last block's closing barrier)
+    int lane_v = lane_o;  // as in the block loop: nothing per-lane of this epilogue is formed (and held) before the loop
+    asm volatile("" : "+v"(lane_v));
+    const int lane = lane_v, r = lane_v & 31, hh = lane_v >> 5;
+    float* X = reinterpret_cast<float*>(stage_scr);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      X[w * 2048 + i * 64 + lane] = dqa0[i];
+      X[w * 2048 + 1024 + i * 64 + lane] = dqa1[i];
+    }
+    __syncthreads();
+    f32x16 a0, a1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      a0[i] = X[(w & 1) * 2048 + (w >> 1) * 1024 + i * 64 + lane];
+      a1[i] = X[(2 + (w & 1)) * 2048 + (w >> 1) * 1024 + i * 64 + lane];
+    }
+    __syncthreads();  // every wave has its tiles: the area now stages the row stores
+    float* red = nullptr;
+    if constexpr (CS) {
+      if (P.csq != nullptr) red = reinterpret_cast<float*>(stage_scr + 4 * 8192);
+    }
+    store_rows_staged(stage_scr + w * 4096, a0, a1, P.scale, r, hh, lane,
+                      P.dq + b * P.dq_sb + (long)(32 * w) * P.dq_ss + h * P.dq_sh, P.dq_ss, P.Sq - 32 * w,
+                      red != nullptr ? red + w * 64 : nullptr);
+    if constexpr (CS) {
+      if (red != nullptr) {  // one query tile (Sq <= 128): partial row b
+        __syncthreads();
+        if (tid < 64)
+          P.csq[(long)b * P.csq_ld + h * 64 + tid] = red[tid] + red[64 + tid] + red[128 + tid] + red[192 + tid];
       }
     }
   }
@@ -1331,15 +1495,22 @@ void launch_bwd_dkdv2_t(const AttnParams& p, int nblk, size_t lds, hipStream_t s
   hipLaunchKernelGGL((attn_bwd_dkdv2_kernel<HB, HK, CA, DR, 3>), dim3(nblk), dim3(256), lds, st, p);
 }
 
-template <bool HK, bool DR, int MB, bool CS>
+template <bool HK, bool DR, int MB, bool CS, bool DQ = false, int NQT = 0>
 void launch_bwd_dkdv_sq_cs(const AttnParams& p, dim3 grid, size_t lds, hipStream_t st) {
   static bool attr = false;  // the staged epilogue puts the dynamic LDS above the 64 KB default
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_sq_kernel<HK, DR, MB, CS>,
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dkdv_sq_kernel<HK, DR, MB, CS, DQ, NQT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr = true;
   }
-  hipLaunchKernelGGL((attn_bwd_dkdv_sq_kernel<HK, DR, MB, CS>), grid, dim3(256), lds, st, p);
+  hipLaunchKernelGGL((attn_bwd_dkdv_sq_kernel<HK, DR, MB, CS, DQ, NQT>), grid, dim3(256), lds, st, p);
+}
+
+// the one-pass arm by query stages (64 rows each)
+template <bool HK, bool DR, bool CS>
+void launch_bwd_dkdv_sq_dq(const AttnParams& p, dim3 grid, size_t lds, hipStream_t st) {
+  if (p.Sq > K2_QT) launch_bwd_dkdv_sq_cs<HK, DR, 0, CS, true, 2>(p, grid, lds, st);
+  else launch_bwd_dkdv_sq_cs<HK, DR, 0, CS, true, 1>(p, grid, lds, st);
 }
 
 template <bool HK, bool DR, int MB>
@@ -1348,8 +1519,15 @@ void launch_bwd_dkdv_sq_mb(const AttnParams& p, dim3 grid, size_t lds, hipStream
   else launch_bwd_dkdv_sq_cs<HK, DR, MB, false>(p, grid, lds, st);
 }
 
+// mb == 0: the one-pass arm (dQ folded in, one workgroup per (b, h) over every key block; MB unused)
 template <bool HK, bool DR>
 void launch_bwd_dkdv_sq_t(const AttnParams& p, int mb, size_t lds, hipStream_t st) {
+  if (mb == 0) {
+    const dim3 grid((unsigned)((long)p.H * p.B));
+    if (p.csk != nullptr) launch_bwd_dkdv_sq_dq<HK, DR, true>(p, grid, lds, st);
+    else launch_bwd_dkdv_sq_dq<HK, DR, false>(p, grid, lds, st);
+    return;
+  }
   const long ng = (p.n_tiles + mb - 1) / mb;
   const dim3 grid((unsigned)(ng * p.H * p.B));
   if (mb >= 8) launch_bwd_dkdv_sq_mb<HK, DR, 8>(p, grid, lds, st);
@@ -1388,31 +1566,24 @@ extern "C" int dllm_attn_bwd(AttnParams* pp, hipStream_t st) {
   AttnParams p = *pp;
   if (!kv_offsets_fit(p)) return -6;
   p.thr = drop_threshold(p.p_drop);
-  // 1) dQ (+ delta): query blocks, forward geometry
-  p.n_tiles = (p.Sq + FWD_BM - 1) / FWD_BM;
+  const int n_qtiles = (p.Sq + FWD_BM - 1) / FWD_BM, n_kblocks = (p.Sk + BWD_BK - 1) / BWD_BK;
   p.n_ktiles = (p.Sk + FWD_BN - 1) / FWD_BN;
-  p.sq_pad = p.n_tiles * FWD_BM;
+  p.sq_pad = n_qtiles * FWD_BM;
   if (p.p_drop > 0.f && p.dmask == nullptr) return -5;
   // column sums ride on the kernels' staged row stores; their variants are instantiated for the bias-LUT-free
   // kernels only
   if ((p.csq != nullptr || p.csk != nullptr) && (p.rowrec == nullptr || p.lut != nullptr)) return -7;
   if ((p.csk == nullptr) != (p.csv == nullptr)) return -7;
-  long nblk = (long)p.n_tiles * p.H * p.B;
-  // 2 K/V buffers + per-key mask + tile flags + bias LUT window
-  size_t lds = (size_t)4 * TILE64 * 2 + (size_t)p.n_ktiles * (FWD_BN + 1) * 4;
-  if (p.lut) lds += (size_t)(p.Sk + FWD_BM + FWD_BN) * 4;
-  if (nblk <= 0 || nblk > 0x7fffffff || lds > 160 * 1024) return -4;
-  DISPATCH4(launch_bwd_dq_t, p.lut != nullptr, p.kpm != nullptr, p.causal != 0, p.p_drop > 0.f, p, (int)nblk, lds,
-            st);
-  DLLM_CHECK_LAUNCH();
-  // 2) dK, dV (+ bias-LUT gradient): key blocks
-  p.n_tiles = (p.Sk + BWD_BK - 1) / BWD_BK;
-  nblk = (long)p.n_tiles * p.H * p.B;
-  // short-query cross-attention (Sq <= 128, no bias, not causal): one workgroup walks MB key blocks with the query
-  // side resident (attn_bwd_dkdv_sq_kernel) — the largest MB in {4, 2} that still launches 6 workgroups per CU (3
-  // rounds at 2 per CU); smaller launches keep one workgroup per key block (dkdv2).  Batch sweep at the T5 cross
-  // shape: dkdv2 wins at batch 8 / 16, MB 2 at 32, MB 4 from 64.  In the t5-base b=512 step: 15.34 -> 13.50 ms/step
-  // (MB 8: 14.10), profiles/r4_dkdv_sq_ab.txt
+  // short-query cross-attention (Sq <= 128, no bias, not causal): one workgroup walks several key blocks with the
+  // query side resident (attn_bwd_dkdv_sq_kernel).
+  //  * one pass: launches with at least 6 workgroups per CU at ONE workgroup per (b, h) fold dQ into that kernel (its
+  //    DQ arm: no dQ kernel, K / V read once; profiles/attn_sq_onepass_ab.txt).  Its LDS footprint is the split
+  //    arm's whatever Sk (K goes through LDS one 128-key block at a time).  DLLM_ROUTE attn_sq_onepass=0 keeps the
+  //    split arm (tests compare the two); a call wanting only one of the dQ and dK / dV column sums takes it too.
+  //  * split (dQ kernel, then dK / dV): the largest MB in {4, 2} that still launches 6 workgroups per CU (3 rounds at 2
+  //    per CU); smaller launches keep one workgroup per key block (dkdv2).  Batch sweep at the T5 cross shape: dkdv2
+  //    wins at batch 8 / 16, MB 2 at 32, MB 4 from 64.  In the t5-base b=512 step: 15.34 -> 13.50 ms/step (MB 8:
+  //    14.10), profiles/r4_dkdv_sq_ab.txt
   constexpr int sq_cap = 4;
   static const int cus = [] {
     int dev = 0, n = 0;
@@ -1420,14 +1591,34 @@ extern "C" int dllm_attn_bwd(AttnParams* pp, hipStream_t st) {
     (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n > 0 ? n : 256;
   }();
-  // DLLM_ROUTE attn_dkdv_sq_force=1 (read per call; tests): the largest allowed MB whatever the launch size
+  // DLLM_ROUTE attn_dkdv_sq_force=1 (read per call; tests): the short-query kernel (one pass, or the largest allowed MB)
+  // whatever the launch size
   const bool force = route_int("attn_dkdv_sq_force", 0) == 1;
+  const bool sq_shape = p.rowrec != nullptr && p.lut == nullptr && !p.causal && p.Sq <= 2 * K2_QT && n_kblocks >= 2;
+  const bool onepass = sq_shape && route_int("attn_sq_onepass", 1) != 0 && (force || (long)p.H * p.B >= 6L * cus) &&
+                       (p.csq == nullptr) == (p.csk == nullptr);
   int mb = 0;
   for (int m = 8; m >= 2; m /= 2)
-    if (m <= sq_cap && mb == 0 && (force || (long)((p.n_tiles + m - 1) / m) * p.H * p.B >= 6L * cus)) mb = m;
-  if (p.rowrec != nullptr && p.lut == nullptr && !p.causal && p.Sq <= 2 * K2_QT && mb > 1 && p.n_tiles >= 2) {
+    if (m <= sq_cap && mb == 0 && (force || (long)((n_kblocks + m - 1) / m) * p.H * p.B >= 6L * cus)) mb = m;
+  // 1) dQ (+ delta): query blocks, forward geometry
+  p.n_tiles = n_qtiles;
+  long nblk = (long)p.n_tiles * p.H * p.B;
+  // 2 K/V buffers + per-key mask + tile flags + bias LUT window
+  size_t lds = (size_t)4 * TILE64 * 2 + (size_t)p.n_ktiles * (FWD_BN + 1) * 4;
+  if (p.lut) lds += (size_t)(p.Sk + FWD_BM + FWD_BN) * 4;
+  if (nblk <= 0 || nblk > 0x7fffffff || lds > 160 * 1024) return -4;
+  if (!onepass) {
+    DISPATCH4(launch_bwd_dq_t, p.lut != nullptr, p.kpm != nullptr, p.causal != 0, p.p_drop > 0.f, p, (int)nblk, lds,
+              st);
+    DLLM_CHECK_LAUNCH();
+  }
+  // 2) dK, dV (+ bias-LUT gradient): key blocks
+  p.n_tiles = n_kblocks;
+  nblk = (long)p.n_tiles * p.H * p.B;
+  if (onepass || (sq_shape && mb > 1)) {
+    if (onepass) mb = 0;
     const size_t lds_sq = (size_t)2 * K2_STAGE + 4096 + BWD_BK * 4 + 4 * 8192 + 2048;
-    if ((long)((p.n_tiles + mb - 1) / mb) * p.H * p.B > 0x7fffffff) return -4;
+    if (nblk > 0x7fffffff) return -4;
     if (p.kpm != nullptr) {
       if (p.p_drop > 0.f) launch_bwd_dkdv_sq_t<true, true>(p, mb, lds_sq, st);
       else launch_bwd_dkdv_sq_t<true, false>(p, mb, lds_sq, st);

@@ -62,7 +62,8 @@ using AttnHdParams = AttnParamsT<uint16_t>;
 
 struct AttnParams : AttnParamsT<uint16_t> {
   float* rowrec;    // [B*H][sq_pad / 64][4][64] per-row terms for dK/dV (written by the dQ kernel):
-                    // -lse2, c_lo - lse2, c_hi - lse2, -delta (rows >= Sq: -inf, -inf, -inf, 0)
+                    // -lse2, c_lo - lse2, c_hi - lse2, -delta (rows >= Sq: -inf, -inf, -inf, 0).  Left unwritten by
+                    // the one-pass cross-attention backward, whose single kernel forms the terms in LDS
   uint32_t* dmask;  // [B*H][n_ktiles][2][sq_pad] dropout keep bits written by fwd, read by bwd
   // Saturated bias ranges (T5 relative buckets): LUT entries [0, sat_lo] all equal lut[0] and [sat_hi, L) all
   // equal lut[L-1], and the LUT gradient is only consumed per bucket.  A (forward, dQ, dK/dV) tile whose LUT

@@ -6,6 +6,7 @@
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8v;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(8))) float f32x8;
 
 namespace {
@@ -64,6 +65,21 @@ DLLM_DEVICE u16x4 ld_tr(const uint16_t* T, int r0, int c0, int i) {
   const int off = (r << 6) + (((col >> 3) ^ swz(r)) << 3) + (col & 4);
   s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(T + off));
   return __builtin_bit_cast(u16x4, v);
+}
+
+// The same read split into its per-lane address and the load, for a caller that walks sequence rows in steps of 16:
+// swz() sees row bits 1 .. 3 only, so rows r0 + 16 j are tr_ptr(T, r0, ..) + j * 16 * 64 elements, an immediate offset
+// of the ds_read (hipcc does not find that by itself and keeps one address register per j).
+DLLM_DEVICE const uint16_t* tr_ptr(const uint16_t* T, int r0, int c0, int i) {
+  const int r = r0 + (i >> 2);
+  const int col = c0 + 4 * (i & 3);
+  return T + (r << 6) + (((col >> 3) ^ swz(r)) << 3) + (col & 4);
+}
+DLLM_DEVICE bf16x8v ld_tr_pair(const uint16_t* lo, const uint16_t* hi) {
+  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)lo);
+  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)hi);
+  const s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bf16x8v, v);
 }
 
 // A operand (32x32x16, k = sequence, permuted k order of an accumulator-fed B) for head-dim rows

@@ -35,6 +35,12 @@ LM head + cross-entropy        full logits while they fit ``lmhead_full_mb`` (16
                                (auto) when the logits would exceed the budget
 attention                      csrc/attn.hip bf16 flash kernels; fp32 inputs on the fp32      r4_t5base_fp32_b16_summary.txt
                                MFMA kernels of csrc/attn_f32.hip (``attn_f32`` = 1)
+cross-attention backward       one pass: dQ folded into the short-query dK/dV kernel (one    attn_sq_onepass_ab.txt
+(Sq <= 128, no bias, not       workgroup per (batch, head) over every key block, K / V read
+causal, >= 2 key blocks)       once, no dQ kernel) when B x H >= 6 per CU (``attn_sq_onepass``
+                               = 1; 0: the split arm); below that the dQ kernel + the        r4_dkdv_sq_ab.txt
+                               short-query dK/dV kernel at 4 / 2 key blocks per workgroup,
+                               or dkdv2 (one per key block) on the smallest launches
 attention, head dim != 64      bf16 at head dims 32 .. 128 (% 8 == 0): csrc/attn_hd.hip      attn_hd_vs_composite.txt
                                (``attn_hd`` = 1; 0: the O(Sq·Sk) composite); anything
                                else: the composite, with a one-time warning
@@ -102,9 +108,10 @@ DEFAULTS: dict = {
     # evaluation batch on the GPU (cli.py)
     "eval_batch": 256,
     # read by the C++ launchers (csrc/route.h): ping-pong GEMM tile-group size; test hook forcing the short-query
-    # dK/dV kernel on any launch size
+    # dK/dV kernel on any launch size; its one-pass arm (dQ folded in; 0: dQ kernel + split arm, the tests' comparison)
     "gemm_grp": 4,
     "attn_dkdv_sq_force": 0,
+    "attn_sq_onepass": 1,
     # csrc/gemm_w4.hip k-loop schedule (template RS): 769 = early fragment reads + DMAs riding on MFMAs + the LDS buffer
     # released half-way through sub-step 0 so the next DMA spreads over 88 MFMAs (default); 257 = without the early
     # release, 1 = the round-5 schedule; bits 16-128 = timing ablations (tools/gemm_w4_bench.py --ablate; garbage)
