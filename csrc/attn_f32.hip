@@ -4,6 +4,8 @@
 // T5 relative-position bias LUT [H, Sq + Sk - 1] (+ its gradient), key-padding mask, causal mask, softmax scale and
 // attention-probability dropout with the exact keep decisions of ops/rng.py attention_keep_mask.  O(S) memory:
 // probabilities are never materialised (the fp32 composite it replaces stored [B, H, Sq, Sk] scores + masks).
+// Sliding window (AttnParamsT::window >= 0; Sq == Sk, not causal): as in csrc/attn_hd.hip, the block walks cover only
+// the blocks that intersect the band (attn_small.h band_range) and the element mask gains |key - row| > w (off_band).
 //
 // Layout trick (no transposes through LDS for P or dS): the 16x16x4 f32 MFMA's C/D map puts rows 4g .. 4g+3
 // (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction index k = g from
@@ -105,7 +107,9 @@ __global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(AttnF32Params P) {
   const float* vb = P.v + (long)b * P.v_sb + (long)h * P.v_sh;
   int kend = P.Sk;
   if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
-  for (int k0 = 0; k0 < kend; k0 += BKY) {
+  int kstart = 0;
+  band_range(P, q0, kstart, kend);
+  for (int k0 = kstart; k0 < kend; k0 += BKY) {
     __syncthreads();  // the previous block's LDS reads are done
     stage<true, false>(kb, P.k_ss, k0, P.Sk, Ks, nullptr, tid);
     stage<false, true>(vb, P.v_ss, k0, P.Sk, nullptr, Vt, tid);
@@ -130,7 +134,7 @@ __global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(AttnF32Params P) {
         const int key = k0 + 16 * t + 4 * g + i;
         float x = st[t][i] * P.scale;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        if (!Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off)) x = -INFINITY;
+        if (!Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off) || off_band(P, row, key)) x = -INFINITY;
         st[t][i] = x;
         mx = fmaxf(mx, x);
       }
@@ -235,7 +239,9 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(AttnF32Params P) {
   const float* vb = P.v + (long)b * P.v_sb + (long)h * P.v_sh;
   int kend = P.Sk;
   if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
-  for (int k0 = 0; k0 < kend; k0 += BKY) {
+  int kstart = 0;
+  band_range(P, q0, kstart, kend);
+  for (int k0 = kstart; k0 < kend; k0 += BKY) {
     __syncthreads();
     stage<true, true>(kb, P.k_ss, k0, P.Sk, Ks, Kt, tid);
     stage<true, false>(vb, P.v_ss, k0, P.Sk, Vs, nullptr, tid);
@@ -265,7 +271,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(AttnF32Params P) {
         const int di = key - row - (k0 - q0 - 63);
         float x = st[t][i] * P.scale;
         if (P.lut) x += Ls[di];
-        const bool msk = !Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off);
+        const bool msk = !Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
         const float pr = msk ? 0.f : __expf(x - lse);
         const float dpk = DROP ? (((kb4 >> i) & 1u) ? dpt[t][i] * dscale : 0.f) : dpt[t][i];
         const float ds = pr * (dpk - dlt);
@@ -335,7 +341,9 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(AttnF32Params P) {
   const float* ob = P.dout + (long)b * P.do_sb + (long)h * P.do_sh;
   int qstart = 0;
   if (P.causal) qstart = max(0, (k0 - P.causal_off) / BQ * BQ);
-  for (int q0 = qstart; q0 < P.Sq; q0 += BQ) {
+  int qend = P.Sq;
+  band_range(P, k0, qstart, qend);
+  for (int q0 = qstart; q0 < qend; q0 += BQ) {
     __syncthreads();
     stage<true, true>(qb, P.q_ss, q0, P.Sq, Qs, Qt, tid);
     stage<true, true>(ob, P.do_ss, q0, P.Sq, Os, Ot, tid);
@@ -371,7 +379,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(AttnF32Params P) {
         const int rl = 16 * t + 4 * g + i, row = q0 + rl;
         float x = sc[t][i] * P.scale;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        const bool msk = !kok || (P.causal && key > row + P.causal_off);
+        const bool msk = !kok || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
         const float pr = msk ? 0.f : __expf(x - Rl[rl]);
         const bool kp = DROP ? keep_key(Rh[rl], key, P.thr) : true;
         const float dpk = kp ? dp[t][i] * dscale : 0.f;

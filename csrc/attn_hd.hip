@@ -7,7 +7,13 @@
 // (its output row is 0) — parallel/context.py _merge combines blocks by it.
 //
 // The real head dim D (D % 8 == 0, 32 <= D <= DP) is a runtime field: columns D .. DP-1 are staged as zeros and never
-// stored.  bias / kpm / causal are runtime flags; only DP and DROP are template parameters (24 kernel instantiations).
+// stored.  bias / kpm / causal / window are runtime flags; only DP and DROP are template parameters (24 kernel
+// instantiations).
+//
+// Sliding window (AttnParamsT::window >= 0, LongT5-local; Sq == Sk, not causal): forward and dQ walk only the key
+// blocks that intersect [q0 - w, q0 + 63 + w], dK / dV only the query blocks that intersect [k0 - w, k0 + 63 + w]
+// (attn_small.h band_range) — the others are never loaded — and the element mask gains |key - row| > w (off_band).
+// Windowed calls at head dim 64 run here too (DP = 64): csrc/attn.hip has no window.
 //
 // Layout trick of csrc/attn_f32.hip, carried over to the 16x16x32 bf16 MFMA: its C/D map puts rows 4g .. 4g+3
 // (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction indices k = 8g + j
@@ -130,7 +136,9 @@ __global__ __launch_bounds__(NT) void attn_hd_fwd_kernel(AttnHdParams P) {
   const uint16_t* vb = P.v + (long)b * P.v_sb + (long)h * P.v_sh;
   int kend = P.Sk;
   if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
-  for (int k0 = 0; k0 < kend; k0 += BKY) {
+  int kstart = 0;
+  band_range(P, q0, kstart, kend);
+  for (int k0 = kstart; k0 < kend; k0 += BKY) {
     __syncthreads();  // the previous block's LDS reads are done
     stage<DP>(kb, P.k_ss, k0, P.Sk, P.D, Ks, tid);
     stage<DP>(vb, P.v_ss, k0, P.Sk, P.D, Vs, tid);
@@ -153,7 +161,7 @@ __global__ __launch_bounds__(NT) void attn_hd_fwd_kernel(AttnHdParams P) {
         const int key = k0 + 16 * t + 4 * g + i;
         float x = st[t][i] * scale2;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        if (!Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off)) x = -INFINITY;
+        if (!Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off) || off_band(P, row, key)) x = -INFINITY;
         st[t][i] = x;
         mx = fmaxf(mx, x);
       }
@@ -248,7 +256,9 @@ __global__ __launch_bounds__(NT) void attn_hd_dq_kernel(AttnHdParams P) {
   const uint16_t* vb = P.v + (long)b * P.v_sb + (long)h * P.v_sh;
   int kend = P.Sk;
   if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
-  for (int k0 = 0; k0 < kend; k0 += BKY) {
+  int kstart = 0;
+  band_range(P, q0, kstart, kend);
+  for (int k0 = kstart; k0 < kend; k0 += BKY) {
     __syncthreads();
     stage<DP>(kb, P.k_ss, k0, P.Sk, P.D, Ks, tid);
     stage<DP>(vb, P.v_ss, k0, P.Sk, P.D, Vs, tid);
@@ -275,7 +285,7 @@ __global__ __launch_bounds__(NT) void attn_hd_dq_kernel(AttnHdParams P) {
         const int di = key - row - (k0 - q0 - 63);
         float x = st[t][i] * scale2;
         if (P.lut) x += Ls[di];
-        const bool msk = !Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off);
+        const bool msk = !Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
         const float pr = msk ? 0.f : ex2(x - lse);
         const float dpk = DROP ? (((kb4 >> i) & 1u) ? dpt[t][i] * dscale : 0.f) : dpt[t][i];
         const float ds = pr * (dpk - dlt);
@@ -333,7 +343,9 @@ __global__ __launch_bounds__(NT) void attn_hd_dkdv_kernel(AttnHdParams P) {
   const uint16_t* ob = P.dout + (long)b * P.do_sb + (long)h * P.do_sh;
   int qstart = 0;
   if (P.causal) qstart = max(0, (k0 - P.causal_off) / BQ * BQ);
-  for (int q0 = qstart; q0 < P.Sq; q0 += BQ) {
+  int qend = P.Sq;
+  band_range(P, k0, qstart, qend);
+  for (int q0 = qstart; q0 < qend; q0 += BQ) {
     __syncthreads();
     stage<DP>(qb, P.q_ss, q0, P.Sq, P.D, Qs, tid);
     stage<DP>(ob, P.do_ss, q0, P.Sq, P.D, Os, tid);
@@ -366,7 +378,7 @@ __global__ __launch_bounds__(NT) void attn_hd_dkdv_kernel(AttnHdParams P) {
         const int rl = 16 * t + 4 * g + i, row = q0 + rl;
         float x = sc[t][i] * scale2;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        const bool msk = !kok || (P.causal && key > row + P.causal_off);
+        const bool msk = !kok || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
         const float pr = msk ? 0.f : ex2(x - Rl[rl]);
         const bool kp = DROP ? keep_key(Rh[rl], key, P.thr) : true;
         const float dpk = kp ? dp[t][i] * dscale : 0.f;

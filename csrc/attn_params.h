@@ -11,6 +11,11 @@
 // Masks: key j is visible to query i iff kpm[b][j] != 0 (when given) and, if causal, j <= i + causal_off
 // (bottom-right aligned).  Causal with Sq > Sk is served, not rejected: causal_off < 0, so the first Sq - Sk query rows
 // see no key and are rows without a visible key (below); tests/test_attn_rows_gpu.py test_masks holds the kernels to it.
+// Window: with window >= 0 key j is visible to query i iff, besides the above, |j - i| <= window (a band around the
+// diagonal); -1: no window.  Windowed calls have Sq == Sk and causal == 0 (the binding checks both).  The block walks of
+// csrc/attn_hd.hip and csrc/attn_f32.hip skip the 64 x 64 blocks outside the band, so work and traffic are
+// O(S * window); csrc/attn.hip has no window and is never given one.  With a window a row can lack a visible key only
+// through the padding mask.
 // Bias: lut[h][(j - i) + Sq - 1] is added to the scaled score.
 // LSE: [B, H, Sq] fp32, forward writes and backward reads; +inf marks a row without a visible key (its output row is
 // 0).  The bf16 families store it in log2 units (scores are scaled by log2(e), softmax by exp2), fp32 in natural-log
@@ -52,6 +57,7 @@ struct AttnParamsT {
   float scale;
   int causal;
   int causal_off;  // Sk - Sq
+  int window;      // -1: none; w >= 0: keys with |j - i| > w are masked (csrc/attn_hd.hip, csrc/attn_f32.hip only)
   float p_drop;
   uint32_t seed;
   uint32_t thr;    // set by the host (csrc/attn.hip: by its launchers)

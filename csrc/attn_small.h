@@ -48,6 +48,22 @@ DLLM_DEVICE bool key_ok(const Params& P, int b, int key) {
   return key < P.Sk && (P.kpm == nullptr || P.kpm[(long)b * P.Sk + key] != 0);
 }
 
+// Sliding window (attn_params.h `window`, -1: none): the pair (row, key) lies outside the band
+template <class Params>
+DLLM_DEVICE bool off_band(const Params& P, int row, int key) {
+  return P.window >= 0 && (key > row ? key - row : row - key) > P.window;
+}
+// Narrows [lo, hi), the positions a block walk covers in steps of 64 from lo, to the 64-blocks that intersect
+// [x0 - window, x0 + 63 + window]: the partners the 64-block at x0 can see.  Blocks outside are never loaded.
+template <class Params>
+DLLM_DEVICE void band_range(const Params& P, int x0, int& lo, int& hi) {
+  if (P.window >= 0) {
+    const int w = min(P.window, max(P.Sq, P.Sk));  // no overflow for any window
+    lo = max(lo, max(0, x0 - w) / 64 * 64);
+    hi = min(hi, x0 + 64 + w);
+  }
+}
+
 // bias window of the (q0, k0) block, times `pre` (log2(e) where scores are in log2 units, 1.f where not): bias of
 // (key, row) at Ls[key - row - (k0 - q0 - 63)]
 template <class Params>

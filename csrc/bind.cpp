@@ -421,6 +421,7 @@ void fill_common(P& p, const AttnFamily<P>& f, int64_t D, const Tensor& q, const
   p.scale = (float)scale;
   p.causal = causal ? 1 : 0;
   p.causal_off = Sk - Sq;
+  p.window = -1;  // set_window: csrc/attn_f32.hip and csrc/attn_hd.hip only
   p.p_drop = (float)drop;
   p.seed = (uint32_t)seed;
   p.thr = drop > 0.0 ? (uint32_t)std::min(65535.0, drop * 65536.0) : 0u;  // ops/rng.py threshold16
@@ -493,12 +494,22 @@ void check_limits_small(const P& p) {
               "attention too large");
 }
 
+// the sliding window of csrc/attn_params.h: a band around the diagonal of a square, non-causal problem
+template <class P>
+void set_window(P& p, int64_t window) {
+  if (window < 0) return;
+  TORCH_CHECK(p.Sq == p.Sk, "attention: window needs Sq == Sk, got ", p.Sq, " and ", p.Sk);
+  TORCH_CHECK(!p.causal, "attention: window with causal is unsupported");
+  p.window = (int)std::min<int64_t>(window, INT_MAX);
+}
+
 template <class P>
 std::vector<Tensor> attn_small_fwd(const AttnFamily<P>& f, int64_t D, const Tensor& q, const Tensor& k,
                                    const Tensor& v, const optional<Tensor>& kpm, const optional<Tensor>& lut,
-                                   double scale, bool causal, double p, int64_t seed) {
+                                   double scale, bool causal, double p, int64_t seed, int64_t window) {
   P prm{};
   fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
+  set_window(prm, window);
   check_limits_small(prm);
   auto out = fill_fwd(prm, q);
   check_rc(f.fwd(&prm, stream()), f.fwd_name);
@@ -510,9 +521,10 @@ std::vector<Tensor> attn_small_bwd(const AttnFamily<P>& f, int64_t D, const Tens
                                    const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& lse,
                                    const optional<Tensor>& kpm, const optional<Tensor>& lut, double scale, bool causal,
                                    double p, int64_t seed, bool need_dlut, const optional<Tensor>& dq_out,
-                                   const optional<Tensor>& dk_out, const optional<Tensor>& dv_out) {
+                                   const optional<Tensor>& dk_out, const optional<Tensor>& dv_out, int64_t window) {
   P prm{};
   fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
+  set_window(prm, window);
   check_limits_small(prm);
   auto r = fill_bwd(prm, f, q, o, dout, lse, dq_out, dk_out, dv_out, need_dlut);
   check_rc(f.bwd(&prm, stream()), f.bwd_name);
@@ -520,17 +532,18 @@ std::vector<Tensor> attn_small_bwd(const AttnFamily<P>& f, int64_t D, const Tens
 }
 
 std::vector<Tensor> attn_f32_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
-                                 const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
-  return attn_small_fwd(kAttnF32, 64, q, k, v, kpm, lut, scale, causal, p, seed);
+                                 const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
+                                 int64_t window) {
+  return attn_small_fwd(kAttnF32, 64, q, k, v, kpm, lut, scale, causal, p, seed, window);
 }
 
 std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
                                  const Tensor& o, const Tensor& lse, const optional<Tensor>& kpm,
                                  const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
                                  bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
-                                 const optional<Tensor>& dv_out) {
+                                 const optional<Tensor>& dv_out, int64_t window) {
   return attn_small_bwd(kAttnF32, 64, dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed, need_dlut, dq_out,
-                        dk_out, dv_out);
+                        dk_out, dv_out, window);
 }
 
 // the head dim of an attn_hd call: what csrc/attn_hd.hip is instantiated for (padded to 32, 16-B rows)
@@ -542,17 +555,18 @@ int64_t attn_hd_dim(const Tensor& q, const Tensor& k) {
 }
 
 std::vector<Tensor> attn_hd_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
-                                const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed) {
-  return attn_small_fwd(kAttnHd, attn_hd_dim(q, k), q, k, v, kpm, lut, scale, causal, p, seed);
+                                const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
+                                int64_t window) {
+  return attn_small_fwd(kAttnHd, attn_hd_dim(q, k), q, k, v, kpm, lut, scale, causal, p, seed, window);
 }
 
 std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
                                 const Tensor& o, const Tensor& lse, const optional<Tensor>& kpm,
                                 const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
                                 bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
-                                const optional<Tensor>& dv_out) {
+                                const optional<Tensor>& dv_out, int64_t window) {
   return attn_small_bwd(kAttnHd, attn_hd_dim(q, k), dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed,
-                        need_dlut, dq_out, dk_out, dv_out);
+                        need_dlut, dq_out, dk_out, dv_out, window);
 }
 
 // ---- csrc/attn.hip: the same helpers, plus its extras (dropout bit planes, saturated-bias ranges, rowrec, column sums)
@@ -1346,17 +1360,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sat_hi") = -1, py::arg("csq") = py::none(), py::arg("csk") = py::none(),
         py::arg("csv") = py::none());
   m.def("attn_f32_fwd", &attn_f32_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
-        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"));
+        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1);
   m.def("attn_f32_bwd", &attn_f32_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
-        py::arg("dv_out") = py::none());
+        py::arg("dv_out") = py::none(), py::arg("window") = -1);
   m.def("attn_hd_fwd", &attn_hd_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
-        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"));
+        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1);
   m.def("attn_hd_bwd", &attn_hd_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
-        py::arg("dv_out") = py::none());
+        py::arg("dv_out") = py::none(), py::arg("window") = -1);
   m.def("gemm_wgrad_segs", &gemm_wgrad_segs, "c (+)= sum_i a_i^T b_i (deferred micro-batch segments, w4)",
         py::arg("a"), py::arg("b"), py::arg("c"), py::arg("beta") = true);
   m.def("gemm_wgrad", &gemm_wgrad, "c (+)= a^T b (token-major bf16 operands)", py::arg("a"), py::arg("b"), py::arg("c"),

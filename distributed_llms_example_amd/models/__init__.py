@@ -1,5 +1,5 @@
-"""Encoder-decoder model families on the fused-op library: T5 / mT5 / FLAN-T5 (models/t5.py) and BART / mBART /
-Pegasus / Marian / M2M100-NLLB / PLBart /
+"""Encoder-decoder model families on the fused-op library: T5 / mT5 / FLAN-T5 / LongT5-local (models/t5.py) and BART /
+mBART / Pegasus / Marian / M2M100-NLLB / PLBart /
 Blenderbot (models/bart.py)."""
 from .bart import BartForConditionalGeneration
 from .config import PRESETS, Seq2SeqConfig, resolve_config

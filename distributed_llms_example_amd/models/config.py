@@ -21,7 +21,8 @@ from dataclasses import dataclass, field
 class Seq2SeqConfig:
     model_type: str = "t5"  # "t5" | BART family: "bart" | "mbart" | "pegasus" | "marian" | "m2m_100" | "plbart" | "blenderbot"
     # T5 implementation variants: "t5" / "mt5" (same layers), "umt5" (every self-attention layer owns its
-    # relative-position bias table: modeling_umt5.py UMT5LayerSelfAttention, has_relative_attention_bias=True)
+    # relative-position bias table: modeling_umt5.py UMT5LayerSelfAttention, has_relative_attention_bias=True),
+    # "longt5" (T5 v1.1 layers whose ENCODER self-attention is a sliding window: modeling_longt5.py)
     t5_flavor: str = "t5"
     vocab_size: int = 32128
     d_model: int = 512
@@ -33,6 +34,12 @@ class Seq2SeqConfig:
     # T5 relative position bias (modeling_t5.py:217-279)
     relative_attention_num_buckets: int = 32
     relative_attention_max_distance: int = 128
+    # LongT5 (t5_flavor="longt5"): "local" = every encoder query sees the keys within local_radius on either side.
+    # "transient-global" (global aggregate tokens of global_block_size inputs) is not implemented; global_block_size
+    # is only passed through config.json
+    encoder_attention_type: str = "local"
+    local_radius: int = 127
+    global_block_size: int = 16
     # "relu" (T5 v1.0), "gated-gelu" (flan / v1.1, gelu_new), "gelu" (BART, erf)
     feed_forward_proj: str = "relu"
     dropout_rate: float = 0.1
@@ -81,6 +88,10 @@ class Seq2SeqConfig:
         return self.model_type == "t5" and self.t5_flavor == "umt5"
 
     @property
+    def local_encoder(self) -> bool:
+        return self.model_type == "t5" and self.t5_flavor == "longt5"
+
+    @property
     def act(self) -> str:
         a = self.feed_forward_proj.split("-")[-1]
         if self.feed_forward_proj == "gated-gelu":
@@ -102,7 +113,8 @@ class Seq2SeqConfig:
         if self.model_type == "t5":
             d = {
                 "architectures": [{"t5": "T5ForConditionalGeneration", "mt5": "MT5ForConditionalGeneration",
-                                   "umt5": "UMT5ForConditionalGeneration"}[self.t5_flavor]],
+                                   "umt5": "UMT5ForConditionalGeneration",
+                                   "longt5": "LongT5ForConditionalGeneration"}[self.t5_flavor]],
                 "model_type": self.t5_flavor,
                 "vocab_size": self.vocab_size,
                 "d_model": self.d_model,
@@ -123,6 +135,9 @@ class Seq2SeqConfig:
                 "decoder_start_token_id": self.decoder_start_token_id,
                 "tie_word_embeddings": self.tie_word_embeddings,
             }
+            if self.local_encoder:
+                d.update(encoder_attention_type=self.encoder_attention_type, local_radius=self.local_radius,
+                         global_block_size=self.global_block_size)
         else:
             arch = {"bart": "BartForConditionalGeneration", "mbart": "MBartForConditionalGeneration",
                     "pegasus": "PegasusForConditionalGeneration", "marian": "MarianMTModel",
@@ -166,7 +181,15 @@ class Seq2SeqConfig:
     @classmethod
     def from_hf_dict(cls, d: dict) -> "Seq2SeqConfig":
         mt = d.get("model_type", "t5")
-        if mt in ("t5", "mt5", "umt5"):
+        if mt in ("t5", "mt5", "umt5", "longt5"):
+            extra = {}
+            if mt == "longt5":
+                eat = d.get("encoder_attention_type", "local")
+                if eat != "local":
+                    raise ValueError(f"unsupported LongT5 encoder_attention_type {eat!r}: only 'local' is implemented "
+                                     "(transient-global needs global aggregate tokens)")
+                extra = dict(encoder_attention_type=eat, local_radius=d.get("local_radius", 127),
+                             global_block_size=d.get("global_block_size", 16))
             ff = d.get("feed_forward_proj", "relu")
             nl = d.get("num_layers", 6)
             tie = d.get("tie_word_embeddings", True)
@@ -182,7 +205,7 @@ class Seq2SeqConfig:
                 initializer_factor=d.get("initializer_factor", 1.0),
                 tie_word_embeddings=tie, scale_decoder_outputs=tie,
                 pad_token_id=d.get("pad_token_id", 0), eos_token_id=_first(d.get("eos_token_id", 1)),
-                decoder_start_token_id=d.get("decoder_start_token_id", 0) or 0,
+                decoder_start_token_id=d.get("decoder_start_token_id", 0) or 0, **extra,
             )
         if mt in _FAMILY:
             fam = {"final_logits_bias": True, **_FAMILY[mt]}
@@ -288,6 +311,10 @@ PRESETS: dict[str, Seq2SeqConfig] = {
     "umt5-small": _t5("umt5-small", 512, 1024, 8, 6, ff="gated-gelu", tie=False, vocab=256384, flavor="umt5"),
     "umt5-base": _t5("umt5-base", 768, 2048, 12, 12, ff="gated-gelu", tie=False, vocab=256384, flavor="umt5"),
     "umt5-xl": _t5("umt5-xl", 2048, 5120, 24, 32, ff="gated-gelu", tie=False, vocab=256384, flavor="umt5"),
+    # LongT5-local: the T5 v1.1 shapes, encoder self-attention windowed to local_radius = 127 (LongT5Config's default).
+    # Shapes as published for google/long-t5-local-{base,large}; a checkpoint directory's config.json overrides them
+    "long-t5-local-base": _t5("long-t5-local-base", 768, 2048, 12, 12, ff="gated-gelu", tie=False, flavor="longt5"),
+    "long-t5-local-large": _t5("long-t5-local-large", 1024, 2816, 24, 16, ff="gated-gelu", tie=False, flavor="longt5"),
     "bart-base": Seq2SeqConfig(
         model_type="bart", name="bart-base", vocab_size=50265, d_model=768, d_kv=64, d_ff=3072, num_layers=6,
         num_decoder_layers=6, num_heads=12, feed_forward_proj="gelu", dropout_rate=0.1, attention_dropout=0.0,
@@ -329,6 +356,10 @@ PRESETS["nllb-200-distilled-600m"] = PRESETS["m2m100_418m"].replace(name="nllb-2
 PRESETS["t5-tiny"] = _t5("t5-tiny", 64, 128, 2, 4, vocab=512, d_kv=16)
 PRESETS["t5-tiny-gated"] = _t5("t5-tiny-gated", 64, 96, 2, 4, ff="gated-gelu", tie=False, vocab=512, d_kv=16)
 PRESETS["umt5-tiny"] = _t5("umt5-tiny", 64, 96, 2, 4, ff="gated-gelu", tie=True, vocab=512, d_kv=16, flavor="umt5")
+# radius 5: a 23-token input spans several windows
+PRESETS["longt5-tiny"] = _t5("longt5-tiny", 64, 128, 2, 4, vocab=512, d_kv=16, flavor="longt5").replace(local_radius=5)
+PRESETS["longt5-tiny-gated"] = _t5("longt5-tiny-gated", 64, 96, 2, 4, ff="gated-gelu", tie=False, vocab=512, d_kv=16,
+                                   flavor="longt5").replace(local_radius=5)
 PRESETS["bart-tiny"] = PRESETS["bart-base"].replace(name="bart-tiny", vocab_size=512, d_model=64, d_kv=16, d_ff=128,
                                                     num_layers=2, num_decoder_layers=2, num_heads=4,
                                                     max_position_embeddings=256)

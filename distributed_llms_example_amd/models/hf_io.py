@@ -59,6 +59,12 @@ def to_hf_state_dict(model) -> dict[str, torch.Tensor]:
                     done = True
             if not done:
                 out[name] = t
+    if cfg.local_encoder and not cfg.tie_word_embeddings:
+        # transformers' LongT5 ties encoder / decoder embed_tokens to `shared` only under tie_word_embeddings, so an
+        # untied checkpoint carries them (as the published LongT5 checkpoints do); without them it would load random
+        # embeddings.  Copies: safetensors refuses tensors that share memory
+        for stack in ("encoder", "decoder"):
+            out[f"{stack}.embed_tokens.weight"] = out["shared.weight"].clone()
     return {k: v.contiguous() for k, v in out.items()}
 
 

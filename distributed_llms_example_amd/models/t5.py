@@ -11,6 +11,11 @@ reference fine-tunes through ``AutoModelForSeq2SeqLM``), restructured for MI355X
 * the relative-position bias is a per-head LUT (ops/attention.py) — layer 0 owns the bucket table
   and every layer reuses it (modeling_t5.py:739-740), as in HF; UMT5 (``t5_flavor="umt5"``) gives every
   self-attention layer its own table (modeling_umt5.py UMT5LayerSelfAttention), one LUT per layer;
+* LongT5-local (``t5_flavor="longt5"``, modeling_longt5.py LongT5LocalAttention): the encoder's self-attention is a
+  sliding window of ``local_radius`` keys on either side with the same bias LUT, run by the windowed kernels
+  (ops/attention.py ``window``) in O(S·radius); its sub-layer is registered as ``LocalSelfAttention`` as in HF.  HF's
+  blocked formulation equals this band on every non-padded query row; padded rows differ (HF averages over masked
+  keys, here they follow the row-without-a-visible-key contract) and reach nothing cross-attention reads;
 * LM head + cross-entropy: logits in bf16, CE fused (ops/cross_entropy.py), the
   ``d_model**-0.5`` tied-embedding scale (modeling_t5.py:1044-1045) applied to the decoder output.
 """
@@ -41,9 +46,11 @@ class T5LayerNorm(nn.Module):
 
 
 class T5Attention(nn.Module):
-    def __init__(self, cfg: Seq2SeqConfig, cross: bool, has_relative_attention_bias: bool, is_decoder: bool):
+    def __init__(self, cfg: Seq2SeqConfig, cross: bool, has_relative_attention_bias: bool, is_decoder: bool,
+                 window: int | None = None):
         super().__init__()
         self.cfg = cfg
+        self.window = window  # LongT5-local encoder: keys within this distance only
         self.cross = cross
         self.is_decoder = is_decoder
         self.n_heads = cfg.num_heads
@@ -74,6 +81,8 @@ class T5Attention(nn.Module):
         H, D = self.n_heads, self.d_kv
         seed = default_rng().next_seed() if p > 0 else 0
         kw = dict(scale=1.0, causal=causal, key_padding_mask=mask, bias_lut=lut, dropout_p=p, seed=seed)
+        if self.window is not None:
+            kw["window"] = self.window
         if self.cross:
             q = self.q(x).view(B, S, H, D)
             kv = kv if kv is not None else self.project_kv(kv_in)
@@ -136,6 +145,16 @@ class T5LayerSelfAttention(nn.Module):
         self.layer_norm = T5LayerNorm(cfg.d_model, cfg.layer_norm_epsilon)
 
 
+class T5LayerLocalSelfAttention(nn.Module):
+    """LongT5's encoder self-attention sub-layer (modeling_longt5.py LongT5LayerLocalSelfAttention)."""
+
+    def __init__(self, cfg, has_bias):
+        super().__init__()
+        self.LocalSelfAttention = T5Attention(cfg, cross=False, has_relative_attention_bias=has_bias,
+                                              is_decoder=False, window=cfg.local_radius)
+        self.layer_norm = T5LayerNorm(cfg.d_model, cfg.layer_norm_epsilon)
+
+
 class T5LayerCrossAttention(nn.Module):
     def __init__(self, cfg):
         super().__init__()
@@ -153,13 +172,20 @@ class T5LayerFF(nn.Module):
 class T5Block(nn.Module):
     def __init__(self, cfg, has_bias, is_decoder):
         super().__init__()
-        self.layer = nn.ModuleList([T5LayerSelfAttention(cfg, has_bias, is_decoder)])
+        local = cfg.local_encoder and not is_decoder
+        self.layer = nn.ModuleList([T5LayerLocalSelfAttention(cfg, has_bias) if local else
+                                    T5LayerSelfAttention(cfg, has_bias, is_decoder)])
         if is_decoder:
             self.layer.append(T5LayerCrossAttention(cfg))
         self.layer.append(T5LayerFF(cfg))
 
     def norms(self):
         return [lyr.layer_norm for lyr in self.layer]
+
+    @property
+    def self_attention(self) -> T5Attention:
+        lyr = self.layer[0]
+        return lyr.LocalSelfAttention if isinstance(lyr, T5LayerLocalSelfAttention) else lyr.SelfAttention
 
 
 class T5Stack(nn.Module):
@@ -192,15 +218,17 @@ class T5Stack(nn.Module):
         B, S = input_ids.shape
         k_len = S + q_offset
         cp = getattr(self, "_cp_group", False)
-        chunk = long_sequence_chunk(S, rows=B * cfg.num_heads) if not self.is_decoder and caches is None else None
+        # a windowed encoder is O(S·radius) in one launch on kernels without an LDS-bounded length: never chunked
+        chunk = (long_sequence_chunk(S, rows=B * cfg.num_heads)
+                 if not self.is_decoder and caches is None and not cfg.local_encoder else None)
         blocks = list(self.block)
         # T5 / mT5: layer 0's table serves every layer; UMT5: each layer's own table
         owners = blocks if cfg.per_layer_position_bias else blocks[:1]
         if (cp is not False or chunk is not None) and not self.is_decoder:
-            luts = [_CPBias(cp, b.layer[0].SelfAttention.relative_attention_bias.weight,
+            luts = [_CPBias(cp, b.self_attention.relative_attention_bias.weight,
                             chunk=chunk if cp is False else None) for b in owners]
         else:
-            luts = [b.layer[0].SelfAttention.bias_lut(S, k_len, q_offset=q_offset) for b in owners]
+            luts = [b.self_attention.bias_lut(S, k_len, q_offset=q_offset) for b in owners]
         # h = dropout(embeddings); normed = block0 self-attn norm(h)
         normed, h = norms.dropout_rms_norm(x, blocks[0].layer[0].layer_norm.weight, eps, p,
                                            rng.next_seed() if p > 0 else 0)
@@ -227,7 +255,7 @@ class T5Stack(nn.Module):
         rng = default_rng()
         subs = list(blk.layer)
         norms_w = [lyr.layer_norm.weight for lyr in subs[1:]] + [next_norm]
-        a = subs[0].SelfAttention(normed, mask=attention_mask if not self.is_decoder else None, lut=lut,
+        a = blk.self_attention(normed, mask=attention_mask if not self.is_decoder else None, lut=lut,
                                   causal=self.is_decoder, p=pa, cache=cache)
         normed, h = norms.add_dropout_rms_norm(h, a, norms_w[0], eps, p, rng.next_seed() if p > 0 else 0)
         j = 1
@@ -334,6 +362,9 @@ class T5ForConditionalGeneration(nn.Module):
         and the full decoder batch.  Encoder self-attention becomes ring attention (parallel/context.py); the
         encoder output is all-gathered along the sequence for the decoder, which every CP rank runs on the
         same batch.  The dropout seed stream must be identical on the ranks of one CP group."""
+        if enable and self.config.local_encoder:
+            raise NotImplementedError("context parallelism is not implemented for LongT5: ring attention has no "
+                                      "sliding window")
         if enable:
             self.encoder._cp_group = group
         elif hasattr(self.encoder, "_cp_group"):

@@ -21,6 +21,10 @@ Kernels: csrc/attn.hip (bf16, head dim 64: forward; backward = dQ kernel + dK/dV
 LUT), csrc/attn_hd.hip (bf16, every other head dim 32 .. 128 that is a multiple of 8: the same op templated on the
 padded head dim) and csrc/attn_f32.hip (fp32 at head dim 64, the reference's own precision: the same op on the
 f32-input matrix cores).  All are O(S) memory.  ``_route`` picks one; what none serves takes the O(Sq·Sk) composite.
+
+Sliding window (LongT5-local encoder self-attention): ``window=w`` keeps key ``j`` for query ``i`` only when
+``|j - i| <= w`` (``Sq == Sk``, not causal).  csrc/attn_hd.hip (bf16, head dim 64 included) and csrc/attn_f32.hip skip
+the key blocks outside the band, O(S·w) work; csrc/attn.hip has no window.  The composite masks a full score matrix.
 """
 from __future__ import annotations
 
@@ -97,7 +101,7 @@ def saturated_ranges(idx: torch.Tensor) -> tuple[int, int]:
 # --------------------------------------------------------------------------- reference
 
 
-def _reference(q, k, v, scale, causal, kpm, lut, p, seed):
+def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None):
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     qf = q.float().permute(0, 2, 1, 3)
@@ -114,12 +118,26 @@ def _reference(q, k, v, scale, causal, kpm, lut, p, seed):
         off = Sk - Sq
         cm = torch.arange(Sk, device=q.device)[None, :] > (torch.arange(Sq, device=q.device)[:, None] + off)
         s = s.masked_fill(cm, neg)
+    if window is not None:
+        _check_window(window, Sq, Sk, causal)
+        dist = torch.arange(Sk, device=q.device)[None, :] - torch.arange(Sq, device=q.device)[:, None]
+        s = s.masked_fill(dist.abs() > window, neg)
     pr = torch.softmax(s, dim=-1)
     if p > 0.0:
         keep = attention_keep_mask(seed, p, B, H, Sq, Sk, q.device)
         pr = pr * keep.to(pr.dtype) * (1.0 / (1.0 - p))
     o = torch.matmul(pr, vf)
     return o.permute(0, 2, 1, 3).to(q.dtype)
+
+
+def _check_window(window, Sq, Sk, causal) -> None:
+    """A window is a band around the diagonal of a square, non-causal problem (csrc/attn_params.h)."""
+    if window < 0:
+        raise ValueError(f"attention: window must be >= 0 or None, got {window}")
+    if Sq != Sk:
+        raise ValueError(f"attention: window needs Sq == Sk, got {Sq} and {Sk}")
+    if causal:
+        raise ValueError("attention: window with causal is unsupported")
 
 
 # --------------------------------------------------------------------------- native
@@ -133,9 +151,10 @@ def _split(mode, a, b, c):
     return a, b, c
 
 
-def _tuned(q) -> bool:
-    """csrc/attn.hip serves the call (bf16, head dim 64); else csrc/attn_f32.hip (fp32) or csrc/attn_hd.hip (bf16)."""
-    return q.dtype != torch.float32 and q.shape[-1] == 64
+def _tuned(q, window=None) -> bool:
+    """csrc/attn.hip serves the call (bf16, head dim 64, no window); else csrc/attn_f32.hip (fp32) or
+    csrc/attn_hd.hip (bf16)."""
+    return q.dtype != torch.float32 and q.shape[-1] == 64 and window is None
 
 
 class _AttnFn(torch.autograd.Function):
@@ -144,26 +163,27 @@ class _AttnFn(torch.autograd.Function):
     gradient buffer through strided views instead of three zero-padded slice gradients."""
 
     @staticmethod
-    def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed):
+    def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed, window=None):
         C = _ext.native()
         q, k, v = _split(mode, a, b, c)
         args = (q, k, v, kpm, lut, float(scale), bool(causal), float(p), int(seed))
         sat_lo = sat_hi = -1
         dmask = None
-        if _tuned(q):
+        if _tuned(q, window):
             # saturated bias tiles add a scalar instead of reading the LUT (forward -2 %)
             sat = getattr(lut, "_dllm_sat", None) if lut is not None else None
             sat_lo, sat_hi = sat if sat is not None else (-1, -1)
             o, lse, dmask = C.attn_fwd(*args, sat_lo, sat_hi)
         else:
-            o, lse = (C.attn_f32_fwd if q.dtype == torch.float32 else C.attn_hd_fwd)(*args)
+            o, lse = (C.attn_f32_fwd if q.dtype == torch.float32 else C.attn_hd_fwd)(
+                *args, -1 if window is None else int(window))
         ctx.save_for_backward(a, b, c, o, lse, lut, kpm, dmask)
-        ctx.cfg = (mode, scale, causal, p, seed, lut is not None and lut.requires_grad, sat_lo, sat_hi)
+        ctx.cfg = (mode, scale, causal, p, seed, lut is not None and lut.requires_grad, sat_lo, sat_hi, window)
         # packed inputs straight from a biased projection (ops/linear.py marks its output): the backward kernels also
         # sum dQ / dK / dV over tokens for that projection's bias gradient (colsum_record).  csrc/attn.hip only (the
         # partials hard-code H * 64) and bias-LUT-free calls only (its column-sum variants exist for those); everything
         # else takes the separate reduction, as with BIAS_COLSUM = False
-        cs_ok = BIAS_COLSUM and lut is None and _tuned(q)
+        cs_ok = BIAS_COLSUM and lut is None and _tuned(q, window)
         ctx.cs = (cs_ok and mode != "sep" and _bias_out(a), cs_ok and mode == "q_kv" and _bias_out(b))
         # ops/linear.py stacked_linear: the packed kv is a slice of a multi-layer projection and its
         # gradient has a home in the stacked gradient buffer — write dK/dV there directly
@@ -174,7 +194,7 @@ class _AttnFn(torch.autograd.Function):
     def backward(ctx, do):
         C = _ext.native()
         a, b, c, o, lse, lut, kpm, dmask = ctx.saved_tensors
-        mode, scale, causal, p, seed, need_dlut, sat_lo, sat_hi = ctx.cfg
+        mode, scale, causal, p, seed, need_dlut, sat_lo, sat_hi, window = ctx.cfg
         q, k, v = _split(mode, a, b, c)
         da = db = dc = None
         if mode == "qkv":
@@ -205,10 +225,11 @@ class _AttnFn(torch.autograd.Function):
                     csk, csv = pkv[:, :HD], pkv[:, HD:]
         args = (do.contiguous(), q, k, v, o, lse, kpm, lut, float(scale), bool(causal), float(p), int(seed),
                 bool(need_dlut), dq, dk, dv)
-        if _tuned(q):
+        if _tuned(q, window):
             rq, rk, rv, dlut = C.attn_bwd(*args, dmask, sat_lo, sat_hi, csq, csk, csv)
         else:
-            rq, rk, rv, dlut = (C.attn_f32_bwd if q.dtype == torch.float32 else C.attn_hd_bwd)(*args)
+            rq, rk, rv, dlut = (C.attn_f32_bwd if q.dtype == torch.float32 else C.attn_hd_bwd)(
+                *args, -1 if window is None else int(window))
         if part is not None:  # per-block partials, reduced by the consumer into the bias gradient (ops/gemm.py)
             colsum_record(da, part)
         if pq is not None:
@@ -218,7 +239,7 @@ class _AttnFn(torch.autograd.Function):
         if mode == "sep":
             da, db, dc = rq, rk, rv
         streams.pair_join()  # side-stream weight gradients paired with these VALU-bound kernels (ops/streams.py)
-        return None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None
+        return None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None, None
 
 
 # False: the projections' bias gradients from a separate column reduction of dQKV (tests flip the module attribute)
@@ -253,7 +274,8 @@ def _warn_composite(reason: str, t) -> None:
     get_logger().warning(
         "attention: no HIP kernel for %s (head dim %d, %s); running the composite, which materialises fp32 "
         "[B, H, Sq, Sk] scores, masks and probabilities: O(Sq*Sk) memory and time.  The kernels take bf16 at head dims "
-        "32 .. 128 that are multiples of 8 with 16-byte aligned rows, and fp32 at head dim 64.",
+        "32 .. 128 that are multiples of 8 with 16-byte aligned rows, and fp32 at head dim 64, with or without a "
+        "sliding window.",
         reason, t.shape[-1], str(t.dtype).replace("torch.", ""))
 
 
@@ -262,13 +284,13 @@ def _aligned(t) -> bool:
     return t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
 
 
-def _route(t, *rest):
+def _route(t, *rest, window=None):
     """Which kernel family serves a call whose q (or packed qkv) is ``t`` — by ops/routing.py ``attention_route``:
 
-    * ``"attn.hip"``: bf16, head dim 64 (csrc/attn.hip, the tuned kernels);
+    * ``"attn.hip"``: bf16, head dim 64, no ``window`` (csrc/attn.hip, the tuned kernels);
     * ``"attn_hd.hip"``: bf16, any other head dim 32 .. 128 with ``D % 8 == 0`` and 16-byte aligned rows in ``t`` and
       ``rest`` (csrc/attn_hd.hip; blenderbot-400m has 40, t5-3b / t5-11b / nllb-3.3B 128, blenderbot-3B 80; ``attn_hd``
-      = 0 sends them to the composite, A/B);
+      = 0 sends them to the composite, A/B), and with a ``window`` head dim 64 too;
     * ``"attn_f32.hip"``: fp32 at head dim 64 — the reference's own precision (ref/train-torchrun.py:115-128 sets
       neither bf16 nor fp16; Accelerate's default mixed_precision is 'no') — on the f32-input MFMA (``attn_f32`` = 0
       sends it to the composite, A/B);
@@ -282,41 +304,54 @@ def _route(t, *rest):
     if not bf16 and t.dtype != torch.float32:
         _warn_composite("this dtype", t)
         return None
-    r = routing.attention_route(D, bf16)
+    r = routing.attention_route(D, bf16, window)
     if r == "attn_hd.hip" and not all(_aligned(x) for x in (t,) + rest if x is not None):
         _warn_composite("unaligned rows", t)
         return None
     if r == "composite":
-        if D != 64 and not (bf16 and 32 <= D <= 128 and D % 8 == 0):  # (else: switched off by DLLM_ROUTE)
+        served = D == 64 and window is None or bf16 and 32 <= D <= 128 and D % 8 == 0 or not bf16 and D == 64
+        if not served:  # (else: switched off by DLLM_ROUTE)
             _warn_composite("this head dim" if bf16 else "fp32 at this head dim", t)
         return None
     return r
 
 
-def _native(t, *rest) -> bool:
-    return _route(t, *rest) is not None
+def _native(t, *rest, window=None) -> bool:
+    return _route(t, *rest, window=window) is not None
 
 
 def attention(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_mask=None, bias_lut=None,
-              dropout_p: float = 0.0, seed: int = 0):
+              dropout_p: float = 0.0, seed: int = 0, window: int | None = None):
     """Multi-head attention.  q ``[B,Sq,H,D]``, k/v ``[B,Sk,H,D]``; ``key_padding_mask`` bool
-    ``[B,Sk]`` (True = attend); ``bias_lut`` from :func:`relative_bias_lut`."""
-    if _native(q, k, v):
-        return _AttnFn.apply("sep", q, k, v, bias_lut, _prep_kpm(key_padding_mask), scale, causal, dropout_p, seed)
-    return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed)
+    ``[B,Sk]`` (True = attend); ``bias_lut`` from :func:`relative_bias_lut`; ``window``: keys with
+    ``|j - i| > window`` are masked (needs ``Sq == Sk`` and ``causal=False``; None: full attention)."""
+    if window is not None:
+        _check_window(window, q.shape[1], k.shape[1], causal)
+    if _native(q, k, v, window=window):
+        return _AttnFn.apply("sep", q, k, v, bias_lut, _prep_kpm(key_padding_mask), scale, causal, dropout_p, seed,
+                             window)
+    return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed, window)
 
 
 def attention_qkv(qkv, **kw):
     """Self-attention on the fused projection output ``qkv`` = [B, S, 3, H, D]."""
-    if _native(qkv):
+    window = kw.get("window")
+    if window is not None:
+        _check_window(window, qkv.shape[1], qkv.shape[1], kw.get("causal", False))
+    if _native(qkv, window=window):
         return _AttnFn.apply("qkv", qkv, None, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
-                             kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0))
+                             kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
+                             window)
     return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], **kw)
 
 
 def attention_q_kv(q, kv, **kw):
     """Cross-attention with q = [B, Sq, H, D] and the fused key/value projection kv = [B, Sk, 2, H, D]."""
-    if _native(q, kv):
+    window = kw.get("window")
+    if window is not None:
+        _check_window(window, q.shape[1], kv.shape[1], kw.get("causal", False))
+    if _native(q, kv, window=window):
         return _AttnFn.apply("q_kv", q, kv, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
-                             kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0))
+                             kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
+                             window)
     return attention(q, kv[:, :, 0], kv[:, :, 1], **kw)

@@ -44,6 +44,11 @@ causal, >= 2 key blocks)       once, no dQ kernel) when B x H >= 6 per CU (``att
 attention, head dim != 64      bf16 at head dims 32 .. 128 (% 8 == 0): csrc/attn_hd.hip      attn_hd_vs_composite.txt
                                (``attn_hd`` = 1; 0: the O(Sq·Sk) composite); anything
                                else: the composite, with a one-time warning
+sliding-window attention       bf16 at head dims 32 .. 128 (% 8 == 0), 64 included:          attn_window_vs_full.txt
+(LongT5-local encoder)         csrc/attn_hd.hip; fp32 at head dim 64: csrc/attn_f32.hip.
+                               Their block walks skip the blocks outside the band
+                               (O(S·w)); csrc/attn.hip has no window; anything else: the
+                               O(S²) composite, with a one-time warning
 long-context attention         query chunks of ``attn_chunk`` rows from ``attn_chunk_min``   (parallel/context.py)
 weight gradients, small        side stream for micro-batches <= ``wgrad_stream_max_tokens``  r4_wgrad_stream_ab.txt
 micro-batches                  (``wgrad_stream`` = auto | 1 | 0)
@@ -156,10 +161,12 @@ def get(key: str):
     return ov[key] if key in ov else DEFAULTS[key]
 
 
-def attention_route(head_dim: int, bf16: bool = True) -> str:
+def attention_route(head_dim: int, bf16: bool = True, window: int | None = None) -> str:
     """Kernel family of an attention call on the GPU by head dim and dtype (bf16, else fp32): ``"attn.hip"``,
-    ``"attn_hd.hip"``, ``"attn_f32.hip"`` or ``"composite"`` — the rule ops/attention.py ``_route`` applies."""
-    if head_dim == 64:
+    ``"attn_hd.hip"``, ``"attn_f32.hip"`` or ``"composite"`` — the rule ops/attention.py ``_route`` applies.
+    ``window``: the call's sliding window (None: full attention).  csrc/attn.hip has no window, so a windowed bf16
+    call at head dim 64 runs csrc/attn_hd.hip's 64-wide instantiation."""
+    if head_dim == 64 and (window is None or not bf16):
         return "attn.hip" if bf16 else ("attn_f32.hip" if get("attn_f32") else "composite")
     if bf16 and 32 <= head_dim <= 128 and head_dim % 8 == 0 and get("attn_hd"):
         return "attn_hd.hip"
@@ -167,10 +174,11 @@ def attention_route(head_dim: int, bf16: bool = True) -> str:
 
 
 def plan(model: str, tokens_enc: int, tokens_dec: int, d_model: int, d_ff: int, act: str, vocab: int, *,
-         head_dim: int = 64) -> dict:
+         head_dim: int = 64, window: int | None = None) -> dict:
     """What the table routes for one training step of an encoder-decoder model with these shapes (per micro-batch
     token rows): a dict op -> kernel family, as the tests and docs/ARCHITECTURE.md read it.  ``head_dim``: the
-    model's attention head dim (bf16 step)."""
+    model's attention head dim (bf16 step); ``window``: the encoder self-attention's sliding window (LongT5-local),
+    reported as ``attention.window`` with its kernel family under ``enc.self_attention``."""
     rows = {"enc": tokens_enc, "dec": tokens_dec}
     out = {}
     dmode = get("proj_dgrad")
@@ -200,4 +208,7 @@ def plan(model: str, tokens_enc: int, tokens_dec: int, d_model: int, d_ff: int, 
     out["lm_head"] = ("w4-fused-ce" if lm == "fused" or (lm == "auto" and logits_mb > get("lmhead_full_mb"))
                       else "hipblaslt+ce")
     out["attention"] = attention_route(head_dim)
+    if window is not None:
+        out["attention.window"] = int(window)
+        out["enc.self_attention"] = attention_route(head_dim, True, window)
     return out

@@ -2,7 +2,11 @@
 
 ``--head-dim D`` runs the cases at another head dim (default 64: csrc/attn.hip; others: csrc/attn_hd.hip).
 ``--vs-composite B,H,S,bias,kpm,causal,p`` times forward + backward of the kernel and of the composite
-(``A._reference`` on the same bf16 inputs) interleaved in one process, at ``--head-dim``."""
+(``A._reference`` on the same bf16 inputs) interleaved in one process, at ``--head-dim``.
+``--window W --shape B,H,S[,bias,p]`` times forward + backward of three arms interleaved in one process: the windowed
+kernels (csrc/attn_hd.hip, ``window=W``), the same kernels walking every block (``window=S``: masks and skips nothing,
+bitwise the unwindowed call) and what a T5 encoder runs for full attention at that length (csrc/attn.hip at head dim
+64: one call, or above ``attn_chunk_min`` tokens the chunked blocks of parallel/context.py)."""
 import argparse
 import json
 import time
@@ -106,13 +110,77 @@ def vs_composite(B, H, S, bias, kpm, causal, p, D, reps=3, iters=5):
             "composite_tflops": fl / (sorted(tc)[len(tc) // 2] * 1e-3) / 1e12}
 
 
+def vs_window(B, H, S, W, bias, p, D, reps=5, iters=5):
+    """Forward + backward of windowed against full attention on the same bf16 inputs: warm-up, then ``reps`` rounds of
+    ``iters`` calls per arm, the arms interleaved within every round, device-event times, medians."""
+    dev = "cuda"
+    qkv = torch.randn(B, S, 3, H, D, device=dev, dtype=torch.bfloat16, requires_grad=True)
+    tab = torch.randn(32, H, device=dev, requires_grad=True) if bias else None
+    g = torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16)
+
+    def arm(window):
+        def f():
+            lut = A.relative_bias_lut(tab, S, S, True, 32, 128) if bias else None
+            A.attention_qkv(qkv, scale=1.0, bias_lut=lut, dropout_p=p, seed=1, window=window).backward(g)
+            qkv.grad = None
+        return f
+
+    from distributed_llms_example_amd.parallel.context import chunked_attention, long_sequence_chunk
+    chunk = long_sequence_chunk(S, rows=B * H)
+
+    def full():  # what models/t5.py does for a plain T5 encoder of this length
+        if chunk is None:
+            return arm(None)()
+        chunked_attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], chunk=chunk, scale=1.0, bias_table=tab,
+                          bidirectional=True, num_buckets=32, max_distance=128, dropout_p=p, seed=1).backward(g)
+        qkv.grad = None
+
+    arms = {"window": arm(W), "same_kernels_full": arm(S), "routed_full": full}
+    routes = {"window": A._route(qkv, window=W), "same_kernels_full": A._route(qkv, window=S),
+              "routed_full": A._route(qkv) + (f" in {chunk}-token blocks" if chunk else "")}
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    for _ in range(2):
+        for fn in arms.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {n: [] for n in arms}
+    for _ in range(reps):
+        for n, fn in arms.items():
+            ms[n].append(timed(fn))
+    med = {n: sorted(t)[len(t) // 2] for n, t in ms.items()}
+    nb = (S + 63) // 64
+    band = 2 * ((W + 63) // 64) + 1
+    return {"B": B, "H": H, "S": S, "D": D, "window": W, "bias": bias, "p": p, "routes": routes,
+            "ms": {n: [round(x, 4) for x in t] for n, t in ms.items()},
+            "median_ms": {n: round(x, 4) for n, x in med.items()},
+            "key_blocks_per_query_block": {"window": min(band, nb), "full": nb},
+            "speedup_vs_same_kernels_full": med["same_kernels_full"] / med["window"],
+            "speedup_vs_routed_full": med["routed_full"] / med["window"]}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--ab", action="store_true", help="repeat every case 3x")
     ap.add_argument("--head-dim", type=int, default=64)
     ap.add_argument("--vs-composite", default="", help="B,H,S,bias,kpm,causal,p: kernel against the composite")
+    ap.add_argument("--window", type=int, default=None, help="with --shape: windowed against full attention")
+    ap.add_argument("--shape", default="1,32,4096,1,0.1", help="B,H,S[,bias,p] of the --window run")
     a = ap.parse_args()
+    if a.window is not None:
+        f = a.shape.split(",")
+        print(json.dumps(vs_window(int(f[0]), int(f[1]), int(f[2]), a.window, f[3] == "1" if len(f) > 3 else True,
+                                   float(f[4]) if len(f) > 4 else 0.1, a.head_dim)), flush=True)
+        sys.exit(0)
     if a.vs_composite:
         f = a.vs_composite.split(",")
         print(json.dumps(vs_composite(int(f[0]), int(f[1]), int(f[2]), f[3] == "1", f[4] == "1", f[5] == "1",
