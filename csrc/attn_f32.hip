@@ -6,6 +6,8 @@
 // probabilities are never materialised (the fp32 composite it replaces stored [B, H, Sq, Sk] scores + masks).
 // Sliding window (AttnParamsT::window >= 0; Sq == Sk, not causal): as in csrc/attn_hd.hip, the block walks cover only
 // the blocks that intersect the band (attn_small.h band_range) and the element mask gains |key - row| > w (off_band).
+// Segments (AttnParamsT::q_seg / k_seg, sequence packing): as in csrc/attn_hd.hip, blocks of other segments are skipped
+// by their (min, max) id tables (seg_apart) and the element mask gains "same non-negative id" (seg_bits).
 //
 // Layout trick (no transposes through LDS for P or dS): the 16x16x4 f32 MFMA's C/D map puts rows 4g .. 4g+3
 // (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction index k = g from
@@ -73,18 +75,23 @@ DLLM_DEVICE f32x4 rd_col4(const float* tr, int col, int r4) {
   return *reinterpret_cast<const f32x4*>(tr + col * 64 + ((((r4 >> 2) ^ (col & 15))) << 2));
 }
 
+// The second __launch_bounds__ argument of the three kernels is the waves per SIMD their register counts gave before
+// the segment hooks (3, 2, 2): with it the unsegmented fp32 step measures as before, at fewer registers
+// (profiles/packing_regression_gate.txt; without it 0.7 % slower).
 // ================================================================================================ forward
 template <bool DROP>
-__global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(AttnF32Params P) {
+__global__ __launch_bounds__(NT, 3) void attn_f32_fwd_kernel(AttnF32Params P) {
   __shared__ __attribute__((aligned(16))) float Ks[BKY * D];
   __shared__ __attribute__((aligned(16))) float Vt[D * BKY];
   __shared__ float Ls[2 * BKY];
-  __shared__ uint8_t Mk[BKY];  // 1: key valid (in range, not padding)
+  __shared__ __attribute__((aligned(16))) uint8_t Mk[BKY];  // 1: key valid (in range, not padding)
+  __shared__ __attribute__((aligned(16))) int Sg[BKY];  // the keys' segment ids (with segments)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
   const int bh = blockIdx.y, b = bh / P.H, h = bh % P.H;
   const int q0 = blockIdx.x * BQ;
   const int row = q0 + 16 * w + c;
   const int rowc = min(row, P.Sq - 1);
+  const int qsg = P.q_seg ? seg_at(P.q_seg, b, P.Sq, row) : 0;
   float qf[16];
   {
     const float* qp = P.q + (long)b * P.q_sb + (long)rowc * P.q_ss + (long)h * P.q_sh + 16 * g;
@@ -110,12 +117,17 @@ __global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(AttnF32Params P) {
   int kstart = 0;
   band_range(P, q0, kstart, kend);
   for (int k0 = kstart; k0 < kend; k0 += BKY) {
+    if (seg_apart(P, b, q0, k0)) continue;
     __syncthreads();  // the previous block's LDS reads are done
     stage<true, false>(kb, P.k_ss, k0, P.Sk, Ks, nullptr, tid);
     stage<false, true>(vb, P.v_ss, k0, P.Sk, nullptr, Vt, tid);
     stage_bias(P, h, q0, k0, Ls, tid, 1.f);
-    if (tid < BKY) Mk[tid] = key_ok(P, b, k0 + tid);
+    if (tid < BKY) {
+      Mk[tid] = key_ok(P, b, k0 + tid);
+      if (P.q_seg) Sg[tid] = seg_at(P.k_seg, b, P.Sk, k0 + tid);
+    }
     __syncthreads();
+    const uint32_t vis = key_bits(P, Mk, Sg, qsg, g);  // key valid and of the row's segment
     f32x4 st[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -134,7 +146,7 @@ __global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(AttnF32Params P) {
         const int key = k0 + 16 * t + 4 * g + i;
         float x = st[t][i] * P.scale;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        if (!Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off) || off_band(P, row, key)) x = -INFINITY;
+        if (hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key)) x = -INFINITY;
         st[t][i] = x;
         mx = fmaxf(mx, x);
       }
@@ -202,18 +214,20 @@ __global__ __launch_bounds__(NT) void attn_f32_delta_kernel(AttnF32Params P) {
 }
 
 template <bool DROP>
-__global__ __launch_bounds__(NT) void attn_f32_dq_kernel(AttnF32Params P) {
+__global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
   __shared__ __attribute__((aligned(16))) float Ks[BKY * D];
   __shared__ __attribute__((aligned(16))) float Kt[D * BKY];
   __shared__ __attribute__((aligned(16))) float Vs[BKY * D];
   __shared__ float Ls[2 * BKY];
   __shared__ float Ds[BQ * (BKY + 1)];  // dS tile of the block, row stride 65: a diagonal walk is bank-conflict free
-  __shared__ uint8_t Mk[BKY];
+  __shared__ __attribute__((aligned(16))) uint8_t Mk[BKY];
+  __shared__ __attribute__((aligned(16))) int Sg[BKY];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
   const int bh = blockIdx.y, b = bh / P.H, h = bh % P.H;
   const int q0 = blockIdx.x * BQ;
   const int row = q0 + 16 * w + c;
   const int rowc = min(row, P.Sq - 1);
+  const int qsg = P.q_seg ? seg_at(P.q_seg, b, P.Sq, row) : 0;
   const bool row_ok = row < P.Sq;
   float qf[16], dof[16];
   {
@@ -242,12 +256,17 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(AttnF32Params P) {
   int kstart = 0;
   band_range(P, q0, kstart, kend);
   for (int k0 = kstart; k0 < kend; k0 += BKY) {
+    if (seg_apart(P, b, q0, k0)) continue;
     __syncthreads();
     stage<true, true>(kb, P.k_ss, k0, P.Sk, Ks, Kt, tid);
     stage<true, false>(vb, P.v_ss, k0, P.Sk, Vs, nullptr, tid);
     stage_bias(P, h, q0, k0, Ls, tid, 1.f);
-    if (tid < BKY) Mk[tid] = key_ok(P, b, k0 + tid);
+    if (tid < BKY) {
+      Mk[tid] = key_ok(P, b, k0 + tid);
+      if (P.q_seg) Sg[tid] = seg_at(P.k_seg, b, P.Sk, k0 + tid);
+    }
     __syncthreads();
+    const uint32_t vis = key_bits(P, Mk, Sg, qsg, g);  // key valid and of the row's segment
     f32x4 st[4], dpt[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -271,7 +290,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(AttnF32Params P) {
         const int di = key - row - (k0 - q0 - 63);
         float x = st[t][i] * P.scale;
         if (P.lut) x += Ls[di];
-        const bool msk = !Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
+        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
         const float pr = msk ? 0.f : __expf(x - lse);
         const float dpk = DROP ? (((kb4 >> i) & 1u) ? dpt[t][i] * dscale : 0.f) : dpt[t][i];
         const float ds = pr * (dpk - dlt);
@@ -303,7 +322,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(AttnF32Params P) {
 }
 
 template <bool DROP>
-__global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(AttnF32Params P) {
+__global__ __launch_bounds__(NT, 2) void attn_f32_dkdv_kernel(AttnF32Params P) {
   __shared__ __attribute__((aligned(16))) float Qs[BQ * D];
   __shared__ __attribute__((aligned(16))) float Qt[D * BQ];
   __shared__ __attribute__((aligned(16))) float Os[BQ * D];  // dO, row-major
@@ -311,6 +330,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(AttnF32Params P) {
   __shared__ float Ls[2 * BQ];
   __shared__ float Rl[BQ], Rd[BQ];
   __shared__ uint32_t Rh[BQ];
+  __shared__ __attribute__((aligned(16))) int Rs[BQ];  // the rows' segment ids (with segments)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
   const int bh = blockIdx.y, b = bh / P.H, h = bh % P.H;
   const int k0 = blockIdx.x * BKY;
@@ -331,6 +351,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(AttnF32Params P) {
   const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
   const uint32_t seed = DROP ? eff_seed(P.seed) : 0u;
   const bool kok = key_ok(P, b, key);
+  const int ksg = P.q_seg ? seg_at(P.k_seg, b, P.Sk, key) : 0;
   f32x4 dk[4], dv[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -344,6 +365,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(AttnF32Params P) {
   int qend = P.Sq;
   band_range(P, k0, qstart, qend);
   for (int q0 = qstart; q0 < qend; q0 += BQ) {
+    if (seg_apart(P, b, q0, k0)) continue;
     __syncthreads();
     stage<true, true>(qb, P.q_ss, q0, P.Sq, Qs, Qt, tid);
     stage<true, true>(ob, P.do_ss, q0, P.Sq, Os, Ot, tid);
@@ -354,8 +376,10 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(AttnF32Params P) {
       Rl[tid] = ok ? P.lse[(long)bh * P.Sq + r] : INFINITY;
       Rd[tid] = ok ? P.delta[(long)bh * P.Sq + r] : 0.f;
       if (DROP) Rh[tid] = mix32(seed, (uint32_t)((long)bh * P.Sq + min(r, P.Sq - 1)));
+      if (P.q_seg) Rs[tid] = seg_at(P.q_seg, b, P.Sq, r);
     }
     __syncthreads();
+    const uint32_t vis = kok ? seg_bits(P, Rs, ksg, g) : 0u;  // key valid and of the rows' segments
     f32x4 sc[4], dp[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -379,7 +403,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(AttnF32Params P) {
         const int rl = 16 * t + 4 * g + i, row = q0 + rl;
         float x = sc[t][i] * P.scale;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        const bool msk = !kok || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
+        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
         const float pr = msk ? 0.f : __expf(x - Rl[rl]);
         const bool kp = DROP ? keep_key(Rh[rl], key, P.thr) : true;
         const float dpk = kp ? dp[t][i] * dscale : 0.f;

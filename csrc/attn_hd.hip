@@ -15,6 +15,12 @@
 // (attn_small.h band_range) — the others are never loaded — and the element mask gains |key - row| > w (off_band).
 // Windowed calls at head dim 64 run here too (DP = 64): csrc/attn.hip has no window.
 //
+// Segments (AttnParamsT::q_seg / k_seg, sequence packing): the element mask gains "same non-negative id" (attn_small.h
+// seg_bits / key_bits: one 16-bit visibility word per lane and block from the ids and key validity staged in LDS) and
+// the walks skip — never load — the blocks whose (min, max) id range does not overlap the workgroup's own (seg_apart,
+// uniform per workgroup, so the barriers stay matched).  A runtime flag like the window; packed calls at head dim 64
+// run here too.
+//
 // Layout trick of csrc/attn_f32.hip, carried over to the 16x16x32 bf16 MFMA: its C/D map puts rows 4g .. 4g+3
 // (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction indices k = 8g + j
 // (j = 0 .. 7) from lane group g.  S^T = K Q^T leaves each lane with keys 16t + 4g + i of ONE query row; two such
@@ -110,19 +116,29 @@ DLLM_DEVICE bf16x8v pack8(f32x4 a, f32x4 b) {
 // 4 bf16 of an accumulator tile to columns d0 .. d0 + 3 of a row (8-B store)
 DLLM_DEVICE void st4(uint16_t* p, f32x4 v) { Elem<uint16_t>::store4(p, v); }
 
+// Waves per SIMD each instantiation is held to (the second __launch_bounds__ argument): what its register count gave
+// before the segment hooks, so that the runtime flags added since cannot cost the unsegmented calls their occupancy.
+constexpr int occ_fwd(int DP) { return DP == 32 ? 5 : DP == 64 ? 4 : 3; }
+constexpr int occ_dq(int DP, bool DROP) {
+  return DP == 32 ? 4 : DP == 64 ? (DROP ? 3 : 4) : DP == 96 ? 3 : (DROP ? 3 : 2);
+}
+constexpr int occ_dkdv(int DP) { return DP == 32 ? 3 : 2; }
+
 // ================================================================================================ forward
 template <int DP, bool DROP>
-__global__ __launch_bounds__(NT) void attn_hd_fwd_kernel(AttnHdParams P) {
+__global__ __launch_bounds__(NT, occ_fwd(DP)) void attn_hd_fwd_kernel(AttnHdParams P) {
   constexpr int KS = DP / 32, DT = DP / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[Img<DP>::SIZE];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[Img<DP>::SIZE];
   __shared__ float Ls[2 * BKY];
-  __shared__ uint8_t Mk[BKY];  // 1: key valid (in range, not padding)
+  __shared__ __attribute__((aligned(16))) uint8_t Mk[BKY];  // 1: key valid (in range, not padding)
+  __shared__ __attribute__((aligned(16))) int Sg[BKY];  // the keys' segment ids (with segments)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
   const int bh = blockIdx.y, b = bh / P.H, h = bh % P.H;
   const int q0 = blockIdx.x * BQ;
   const int row = q0 + 16 * w + c;
   const int rowc = min(row, P.Sq - 1);
+  const int qsg = P.q_seg ? seg_at(P.q_seg, b, P.Sq, row) : 0;
   bf16x8v qf[KS];
   load_row_frags<DP>(P.q + (long)b * P.q_sb + (long)rowc * P.q_ss + (long)h * P.q_sh, g, P.D, qf);
   const uint32_t rh = DROP ? mix32(eff_seed(P.seed), (uint32_t)((long)bh * P.Sq + rowc)) : 0u;
@@ -139,12 +155,17 @@ __global__ __launch_bounds__(NT) void attn_hd_fwd_kernel(AttnHdParams P) {
   int kstart = 0;
   band_range(P, q0, kstart, kend);
   for (int k0 = kstart; k0 < kend; k0 += BKY) {
+    if (seg_apart(P, b, q0, k0)) continue;
     __syncthreads();  // the previous block's LDS reads are done
     stage<DP>(kb, P.k_ss, k0, P.Sk, P.D, Ks, tid);
     stage<DP>(vb, P.v_ss, k0, P.Sk, P.D, Vs, tid);
     stage_bias(P, h, q0, k0, Ls, tid, LOG2E);
-    if (tid < BKY) Mk[tid] = key_ok(P, b, k0 + tid);
+    if (tid < BKY) {
+      Mk[tid] = key_ok(P, b, k0 + tid);
+      if (P.q_seg) Sg[tid] = seg_at(P.k_seg, b, P.Sk, k0 + tid);
+    }
     __syncthreads();
+    const uint32_t vis = key_bits(P, Mk, Sg, qsg, g);  // key valid and of the row's segment
     f32x4 st[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -161,7 +182,7 @@ __global__ __launch_bounds__(NT) void attn_hd_fwd_kernel(AttnHdParams P) {
         const int key = k0 + 16 * t + 4 * g + i;
         float x = st[t][i] * scale2;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        if (!Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off) || off_band(P, row, key)) x = -INFINITY;
+        if (hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key)) x = -INFINITY;
         st[t][i] = x;
         mx = fmaxf(mx, x);
       }
@@ -227,18 +248,20 @@ __global__ __launch_bounds__(NT) void attn_hd_delta_kernel(AttnHdParams P) {
 }
 
 template <int DP, bool DROP>
-__global__ __launch_bounds__(NT) void attn_hd_dq_kernel(AttnHdParams P) {
+__global__ __launch_bounds__(NT, occ_dq(DP, DROP)) void attn_hd_dq_kernel(AttnHdParams P) {
   constexpr int KS = DP / 32, DT = DP / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[Img<DP>::SIZE];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[Img<DP>::SIZE];
   __shared__ float Ls[2 * BKY];
   __shared__ float Ds[BQ * (BKY + 1)];  // dS tile of the block, row stride 65: a diagonal walk is bank-conflict free
-  __shared__ uint8_t Mk[BKY];
+  __shared__ __attribute__((aligned(16))) uint8_t Mk[BKY];
+  __shared__ __attribute__((aligned(16))) int Sg[BKY];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
   const int bh = blockIdx.y, b = bh / P.H, h = bh % P.H;
   const int q0 = blockIdx.x * BQ;
   const int row = q0 + 16 * w + c;
   const int rowc = min(row, P.Sq - 1);
+  const int qsg = P.q_seg ? seg_at(P.q_seg, b, P.Sq, row) : 0;
   const bool row_ok = row < P.Sq;
   bf16x8v qf[KS], dof[KS];
   load_row_frags<DP>(P.q + (long)b * P.q_sb + (long)rowc * P.q_ss + (long)h * P.q_sh, g, P.D, qf);
@@ -259,12 +282,17 @@ __global__ __launch_bounds__(NT) void attn_hd_dq_kernel(AttnHdParams P) {
   int kstart = 0;
   band_range(P, q0, kstart, kend);
   for (int k0 = kstart; k0 < kend; k0 += BKY) {
+    if (seg_apart(P, b, q0, k0)) continue;
     __syncthreads();
     stage<DP>(kb, P.k_ss, k0, P.Sk, P.D, Ks, tid);
     stage<DP>(vb, P.v_ss, k0, P.Sk, P.D, Vs, tid);
     stage_bias(P, h, q0, k0, Ls, tid, LOG2E);
-    if (tid < BKY) Mk[tid] = key_ok(P, b, k0 + tid);
+    if (tid < BKY) {
+      Mk[tid] = key_ok(P, b, k0 + tid);
+      if (P.q_seg) Sg[tid] = seg_at(P.k_seg, b, P.Sk, k0 + tid);
+    }
     __syncthreads();
+    const uint32_t vis = key_bits(P, Mk, Sg, qsg, g);  // key valid and of the row's segment
     f32x4 st[4], dpt[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -285,7 +313,7 @@ __global__ __launch_bounds__(NT) void attn_hd_dq_kernel(AttnHdParams P) {
         const int di = key - row - (k0 - q0 - 63);
         float x = st[t][i] * scale2;
         if (P.lut) x += Ls[di];
-        const bool msk = !Mk[16 * t + 4 * g + i] || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
+        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
         const float pr = msk ? 0.f : ex2(x - lse);
         const float dpk = DROP ? (((kb4 >> i) & 1u) ? dpt[t][i] * dscale : 0.f) : dpt[t][i];
         const float ds = pr * (dpk - dlt);
@@ -314,13 +342,14 @@ __global__ __launch_bounds__(NT) void attn_hd_dq_kernel(AttnHdParams P) {
 }
 
 template <int DP, bool DROP>
-__global__ __launch_bounds__(NT) void attn_hd_dkdv_kernel(AttnHdParams P) {
+__global__ __launch_bounds__(NT, occ_dkdv(DP)) void attn_hd_dkdv_kernel(AttnHdParams P) {
   constexpr int KS = DP / 32, DT = DP / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Qs[Img<DP>::SIZE];
   __shared__ __attribute__((aligned(16))) uint16_t Os[Img<DP>::SIZE];  // dO
   __shared__ float Ls[2 * BQ];
   __shared__ float Rl[BQ], Rd[BQ];
   __shared__ uint32_t Rh[BQ];
+  __shared__ __attribute__((aligned(16))) int Rs[BQ];  // the rows' segment ids (with segments)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
   const int bh = blockIdx.y, b = bh / P.H, h = bh % P.H;
   const int k0 = blockIdx.x * BKY;
@@ -333,6 +362,7 @@ __global__ __launch_bounds__(NT) void attn_hd_dkdv_kernel(AttnHdParams P) {
   const float scale2 = P.scale * LOG2E;
   const uint32_t seed = DROP ? eff_seed(P.seed) : 0u;
   const bool kok = key_ok(P, b, key);
+  const int ksg = P.q_seg ? seg_at(P.k_seg, b, P.Sk, key) : 0;
   f32x4 dk[DT], dv[DT];
 #pragma unroll
   for (int i = 0; i < DT; ++i) {
@@ -346,6 +376,7 @@ __global__ __launch_bounds__(NT) void attn_hd_dkdv_kernel(AttnHdParams P) {
   int qend = P.Sq;
   band_range(P, k0, qstart, qend);
   for (int q0 = qstart; q0 < qend; q0 += BQ) {
+    if (seg_apart(P, b, q0, k0)) continue;
     __syncthreads();
     stage<DP>(qb, P.q_ss, q0, P.Sq, P.D, Qs, tid);
     stage<DP>(ob, P.do_ss, q0, P.Sq, P.D, Os, tid);
@@ -356,8 +387,10 @@ __global__ __launch_bounds__(NT) void attn_hd_dkdv_kernel(AttnHdParams P) {
       Rl[tid] = ok ? P.lse[(long)bh * P.Sq + r] : INFINITY;
       Rd[tid] = ok ? P.delta[(long)bh * P.Sq + r] : 0.f;
       if (DROP) Rh[tid] = mix32(seed, (uint32_t)((long)bh * P.Sq + min(r, P.Sq - 1)));
+      if (P.q_seg) Rs[tid] = seg_at(P.q_seg, b, P.Sq, r);
     }
     __syncthreads();
+    const uint32_t vis = kok ? seg_bits(P, Rs, ksg, g) : 0u;  // key valid and of the rows' segments
     f32x4 sc[4], dp[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -378,7 +411,7 @@ __global__ __launch_bounds__(NT) void attn_hd_dkdv_kernel(AttnHdParams P) {
         const int rl = 16 * t + 4 * g + i, row = q0 + rl;
         float x = sc[t][i] * scale2;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        const bool msk = !kok || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
+        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
         const float pr = msk ? 0.f : ex2(x - Rl[rl]);
         const bool kp = DROP ? keep_key(Rh[rl], key, P.thr) : true;
         const float dpk = kp ? dp[t][i] * dscale : 0.f;

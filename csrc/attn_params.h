@@ -16,6 +16,14 @@
 // csrc/attn_hd.hip and csrc/attn_f32.hip skip the 64 x 64 blocks outside the band, so work and traffic are
 // O(S * window); csrc/attn.hip has no window and is never given one.  With a window a row can lack a visible key only
 // through the padding mask.
+// Segments (sequence packing): with q_seg / k_seg given (both or neither) key j is visible to query i iff, besides the
+// above, k_seg[b][j] >= 0 && q_seg[b][i] == k_seg[b][j]; a negative id is padding, so a query row with a negative id is
+// a row without a visible key.  q_blk / k_blk hold, per 64-block, the min and max of its non-negative ids ((INT_MAX, -1)
+// for a block without one): forward and dQ skip the key blocks, dK / dV the query blocks, whose [min, max] does not
+// overlap their own — never loaded, so work and traffic follow the sum of the squared segment lengths.  The block test
+// is correct for any ids and exact for non-decreasing ones (what data/packing.py emits).  Segments compose with kpm,
+// causal, the bias and dropout (the keep hash still indexes (b, h, row, key)), not with a window (the binding
+// rejects it); csrc/attn.hip has no segments and is never given any.
 // Bias: lut[h][(j - i) + Sq - 1] is added to the scaled score.
 // LSE: [B, H, Sq] fp32, forward writes and backward reads; +inf marks a row without a visible key (its output row is
 // 0).  The bf16 families store it in log2 units (scores are scaled by log2(e), softmax by exp2), fp32 in natural-log
@@ -43,6 +51,10 @@ struct AttnParamsT {
                        // (csrc/attn.hip: always given with lut)
   const uint8_t* kpm;  // [B, Sk] 1 = attend; nullptr: none
   const float* lut;    // [H, Sq + Sk - 1]; nullptr: none
+  const int* q_seg;    // [B, Sq] segment ids, < 0: padding; nullptr: no segments (csrc/attn_hd.hip, csrc/attn_f32.hip only)
+  const int* k_seg;    // [B, Sk]; given with q_seg
+  const int* q_blk;    // [B, ceil(Sq / 64), 2] (min, max) of the ids >= 0 of each 64-block of q_seg; given with q_seg
+  const int* k_blk;    // [B, ceil(Sk / 64), 2]
   long q_sb, q_ss, q_sh;
   long k_sb, k_ss, k_sh;
   long v_sb, v_ss, v_sh;

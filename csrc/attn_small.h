@@ -64,6 +64,50 @@ DLLM_DEVICE void band_range(const Params& P, int x0, int& lo, int& hi) {
   }
 }
 
+// Segments (attn_params.h q_seg / k_seg, nullptr: none).  Id of position x of a [B, S] id tensor; padding (-1) past S
+DLLM_DEVICE int seg_at(const int* seg, int b, int S, int x) { return x < S ? seg[(long)b * S + x] : -1; }
+// Visibility of the lane's 16 pairs of a block as one word: bit 4 t + i <-> the partner at 16 t + 4 g + i.  One
+// register through the block, and 4 (+ 4) 16-B / 4-B LDS reads instead of one per pair.
+// seg_bits: against the segment `own` of the lane's row (forward, dQ: `ids` = the block's key ids) or key (dK / dV:
+// `ids` = the block's row ids), staged in LDS (16-B aligned): set <-> both ids are equal and not padding.  All ones
+// without segments.
+template <class Params>
+DLLM_DEVICE uint32_t seg_bits(const Params& P, const int* ids, int own, int g) {
+  uint32_t m = 0xFFFFu;
+  if (P.q_seg != nullptr) {
+    m = 0u;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const i32x4 v = *reinterpret_cast<const i32x4*>(ids + 16 * t + 4 * g);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) m |= (v[i] >= 0 && v[i] == own ? 1u : 0u) << (4 * t + i);
+    }
+  }
+  return m;
+}
+// key_bits: seg_bits and the staged key validity bytes `mk` (0 / 1 per key of the block, 4-B aligned) of forward / dQ
+template <class Params>
+DLLM_DEVICE uint32_t key_bits(const Params& P, const uint8_t* mk, const int* ids, int own, int g) {
+  uint32_t m = 0u;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(mk + 16 * t + 4 * g);
+    m |= ((w & 1u) | ((w >> 7) & 2u) | ((w >> 14) & 4u) | ((w >> 21) & 8u)) << (4 * t);
+  }
+  return m & seg_bits(P, ids, own, g);
+}
+// element predicate: the pair at (t, i) is hidden
+DLLM_DEVICE bool hidden(uint32_t bits, int t, int i) { return ((bits >> (4 * t + i)) & 1u) == 0u; }
+// no query of the 64-block at q0 shares a segment with a key of the 64-block at k0 (by the blocks' (min, max) ids):
+// the block walks skip such a pair without loading it.  Uniform over the workgroup.
+template <class Params>
+DLLM_DEVICE bool seg_apart(const Params& P, int b, int q0, int k0) {
+  if (P.q_seg == nullptr) return false;
+  const int* qb = P.q_blk + 2 * ((long)b * ((P.Sq + 63) / 64) + q0 / 64);
+  const int* kb = P.k_blk + 2 * ((long)b * ((P.Sk + 63) / 64) + k0 / 64);
+  return qb[0] > kb[1] || kb[0] > qb[1];
+}
+
 // bias window of the (q0, k0) block, times `pre` (log2(e) where scores are in log2 units, 1.f where not): bias of
 // (key, row) at Ls[key - row - (k0 - q0 - 63)]
 template <class Params>

@@ -422,6 +422,7 @@ void fill_common(P& p, const AttnFamily<P>& f, int64_t D, const Tensor& q, const
   p.causal = causal ? 1 : 0;
   p.causal_off = Sk - Sq;
   p.window = -1;  // set_window: csrc/attn_f32.hip and csrc/attn_hd.hip only
+  p.q_seg = p.k_seg = p.q_blk = p.k_blk = nullptr;  // set_segments: the same two families only
   p.p_drop = (float)drop;
   p.seed = (uint32_t)seed;
   p.thr = drop > 0.0 ? (uint32_t)std::min(65535.0, drop * 65536.0) : 0u;  // ops/rng.py threshold16
@@ -503,13 +504,43 @@ void set_window(P& p, int64_t window) {
   p.window = (int)std::min<int64_t>(window, INT_MAX);
 }
 
+// the segments of csrc/attn_params.h: ids [B, Sq] / [B, Sk] and their per-64-block (min, max) tables, all four or none
+template <class P>
+void set_segments(P& p, const optional<Tensor>& q_seg, const optional<Tensor>& k_seg, const optional<Tensor>& q_blk,
+                  const optional<Tensor>& k_blk) {
+  auto has = [](const optional<Tensor>& t) { return t.has_value() && t->defined(); };
+  const int n = has(q_seg) + has(k_seg) + has(q_blk) + has(k_blk);
+  if (n == 0) return;
+  TORCH_CHECK(n == 4, "attention: q_seg, k_seg, q_blk and k_blk are given together or not at all");
+  TORCH_CHECK(p.window < 0, "attention: segments with a window are unsupported");
+  auto check = [&](const Tensor& t, const char* name, int64_t S, bool blk) {
+    const int64_t n1 = blk ? (S + 63) / 64 : S;
+    check_gpu(t, name);
+    TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32");
+    TORCH_CHECK(t.dim() == (blk ? 3 : 2) && t.size(0) == p.B && t.size(1) == n1 && (!blk || t.size(2) == 2), name,
+                ": expected [", p.B, ", ", n1, blk ? ", 2" : "", "], got ", t.sizes());
+    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  };
+  check(*q_seg, "q_seg", p.Sq, false);
+  check(*k_seg, "k_seg", p.Sk, false);
+  check(*q_blk, "q_blk", p.Sq, true);
+  check(*k_blk, "k_blk", p.Sk, true);
+  p.q_seg = q_seg->data_ptr<int>();
+  p.k_seg = k_seg->data_ptr<int>();
+  p.q_blk = q_blk->data_ptr<int>();
+  p.k_blk = k_blk->data_ptr<int>();
+}
+
 template <class P>
 std::vector<Tensor> attn_small_fwd(const AttnFamily<P>& f, int64_t D, const Tensor& q, const Tensor& k,
                                    const Tensor& v, const optional<Tensor>& kpm, const optional<Tensor>& lut,
-                                   double scale, bool causal, double p, int64_t seed, int64_t window) {
+                                   double scale, bool causal, double p, int64_t seed, int64_t window,
+                                   const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
+                                   const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
   P prm{};
   fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
   set_window(prm, window);
+  set_segments(prm, q_seg, k_seg, q_blk, k_blk);
   check_limits_small(prm);
   auto out = fill_fwd(prm, q);
   check_rc(f.fwd(&prm, stream()), f.fwd_name);
@@ -521,10 +552,13 @@ std::vector<Tensor> attn_small_bwd(const AttnFamily<P>& f, int64_t D, const Tens
                                    const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& lse,
                                    const optional<Tensor>& kpm, const optional<Tensor>& lut, double scale, bool causal,
                                    double p, int64_t seed, bool need_dlut, const optional<Tensor>& dq_out,
-                                   const optional<Tensor>& dk_out, const optional<Tensor>& dv_out, int64_t window) {
+                                   const optional<Tensor>& dk_out, const optional<Tensor>& dv_out, int64_t window,
+                                   const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
+                                   const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
   P prm{};
   fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
   set_window(prm, window);
+  set_segments(prm, q_seg, k_seg, q_blk, k_blk);
   check_limits_small(prm);
   auto r = fill_bwd(prm, f, q, o, dout, lse, dq_out, dk_out, dv_out, need_dlut);
   check_rc(f.bwd(&prm, stream()), f.bwd_name);
@@ -533,17 +567,22 @@ std::vector<Tensor> attn_small_bwd(const AttnFamily<P>& f, int64_t D, const Tens
 
 std::vector<Tensor> attn_f32_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
                                  const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
-                                 int64_t window) {
-  return attn_small_fwd(kAttnF32, 64, q, k, v, kpm, lut, scale, causal, p, seed, window);
+                                 int64_t window,
+                                 const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
+                                 const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
+  return attn_small_fwd(kAttnF32, 64, q, k, v, kpm, lut, scale, causal, p, seed, window, q_seg, k_seg, q_blk,
+                        k_blk);
 }
 
 std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
                                  const Tensor& o, const Tensor& lse, const optional<Tensor>& kpm,
                                  const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
                                  bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
-                                 const optional<Tensor>& dv_out, int64_t window) {
+                                 const optional<Tensor>& dv_out, int64_t window,
+                                 const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
+                                 const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
   return attn_small_bwd(kAttnF32, 64, dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed, need_dlut, dq_out,
-                        dk_out, dv_out, window);
+                        dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk);
 }
 
 // the head dim of an attn_hd call: what csrc/attn_hd.hip is instantiated for (padded to 32, 16-B rows)
@@ -556,17 +595,22 @@ int64_t attn_hd_dim(const Tensor& q, const Tensor& k) {
 
 std::vector<Tensor> attn_hd_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
                                 const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
-                                int64_t window) {
-  return attn_small_fwd(kAttnHd, attn_hd_dim(q, k), q, k, v, kpm, lut, scale, causal, p, seed, window);
+                                int64_t window,
+                                const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
+                                const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
+  return attn_small_fwd(kAttnHd, attn_hd_dim(q, k), q, k, v, kpm, lut, scale, causal, p, seed, window, q_seg, k_seg,
+                        q_blk, k_blk);
 }
 
 std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
                                 const Tensor& o, const Tensor& lse, const optional<Tensor>& kpm,
                                 const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
                                 bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
-                                const optional<Tensor>& dv_out, int64_t window) {
+                                const optional<Tensor>& dv_out, int64_t window,
+                                const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
+                                const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
   return attn_small_bwd(kAttnHd, attn_hd_dim(q, k), dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed,
-                        need_dlut, dq_out, dk_out, dv_out, window);
+                        need_dlut, dq_out, dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk);
 }
 
 // ---- csrc/attn.hip: the same helpers, plus its extras (dropout bit planes, saturated-bias ranges, rowrec, column sums)
@@ -1360,17 +1404,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sat_hi") = -1, py::arg("csq") = py::none(), py::arg("csk") = py::none(),
         py::arg("csv") = py::none());
   m.def("attn_f32_fwd", &attn_f32_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
-        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1);
+        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1,
+        py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none());
   m.def("attn_f32_bwd", &attn_f32_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
-        py::arg("dv_out") = py::none(), py::arg("window") = -1);
+        py::arg("dv_out") = py::none(), py::arg("window") = -1, py::arg("q_seg") = py::none(),
+        py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none());
   m.def("attn_hd_fwd", &attn_hd_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
-        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1);
+        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1,
+        py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none());
   m.def("attn_hd_bwd", &attn_hd_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
-        py::arg("dv_out") = py::none(), py::arg("window") = -1);
+        py::arg("dv_out") = py::none(), py::arg("window") = -1, py::arg("q_seg") = py::none(),
+        py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none());
   m.def("gemm_wgrad_segs", &gemm_wgrad_segs, "c (+)= sum_i a_i^T b_i (deferred micro-batch segments, w4)",
         py::arg("a"), py::arg("b"), py::arg("c"), py::arg("beta") = true);
   m.def("gemm_wgrad", &gemm_wgrad, "c (+)= a^T b (token-major bf16 operands)", py::arg("a"), py::arg("b"), py::arg("c"),

@@ -11,6 +11,7 @@ import argparse
 import os
 
 from .data.dataset import convert_examples_to_features, load_samsum, synthetic_samsum_records
+from .data.packing import pack_features
 from .data.tokenization import load_tokenizer
 from .models.config import resolve_config
 from .ops import routing
@@ -38,6 +39,11 @@ def base_parser(description: str, defaults: dict | None = None) -> argparse.Argu
     g.add_argument("--max-source-length", type=int, default=1024)
     g.add_argument("--max-target-length", type=int, default=128)
     g.add_argument("--ignore-pad-labels", action="store_true", help="mask pad tokens out of the loss")
+    g.add_argument("--pack-sequences", action="store_true",
+                   help="pack several training examples into each max-source-length x max-target-length row, with "
+                        "attention confined to each example (segment-masked kernels); steps and schedules then count "
+                        "rows.  Implies that pad labels are not trained on (as --ignore-pad-labels); evaluation stays "
+                        "unpacked; not for LongT5 or --context-parallel")
     g.add_argument("--precision", choices=["bf16", "fp32"], default=None, help="default: bf16 on GPU, fp32 on CPU")
     g.add_argument("--grad-accum", type=int, default=None)
     g.add_argument("--coalesce-grad-accum", type=str, default="auto",
@@ -116,6 +122,13 @@ def build_data(args, cfg):
                          [r["summary"] for r in recs["train"]])
     tr = convert_examples_to_features(recs["train"], tok, args.max_source_length, args.max_target_length,
                                       ignore_pad_labels=args.ignore_pad_labels)
+    if getattr(args, "pack_sequences", False):
+        if cfg.local_encoder:
+            raise NotImplementedError("--pack-sequences is not implemented for LongT5 (windowed attention takes no "
+                                      "segments)")
+        if getattr(args, "context_parallel", 1) > 1:
+            raise NotImplementedError("--pack-sequences is not implemented under --context-parallel")
+        tr = pack_features(tr, cfg, args.max_source_length, args.max_target_length, seed=args.seed)
     ev_recs = recs["validation"][: args.max_eval_samples] if args.max_eval_samples else recs["validation"]
     ev = convert_examples_to_features(ev_recs, tok, args.max_source_length, args.max_target_length,
                                       ignore_pad_labels=args.ignore_pad_labels)

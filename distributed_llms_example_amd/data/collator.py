@@ -5,6 +5,9 @@
 * ``decoder_input_ids = model.prepare_decoder_input_ids_from_labels(labels)`` (shift right with the
   decoder start token, -100 → pad; modeling_t5.py:618-637, modeling_bart.py:58-71).
 
+Packed rows (data/packing.py: features that carry ``segment_ids``) have one fixed shape and their decoder inputs were
+built per segment by the packer, so they are stacked key by key as they are.
+
 Returns int64 CPU tensors; ``pin_memory`` lets the device copy run async (non_blocking).
 """
 from __future__ import annotations
@@ -40,6 +43,12 @@ class DataCollatorForSeq2Seq:
         return torch.from_numpy(out)
 
     def __call__(self, features):
+        if "segment_ids" in features[0]:  # packed rows: fixed shape, nothing to pad or shift
+            batch = {k: torch.from_numpy(np.stack([np.asarray(f[k]) for f in features]).astype(np.int64))
+                     for k in features[0]}
+            if self.pin_memory and torch.cuda.is_available():
+                batch = {k: v.pin_memory() for k, v in batch.items()}
+            return batch
         ids = self._pad([np.asarray(f["input_ids"]) for f in features], self.pad_token_id)
         if "attention_mask" in features[0]:
             am = self._pad([np.asarray(f["attention_mask"]) for f in features], 0)

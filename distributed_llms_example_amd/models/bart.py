@@ -16,6 +16,12 @@ and the NEXT sub-layer's LayerNorm are one kernel returning both (as T5's RMSNor
 features, cos in the second) or padding-aware with offset 2 (M2M100 / NLLB); SiLU FFN (Marian's ``swish``); no
 ``final_logits_bias`` (M2M100); learned positions without the offset 2 (Blenderbot); mBART's and PLBart's decoder
 input starts from the label's last non-pad token (the language id).
+
+Sequence packing (data/packing.py): ``forward(segment_ids=, decoder_segment_ids=, position_ids=,
+decoder_position_ids=)`` runs rows that hold several examples.  Attention is confined to one example by the
+segment-masked kernels (ops/attention.py) — (seg, seg) in the encoder, (dseg, dseg) with causal in the decoder, (dseg,
+seg) across — and every position kind reads the row of its table at ``position_ids``, the index within the example,
+in place of the running index.
 """
 from __future__ import annotations
 
@@ -58,7 +64,7 @@ class BartAttention(nn.Module):
         B, S, _ = kv_in.shape
         return self.kv_proj(kv_in).view(B, S, 2, self.n_heads, self.head_dim)
 
-    def forward(self, x, kv_in=None, mask=None, causal=False, p=0.0, cache=None, kv=None, residual=False):
+    def forward(self, x, kv_in=None, mask=None, causal=False, p=0.0, cache=None, kv=None, residual=False, seg=None):
         """Attention block output; with ``residual`` also ``x`` for the post-LN residual, its gradient accumulated by
         the input projection's dgrad GEMM (ops/linear.py linear_res)."""
         B, S, _ = x.shape
@@ -66,6 +72,10 @@ class BartAttention(nn.Module):
         H, D = self.n_heads, self.head_dim
         seed = default_rng().next_seed() if p > 0 else 0
         kw = dict(scale=self.scaling, causal=causal, key_padding_mask=mask, dropout_p=p, seed=seed)
+        if seg is not None:  # packed rows: (query, key) ops/attention.py Segments
+            if cache is not None:
+                raise NotImplementedError("packed inputs (segment ids) are not implemented with a generation cache")
+            kw["q_segments"], kw["k_segments"] = seg
         if self.cross:
             if residual:
                 q, res = linear_res(x, self.q_proj)
@@ -106,7 +116,7 @@ class BartLayer(nn.Module):
         self.final_layer_norm = nn.LayerNorm(d)
         self.cfg = cfg
 
-    def forward(self, h, mask=None, enc_out=None, enc_mask=None, cache=None, cross_kv=None):
+    def forward(self, h, mask=None, enc_out=None, enc_mask=None, cache=None, cross_kv=None, seg=None, cross_seg=None):
         cfg = self.cfg
         tr = self.training
         p = cfg.dropout_rate if tr else 0.0
@@ -117,12 +127,13 @@ class BartLayer(nn.Module):
         # post-LN blocks: each block's input is both the sublayer input and the residual; the sublayers hand the
         # residual back from their input projection so its gradient is summed inside that projection's dgrad GEMM
         a, h = self.self_attn(h, mask=None if self.is_decoder else mask, causal=self.is_decoder, p=pa, cache=cache,
-                              residual=True)
+                              residual=True, seg=seg)
         xb = _NORM_BIAS_COLSUM  # out_proj / fc2 bias gradients summed by the norm backward kernel (ops/norms.py)
         h = norms.add_dropout_layer_norm(h, a, self.self_attn_layer_norm.weight, self.self_attn_layer_norm.bias, eps,
                                          p, rng.next_seed() if p > 0 else 0, xb)
         if self.is_decoder:
-            c, h = self.encoder_attn(h, kv_in=enc_out, mask=enc_mask, p=pa, kv=cross_kv, residual=True)
+            c, h = self.encoder_attn(h, kv_in=enc_out, mask=enc_mask, p=pa, kv=cross_kv, residual=True,
+                                     seg=cross_seg)
             h = norms.add_dropout_layer_norm(h, c, self.encoder_attn_layer_norm.weight,
                                              self.encoder_attn_layer_norm.bias, eps, p,
                                              rng.next_seed() if p > 0 else 0, xb)
@@ -130,7 +141,8 @@ class BartLayer(nn.Module):
         return norms.add_dropout_layer_norm(h, f, self.final_layer_norm.weight, self.final_layer_norm.bias, eps, p,
                                             rng.next_seed() if p > 0 else 0, xb)
 
-    def forward_pre(self, normed, h, next_norm, mask=None, enc_out=None, enc_mask=None, cache=None, cross_kv=None):
+    def forward_pre(self, normed, h, next_norm, mask=None, enc_out=None, enc_mask=None, cache=None, cross_kv=None,
+                    seg=None, cross_seg=None):
         """Pre-LN layer (mBART / Pegasus) on (LN_self_attn(h), h) -> (next_norm(h'), h'): every residual update is
         fused with the LayerNorm that follows it (the next sub-layer's, or ``next_norm``: the next layer's first
         LayerNorm or the stack's final one)."""
@@ -142,12 +154,13 @@ class BartLayer(nn.Module):
         eps = cfg.layer_norm_epsilon
         rng = default_rng()
         xb = _NORM_BIAS_COLSUM
-        a = self.self_attn(normed, mask=None if self.is_decoder else mask, causal=self.is_decoder, p=pa, cache=cache)
+        a = self.self_attn(normed, mask=None if self.is_decoder else mask, causal=self.is_decoder, p=pa, cache=cache,
+                           seg=seg)
         if self.is_decoder:
             normed, h = norms.add_dropout_layer_norm_pre(h, a, self.encoder_attn_layer_norm.weight,
                                                          self.encoder_attn_layer_norm.bias, eps, p,
                                                          rng.next_seed() if p > 0 else 0, xb)
-            a = self.encoder_attn(normed, kv_in=enc_out, mask=enc_mask, p=pa, kv=cross_kv)
+            a = self.encoder_attn(normed, kv_in=enc_out, mask=enc_mask, p=pa, kv=cross_kv, seg=cross_seg)
         normed, h = norms.add_dropout_layer_norm_pre(h, a, self.final_layer_norm.weight, self.final_layer_norm.bias,
                                                      eps, p, rng.next_seed() if p > 0 else 0, xb)
         f = ffn(normed, self.fc1, self.fc2, cfg.act, pact, rng.next_seed() if pact > 0 else 0)
@@ -184,8 +197,10 @@ class M2M100Positions(nn.Module):
         self.pad = pad
         self.register_buffer("weight", w, persistent=False)
 
-    def positions(self, input_ids, past: int):
+    def positions(self, input_ids, past: int, position_ids=None):
         keep = input_ids.ne(self.pad).long()
+        if position_ids is not None:  # packed rows: the index within the example in place of the running count
+            return (position_ids + 1) * keep + self.pad
         return (torch.cumsum(keep, dim=1) + past) * keep + self.pad
 
 
@@ -240,16 +255,22 @@ class BartStack(nn.Module):
         return stacked_linear(enc_out, self.cross_kv_linears(), (B, S, 2, H, self.cfg.d_model // H))
 
     def forward(self, input_ids, attention_mask=None, enc_out=None, enc_mask=None, caches=None, q_offset=0,
-                cross_kv=None):
+                cross_kv=None, seg=None, cross_seg=None, position_ids=None):
         cfg = self.cfg
         p = cfg.dropout_rate if self.training else 0.0
         B, S = input_ids.shape
+        if (seg is not None or position_ids is not None) and caches is not None:
+            raise NotImplementedError("packed inputs (segment / position ids) are not implemented with a generation "
+                                      "cache")
         x = embedding(input_ids, self._embed[0].weight, padding_idx=cfg.pad_token_id)
         if self.embed_scale != 1.0:
             x = x * self.embed_scale
         pw = self.embed_positions.weight
         if self._pos_offset is None:  # padding-aware positions, one row per sequence
-            x = x + pw[self.embed_positions.positions(input_ids, q_offset)].to(x.dtype)
+            x = x + pw[self.embed_positions.positions(input_ids, q_offset, position_ids)].to(x.dtype)
+        elif position_ids is not None:  # packed rows: one table row per token, by its index within its example
+            pos = position_ids + self._pos_offset
+            x = x + (embedding(pos, pw) if pw.requires_grad else pw[pos].to(x.dtype))
         else:
             pos = torch.arange(q_offset, q_offset + S, device=input_ids.device) + self._pos_offset
             x = x + (embedding(pos, pw) if pw.requires_grad else pw[pos].to(x.dtype)).unsqueeze(0)
@@ -260,19 +281,20 @@ class BartStack(nn.Module):
             cross_kv = self.project_cross_kv(enc_out)
         seed = default_rng().next_seed() if p > 0 else 0
         if cfg.normalize_before:
-            return self._forward_pre(x, p, seed, attention_mask, enc_out, enc_mask, caches, cross_kv)
+            return self._forward_pre(x, p, seed, attention_mask, enc_out, enc_mask, caches, cross_kv, seg, cross_seg)
         h = activations.dropout(x, p, seed)
         for i, layer in enumerate(self.layers):
             cache = caches[i] if caches is not None else None
             ckv = cross_kv[i] if cross_kv is not None else None
 
             def run(h, layer=layer, cache=cache, ckv=ckv):
-                return layer(h, mask=attention_mask, enc_out=enc_out, enc_mask=enc_mask, cache=cache, cross_kv=ckv)
+                return layer(h, mask=attention_mask, enc_out=enc_out, enc_mask=enc_mask, cache=cache, cross_kv=ckv,
+                             seg=seg, cross_seg=cross_seg)
 
             h = run_block(run, h, checkpoint=cfg.gradient_checkpointing and self.training and caches is None)
         return h
 
-    def _forward_pre(self, x, p, seed, attention_mask, enc_out, enc_mask, caches, cross_kv):
+    def _forward_pre(self, x, p, seed, attention_mask, enc_out, enc_mask, caches, cross_kv, seg=None, cross_seg=None):
         """Pre-LN stack: (LN_0(h), h) with h = dropout(embeddings), layer by layer, ending in (layer_norm(h), h)."""
         cfg = self.cfg
         layers = list(self.layers)
@@ -285,7 +307,7 @@ class BartStack(nn.Module):
 
             def run(normed, h, layer=layer, nxt=nxt, cache=cache, ckv=ckv):
                 return layer.forward_pre(normed, h, nxt, mask=attention_mask, enc_out=enc_out, enc_mask=enc_mask,
-                                         cache=cache, cross_kv=ckv)
+                                         cache=cache, cross_kv=ckv, seg=seg, cross_seg=cross_seg)
 
             normed, h = run_block(run, normed, h, checkpoint=cfg.gradient_checkpointing and self.training and
                                   caches is None)
@@ -353,12 +375,14 @@ class BartForConditionalGeneration(nn.Module):
 
     prepare_decoder_input_ids_from_labels = shift_right
 
-    def encode(self, input_ids, attention_mask=None):
-        return self.model.encoder(input_ids, attention_mask=attention_mask)
+    def encode(self, input_ids, attention_mask=None, seg=None, position_ids=None):
+        return self.model.encoder(input_ids, attention_mask=attention_mask, seg=seg, position_ids=position_ids)
 
-    def decode(self, decoder_input_ids, enc_out, enc_mask=None, caches=None, q_offset=0, cross_kv=None):
+    def decode(self, decoder_input_ids, enc_out, enc_mask=None, caches=None, q_offset=0, cross_kv=None, seg=None,
+               cross_seg=None, position_ids=None):
         return self.model.decoder(decoder_input_ids, enc_out=enc_out, enc_mask=enc_mask, caches=caches,
-                                  q_offset=q_offset, cross_kv=cross_kv)
+                                  q_offset=q_offset, cross_kv=cross_kv, seg=seg, cross_seg=cross_seg,
+                                  position_ids=position_ids)
 
     def output_embedding(self):
         return self.model.shared.weight
@@ -400,11 +424,26 @@ class BartForConditionalGeneration(nn.Module):
                 layer.cfg = self.config
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, labels=None,
-                label_smoothing: float = 0.0, return_logits: bool = False, encoder_outputs=None):
-        enc = encoder_outputs if encoder_outputs is not None else self.encode(input_ids, attention_mask)
-        if decoder_input_ids is None:
-            decoder_input_ids = self.shift_right(labels)
-        dec = self.decode(decoder_input_ids, enc, attention_mask)
+                label_smoothing: float = 0.0, return_logits: bool = False, encoder_outputs=None, segment_ids=None,
+                decoder_segment_ids=None, position_ids=None, decoder_position_ids=None):
+        packed = [segment_ids, decoder_segment_ids, position_ids, decoder_position_ids]
+        if any(t is not None for t in packed):
+            # packed rows (data/packing.py): several examples per row; the block tables are built once per batch
+            if any(t is None for t in packed) or decoder_input_ids is None:
+                raise ValueError("packed inputs need segment_ids, decoder_segment_ids, position_ids, "
+                                 "decoder_position_ids and decoder_input_ids (built per segment by data/packing.py)")
+            es, ds = attn_ops.segments(segment_ids), attn_ops.segments(decoder_segment_ids)
+            if attention_mask is None:
+                attention_mask = segment_ids >= 0
+            enc = encoder_outputs if encoder_outputs is not None else self.encode(
+                input_ids, attention_mask, seg=(es, es), position_ids=position_ids)
+            dec = self.decode(decoder_input_ids, enc, attention_mask, seg=(ds, ds), cross_seg=(ds, es),
+                              position_ids=decoder_position_ids)
+        else:
+            enc = encoder_outputs if encoder_outputs is not None else self.encode(input_ids, attention_mask)
+            if decoder_input_ids is None:
+                decoder_input_ids = self.shift_right(labels)
+            dec = self.decode(decoder_input_ids, enc, attention_mask)
         loss = None
         if labels is not None and not return_logits and wants_lm_head_loss(dec, labels.numel(), self.config.vocab_size):
             # LM head + CE with final_logits_bias, no materialised logits (ops/lm_head.py)

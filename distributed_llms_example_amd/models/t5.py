@@ -16,6 +16,10 @@ reference fine-tunes through ``AutoModelForSeq2SeqLM``), restructured for MI355X
   (ops/attention.py ``window``) in O(S·radius); its sub-layer is registered as ``LocalSelfAttention`` as in HF.  HF's
   blocked formulation equals this band on every non-padded query row; padded rows differ (HF averages over masked
   keys, here they follow the row-without-a-visible-key contract) and reach nothing cross-attention reads;
+* sequence packing (data/packing.py): ``forward(segment_ids=, decoder_segment_ids=)`` confines every attention to the
+  tokens of one example — encoder self-attention by (seg, seg), decoder self-attention by (dseg, dseg) with causal,
+  cross-attention by (dseg, seg) — on the segment-masked kernels (ops/attention.py).  Inside one example ``j - i`` is
+  what it was unpacked, so the bias LUT is unchanged.  Not for LongT5, context parallelism or a generation cache;
 * LM head + cross-entropy: logits in bf16, CE fused (ops/cross_entropy.py), the
   ``d_model**-0.5`` tied-embedding scale (modeling_t5.py:1044-1045) applied to the decoder output.
 """
@@ -76,19 +80,25 @@ class T5Attention(nn.Module):
         B, S, _ = kv_in.shape
         return self.kv(kv_in).view(B, S, 2, self.n_heads, self.d_kv)
 
-    def forward(self, x, kv_in=None, mask=None, lut=None, causal=False, p=0.0, cache=None, kv=None):
+    def forward(self, x, kv_in=None, mask=None, lut=None, causal=False, p=0.0, cache=None, kv=None, seg=None):
         B, S, _ = x.shape
         H, D = self.n_heads, self.d_kv
         seed = default_rng().next_seed() if p > 0 else 0
         kw = dict(scale=1.0, causal=causal, key_padding_mask=mask, bias_lut=lut, dropout_p=p, seed=seed)
         if self.window is not None:
             kw["window"] = self.window
+        if seg is not None:  # packed rows: (query, key) ops/attention.py Segments
+            if self.window is not None or cache is not None or isinstance(lut, _CPBias):
+                raise NotImplementedError("packed inputs (segment ids) are not implemented for LongT5's window, "
+                                          "context parallelism or a generation cache")
+            kw["q_segments"], kw["k_segments"] = seg
         if self.cross:
             q = self.q(x).view(B, S, H, D)
             kv = kv if kv is not None else self.project_kv(kv_in)
             if kv.shape[0] != B:  # beam search: the nb hypotheses of a batch entry share its encoder K/V (read once)
                 q = q.reshape(kv.shape[0], (B // kv.shape[0]) * S, H, D)
-            chunk = long_sequence_chunk(kv.shape[1], cross=True)
+            # segment-masked kernels keep nothing length-bound in LDS: a packed call is never chunked
+            chunk = long_sequence_chunk(kv.shape[1], cross=True) if seg is None else None
             if chunk is not None:  # long encoder output: key-chunked blocks merged by LSE
                 o = chunked_cross_attention(q, kv[:, :, 0], kv[:, :, 1], chunk=chunk, scale=1.0,
                                             key_padding_mask=mask, dropout_p=p, seed=seed)
@@ -208,7 +218,7 @@ class T5Stack(nn.Module):
         return stacked_linear(enc_out, self.cross_kv_linears(), (B, S, 2, self.cfg.num_heads, self.cfg.d_kv))
 
     def forward(self, input_ids, attention_mask=None, enc_out=None, enc_mask=None, caches=None, q_offset=0,
-                cross_kv=None):
+                cross_kv=None, seg=None, cross_seg=None):
         cfg = self.cfg
         p = cfg.dropout_rate if self.training else 0.0
         pa = cfg.attention_dropout if self.training else 0.0
@@ -218,9 +228,12 @@ class T5Stack(nn.Module):
         B, S = input_ids.shape
         k_len = S + q_offset
         cp = getattr(self, "_cp_group", False)
+        if seg is not None and (cp is not False or caches is not None or cfg.local_encoder):
+            raise NotImplementedError("packed inputs (segment ids) are not implemented for LongT5, under context "
+                                      "parallelism or with a generation cache")
         # a windowed encoder is O(S·radius) in one launch on kernels without an LDS-bounded length: never chunked
         chunk = (long_sequence_chunk(S, rows=B * cfg.num_heads)
-                 if not self.is_decoder and caches is None and not cfg.local_encoder else None)
+                 if not self.is_decoder and caches is None and not cfg.local_encoder and seg is None else None)
         blocks = list(self.block)
         # T5 / mT5: layer 0's table serves every layer; UMT5: each layer's own table
         owners = blocks if cfg.per_layer_position_bias else blocks[:1]
@@ -241,7 +254,8 @@ class T5Stack(nn.Module):
             lut = luts[i if len(luts) > 1 else 0]
 
             def run(normed, h, blk=blk, nxt=nxt, ckv=ckv, cache=cache, lut=lut):
-                return self._block(blk, nxt, normed, h, attention_mask, lut, enc_out, enc_mask, ckv, cache, p, pa, eps)
+                return self._block(blk, nxt, normed, h, attention_mask, lut, enc_out, enc_mask, ckv, cache, p, pa, eps,
+                                   seg, cross_seg)
 
             normed, h = run_block(run, normed, h, checkpoint=cfg.gradient_checkpointing and self.training and
                                   caches is None)
@@ -249,18 +263,20 @@ class T5Stack(nn.Module):
         return activations.dropout(normed, p, rng.next_seed() if p > 0 else 0)
 
 
-    def _block(self, blk, next_norm, normed, h, attention_mask, lut, enc_out, enc_mask, ckv, cache, p, pa, eps):
+    def _block(self, blk, next_norm, normed, h, attention_mask, lut, enc_out, enc_mask, ckv, cache, p, pa, eps,
+               seg=None, cross_seg=None):
         """One T5 block on (norm(h), h) -> (next norm(h'), h'): self-attention, [cross-attention], FFN, each
         residual update fused with the following RMSNorm."""
         rng = default_rng()
         subs = list(blk.layer)
         norms_w = [lyr.layer_norm.weight for lyr in subs[1:]] + [next_norm]
         a = blk.self_attention(normed, mask=attention_mask if not self.is_decoder else None, lut=lut,
-                                  causal=self.is_decoder, p=pa, cache=cache)
+                                  causal=self.is_decoder, p=pa, cache=cache, seg=seg)
         normed, h = norms.add_dropout_rms_norm(h, a, norms_w[0], eps, p, rng.next_seed() if p > 0 else 0)
         j = 1
         if self.is_decoder:
-            c = subs[1].EncDecAttention(normed, kv_in=enc_out, mask=enc_mask, lut=None, causal=False, p=pa, kv=ckv)
+            c = subs[1].EncDecAttention(normed, kv_in=enc_out, mask=enc_mask, lut=None, causal=False, p=pa, kv=ckv,
+                                        seg=cross_seg)
             normed, h = norms.add_dropout_rms_norm(h, c, norms_w[1], eps, p, rng.next_seed() if p > 0 else 0)
             j = 2
         f = subs[j].DenseReluDense(normed, p)
@@ -319,12 +335,13 @@ class T5ForConditionalGeneration(nn.Module):
 
     prepare_decoder_input_ids_from_labels = shift_right
 
-    def encode(self, input_ids, attention_mask=None):
-        return self.encoder(input_ids, attention_mask=attention_mask)
+    def encode(self, input_ids, attention_mask=None, seg=None):
+        return self.encoder(input_ids, attention_mask=attention_mask, seg=seg)
 
-    def decode(self, decoder_input_ids, enc_out, enc_mask=None, caches=None, q_offset=0, cross_kv=None):
+    def decode(self, decoder_input_ids, enc_out, enc_mask=None, caches=None, q_offset=0, cross_kv=None, seg=None,
+               cross_seg=None):
         return self.decoder(decoder_input_ids, enc_out=enc_out, enc_mask=enc_mask, caches=caches, q_offset=q_offset,
-                            cross_kv=cross_kv)
+                            cross_kv=cross_kv, seg=seg, cross_seg=cross_seg)
 
     def output_embedding(self):
         return self.shared.weight if self.config.tie_word_embeddings else self.lm_head.weight
@@ -372,8 +389,13 @@ class T5ForConditionalGeneration(nn.Module):
         return self
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, labels=None,
-                label_smoothing: float = 0.0, return_logits: bool = False, encoder_outputs=None):
+                label_smoothing: float = 0.0, return_logits: bool = False, encoder_outputs=None, segment_ids=None,
+                decoder_segment_ids=None, position_ids=None, decoder_position_ids=None):
+        # (position ids of a packed batch: the relative bias needs none, j - i inside an example is what it was)
         cp = getattr(self.encoder, "_cp_group", False)
+        if segment_ids is not None or decoder_segment_ids is not None:
+            return self._forward_packed(input_ids, attention_mask, decoder_input_ids, labels, label_smoothing,
+                                        return_logits, encoder_outputs, segment_ids, decoder_segment_ids)
         if cp is not False and encoder_outputs is None:
             enc, attention_mask = context_parallel_encode(self.encode, input_ids, attention_mask, cp)
         else:
@@ -381,6 +403,31 @@ class T5ForConditionalGeneration(nn.Module):
         if decoder_input_ids is None:
             decoder_input_ids = self.shift_right(labels)
         dec = self.decode(decoder_input_ids, enc, attention_mask)
+        return self._lm_output(dec, enc, labels, label_smoothing, return_logits)
+
+    def _forward_packed(self, input_ids, attention_mask, decoder_input_ids, labels, label_smoothing, return_logits,
+                        encoder_outputs, segment_ids, decoder_segment_ids):
+        """``forward`` on packed rows: several examples per row, told apart by ``segment_ids`` [B, S] and
+        ``decoder_segment_ids`` [B, T] (ids 0, 1, 2, ... in order, -1 on the padded tail; data/packing.py).  The
+        per-64-block tables are built here, once per batch, and shared by every layer."""
+        if segment_ids is None or decoder_segment_ids is None:
+            raise ValueError("packed inputs need both segment_ids and decoder_segment_ids")
+        if getattr(self.encoder, "_cp_group", False) is not False:
+            raise NotImplementedError("packed inputs (segment ids) are not implemented under context parallelism")
+        if self.config.local_encoder:
+            raise NotImplementedError("packed inputs (segment ids) are not implemented for LongT5: the windowed "
+                                      "kernels take no segments")
+        if decoder_input_ids is None:
+            raise ValueError("packed inputs need decoder_input_ids: shifting the labels of a packed row would leak "
+                             "one example's last token into the next (data/packing.py builds them per segment)")
+        es, ds = attn_ops.segments(segment_ids), attn_ops.segments(decoder_segment_ids)
+        if attention_mask is None:
+            attention_mask = segment_ids >= 0
+        enc = encoder_outputs if encoder_outputs is not None else self.encode(input_ids, attention_mask, seg=(es, es))
+        dec = self.decode(decoder_input_ids, enc, attention_mask, seg=(ds, ds), cross_seg=(ds, es))
+        return self._lm_output(dec, enc, labels, label_smoothing, return_logits)
+
+    def _lm_output(self, dec, enc, labels, label_smoothing, return_logits):
         if labels is not None and not return_logits and wants_lm_head_loss(dec, labels.numel(), self.config.vocab_size):
             # LM head + CE without materialised logits: GEMM-epilogue CE or vocabulary chunks (ops/lm_head.py)
             scale = self.config.d_model ** -0.5 if self.config.scale_decoder_outputs else None

@@ -25,6 +25,13 @@ f32-input matrix cores).  All are O(S) memory.  ``_route`` picks one; what none 
 Sliding window (LongT5-local encoder self-attention): ``window=w`` keeps key ``j`` for query ``i`` only when
 ``|j - i| <= w`` (``Sq == Sk``, not causal).  csrc/attn_hd.hip (bf16, head dim 64 included) and csrc/attn_f32.hip skip
 the key blocks outside the band, O(S·w) work; csrc/attn.hip has no window.  The composite masks a full score matrix.
+
+Segments (sequence packing, data/packing.py): ``q_segments`` ``[B, Sq]`` and ``k_segments`` ``[B, Sk]`` integer ids,
+both or neither; key ``j`` is visible to query ``i`` only when ``k_segments[b, j] >= 0`` and the two ids are equal (a
+negative id is padding; a query row with one sees no key: output row 0).  Pass ids (cheap, ``[B, S]``) or, to build the
+per-64-block tables once per batch instead of once per call, a :class:`Segments` from :func:`segments`.
+csrc/attn_hd.hip (bf16, head dim 64 included) and csrc/attn_f32.hip skip the blocks of other segments; csrc/attn.hip has
+no segments.  They compose with causal, the key-padding mask, the bias and dropout, not with ``window``.
 """
 from __future__ import annotations
 
@@ -101,7 +108,48 @@ def saturated_ranges(idx: torch.Tensor) -> tuple[int, int]:
 # --------------------------------------------------------------------------- reference
 
 
-def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None):
+class Segments:
+    """Segment ids of one side of a packed batch as the kernels take them: ``ids`` int32 ``[B, S]`` contiguous and
+    ``blk`` int32 ``[B, ceil(S / 64), 2]``, the (min, max) of the non-negative ids of each 64-block — ``(INT_MAX, -1)``
+    for a block without one (csrc/attn_params.h).  Built once per batch by :func:`segments`."""
+
+    __slots__ = ("ids", "blk")
+
+    def __init__(self, ids: torch.Tensor, blk: torch.Tensor):
+        self.ids, self.blk = ids, blk
+
+
+_INT_MAX = 2**31 - 1
+
+
+def segments(ids) -> "Segments | None":
+    """:class:`Segments` of integer ids ``[B, S]`` (None and a ``Segments`` pass through)."""
+    if ids is None or isinstance(ids, Segments):
+        return ids
+    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"attention: segment ids must be int32 or int64 [B, S], got {ids.dtype} {tuple(ids.shape)}")
+    ids = ids.to(torch.int32).contiguous()
+    B, S = ids.shape
+    x = torch.nn.functional.pad(ids, (0, -S % 64), value=-1).view(B, -1, 64)
+    lo = torch.where(x >= 0, x, torch.full_like(x, _INT_MAX)).amin(-1)
+    hi = x.clamp_min(-1).amax(-1)
+    return Segments(ids, torch.stack((lo, hi), -1).contiguous())
+
+
+def _check_segments(q_seg, k_seg, B, Sq, Sk, window) -> None:
+    """Segments come for both sides or neither, as ids [B, Sq] / [B, Sk], and not with a window."""
+    if q_seg is None and k_seg is None:
+        return
+    if q_seg is None or k_seg is None:
+        raise ValueError("attention: q_segments and k_segments are given together or not at all")
+    if window is not None:
+        raise ValueError("attention: segments with a window are unsupported")
+    for name, sg, S in (("q_segments", q_seg, Sq), ("k_segments", k_seg, Sk)):
+        if tuple(sg.ids.shape) != (B, S):
+            raise ValueError(f"attention: {name} must be [B, S] = [{B}, {S}], got {tuple(sg.ids.shape)}")
+
+
+def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None, q_seg=None, k_seg=None):
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     qf = q.float().permute(0, 2, 1, 3)
@@ -122,7 +170,15 @@ def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None):
         _check_window(window, Sq, Sk, causal)
         dist = torch.arange(Sk, device=q.device)[None, :] - torch.arange(Sq, device=q.device)[:, None]
         s = s.masked_fill(dist.abs() > window, neg)
+    q_seg, k_seg = segments(q_seg), segments(k_seg)
+    _check_segments(q_seg, k_seg, B, Sq, Sk, window)
+    if q_seg is not None:
+        qs, ks = q_seg.ids.to(q.device), k_seg.ids.to(q.device)
+        hid = (ks[:, None, :] < 0) | (qs[:, :, None] != ks[:, None, :])
+        s = s.masked_fill(hid[:, None], neg)
     pr = torch.softmax(s, dim=-1)
+    if q_seg is not None:  # the kernels' contract for a row without a visible key (here: a padding row): output 0
+        pr = pr * (qs >= 0)[:, None, :, None].to(pr.dtype)
     if p > 0.0:
         keep = attention_keep_mask(seed, p, B, H, Sq, Sk, q.device)
         pr = pr * keep.to(pr.dtype) * (1.0 / (1.0 - p))
@@ -151,10 +207,15 @@ def _split(mode, a, b, c):
     return a, b, c
 
 
-def _tuned(q, window=None) -> bool:
-    """csrc/attn.hip serves the call (bf16, head dim 64, no window); else csrc/attn_f32.hip (fp32) or
+def _tuned(q, window=None, seg=None) -> bool:
+    """csrc/attn.hip serves the call (bf16, head dim 64, no window, no segments); else csrc/attn_f32.hip (fp32) or
     csrc/attn_hd.hip (bf16)."""
-    return q.dtype != torch.float32 and q.shape[-1] == 64 and window is None
+    return q.dtype != torch.float32 and q.shape[-1] == 64 and window is None and seg is None
+
+
+def _seg_args(q_seg, k_seg) -> tuple:
+    """The trailing segment arguments of attn_hd_* / attn_f32_* (csrc/bind.cpp): ids and block tables, or nothing."""
+    return () if q_seg is None else (q_seg.ids, k_seg.ids, q_seg.blk, k_seg.blk)
 
 
 class _AttnFn(torch.autograd.Function):
@@ -163,27 +224,28 @@ class _AttnFn(torch.autograd.Function):
     gradient buffer through strided views instead of three zero-padded slice gradients."""
 
     @staticmethod
-    def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed, window=None):
+    def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed, window=None, q_seg=None, k_seg=None):
         C = _ext.native()
         q, k, v = _split(mode, a, b, c)
         args = (q, k, v, kpm, lut, float(scale), bool(causal), float(p), int(seed))
         sat_lo = sat_hi = -1
         dmask = None
-        if _tuned(q, window):
+        if _tuned(q, window, q_seg):
             # saturated bias tiles add a scalar instead of reading the LUT (forward -2 %)
             sat = getattr(lut, "_dllm_sat", None) if lut is not None else None
             sat_lo, sat_hi = sat if sat is not None else (-1, -1)
             o, lse, dmask = C.attn_fwd(*args, sat_lo, sat_hi)
         else:
             o, lse = (C.attn_f32_fwd if q.dtype == torch.float32 else C.attn_hd_fwd)(
-                *args, -1 if window is None else int(window))
+                *args, -1 if window is None else int(window), *_seg_args(q_seg, k_seg))
         ctx.save_for_backward(a, b, c, o, lse, lut, kpm, dmask)
         ctx.cfg = (mode, scale, causal, p, seed, lut is not None and lut.requires_grad, sat_lo, sat_hi, window)
+        ctx.seg = (q_seg, k_seg)  # plain int tensors, no graph: kept as they are
         # packed inputs straight from a biased projection (ops/linear.py marks its output): the backward kernels also
         # sum dQ / dK / dV over tokens for that projection's bias gradient (colsum_record).  csrc/attn.hip only (the
         # partials hard-code H * 64) and bias-LUT-free calls only (its column-sum variants exist for those); everything
         # else takes the separate reduction, as with BIAS_COLSUM = False
-        cs_ok = BIAS_COLSUM and lut is None and _tuned(q, window)
+        cs_ok = BIAS_COLSUM and lut is None and _tuned(q, window, q_seg)
         ctx.cs = (cs_ok and mode != "sep" and _bias_out(a), cs_ok and mode == "q_kv" and _bias_out(b))
         # ops/linear.py stacked_linear: the packed kv is a slice of a multi-layer projection and its
         # gradient has a home in the stacked gradient buffer — write dK/dV there directly
@@ -225,11 +287,11 @@ class _AttnFn(torch.autograd.Function):
                     csk, csv = pkv[:, :HD], pkv[:, HD:]
         args = (do.contiguous(), q, k, v, o, lse, kpm, lut, float(scale), bool(causal), float(p), int(seed),
                 bool(need_dlut), dq, dk, dv)
-        if _tuned(q, window):
+        if _tuned(q, window, ctx.seg[0]):
             rq, rk, rv, dlut = C.attn_bwd(*args, dmask, sat_lo, sat_hi, csq, csk, csv)
         else:
             rq, rk, rv, dlut = (C.attn_f32_bwd if q.dtype == torch.float32 else C.attn_hd_bwd)(
-                *args, -1 if window is None else int(window))
+                *args, -1 if window is None else int(window), *_seg_args(*ctx.seg))
         if part is not None:  # per-block partials, reduced by the consumer into the bias gradient (ops/gemm.py)
             colsum_record(da, part)
         if pq is not None:
@@ -239,7 +301,7 @@ class _AttnFn(torch.autograd.Function):
         if mode == "sep":
             da, db, dc = rq, rk, rv
         streams.pair_join()  # side-stream weight gradients paired with these VALU-bound kernels (ops/streams.py)
-        return None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None, None
+        return None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None, None, None, None
 
 
 # False: the projections' bias gradients from a separate column reduction of dQKV (tests flip the module attribute)
@@ -284,13 +346,13 @@ def _aligned(t) -> bool:
     return t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
 
 
-def _route(t, *rest, window=None):
+def _route(t, *rest, window=None, seg=False):
     """Which kernel family serves a call whose q (or packed qkv) is ``t`` — by ops/routing.py ``attention_route``:
 
     * ``"attn.hip"``: bf16, head dim 64, no ``window`` (csrc/attn.hip, the tuned kernels);
     * ``"attn_hd.hip"``: bf16, any other head dim 32 .. 128 with ``D % 8 == 0`` and 16-byte aligned rows in ``t`` and
       ``rest`` (csrc/attn_hd.hip; blenderbot-400m has 40, t5-3b / t5-11b / nllb-3.3B 128, blenderbot-3B 80; ``attn_hd``
-      = 0 sends them to the composite, A/B), and with a ``window`` head dim 64 too;
+      = 0 sends them to the composite, A/B), and with a ``window`` or segments (``seg``) head dim 64 too;
     * ``"attn_f32.hip"``: fp32 at head dim 64 — the reference's own precision (ref/train-torchrun.py:115-128 sets
       neither bf16 nor fp16; Accelerate's default mixed_precision is 'no') — on the f32-input MFMA (``attn_f32`` = 0
       sends it to the composite, A/B);
@@ -304,44 +366,61 @@ def _route(t, *rest, window=None):
     if not bf16 and t.dtype != torch.float32:
         _warn_composite("this dtype", t)
         return None
-    r = routing.attention_route(D, bf16, window)
+    r = routing.attention_route(D, bf16, window, segments=seg)
     if r == "attn_hd.hip" and not all(_aligned(x) for x in (t,) + rest if x is not None):
         _warn_composite("unaligned rows", t)
         return None
     if r == "composite":
-        served = D == 64 and window is None or bf16 and 32 <= D <= 128 and D % 8 == 0 or not bf16 and D == 64
+        served = (D == 64 and window is None and not seg or bf16 and 32 <= D <= 128 and D % 8 == 0
+                  or not bf16 and D == 64)
         if not served:  # (else: switched off by DLLM_ROUTE)
             _warn_composite("this head dim" if bf16 else "fp32 at this head dim", t)
         return None
     return r
 
 
-def _native(t, *rest, window=None) -> bool:
-    return _route(t, *rest, window=window) is not None
+def _native(t, *rest, window=None, seg=False) -> bool:
+    return _route(t, *rest, window=window, seg=seg) is not None
+
+
+def _on(sg, t):
+    """``sg`` with its tensors on ``t``'s device (a no-op for what :func:`segments` built there)."""
+    if sg is None or sg.ids.device == t.device:
+        return sg
+    return Segments(sg.ids.to(t.device), sg.blk.to(t.device))
 
 
 def attention(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_mask=None, bias_lut=None,
-              dropout_p: float = 0.0, seed: int = 0, window: int | None = None):
+              dropout_p: float = 0.0, seed: int = 0, window: int | None = None, q_segments=None, k_segments=None):
     """Multi-head attention.  q ``[B,Sq,H,D]``, k/v ``[B,Sk,H,D]``; ``key_padding_mask`` bool
     ``[B,Sk]`` (True = attend); ``bias_lut`` from :func:`relative_bias_lut`; ``window``: keys with
-    ``|j - i| > window`` are masked (needs ``Sq == Sk`` and ``causal=False``; None: full attention)."""
+    ``|j - i| > window`` are masked (needs ``Sq == Sk`` and ``causal=False``; None: full attention);
+    ``q_segments`` / ``k_segments``: ids ``[B,Sq]`` / ``[B,Sk]`` or :class:`Segments` (both or neither, not with
+    ``window``): a key is visible only to the queries of its own non-negative id."""
     if window is not None:
         _check_window(window, q.shape[1], k.shape[1], causal)
-    if _native(q, k, v, window=window):
+    qs, ks = segments(q_segments), segments(k_segments)
+    _check_segments(qs, ks, q.shape[0], q.shape[1], k.shape[1], window)
+    if _native(q, k, v, window=window, seg=qs is not None):
         return _AttnFn.apply("sep", q, k, v, bias_lut, _prep_kpm(key_padding_mask), scale, causal, dropout_p, seed,
-                             window)
-    return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed, window)
+                             window, _on(qs, q), _on(ks, q))
+    return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed, window, qs, ks)
 
 
 def attention_qkv(qkv, **kw):
-    """Self-attention on the fused projection output ``qkv`` = [B, S, 3, H, D]."""
+    """Self-attention on the fused projection output ``qkv`` = [B, S, 3, H, D]; ``segments=`` serves both sides."""
+    kw = dict(kw)
+    if "segments" in kw:
+        kw["q_segments"] = kw["k_segments"] = segments(kw.pop("segments"))
     window = kw.get("window")
     if window is not None:
         _check_window(window, qkv.shape[1], qkv.shape[1], kw.get("causal", False))
-    if _native(qkv, window=window):
+    qs, ks = segments(kw.get("q_segments")), segments(kw.get("k_segments"))
+    _check_segments(qs, ks, qkv.shape[0], qkv.shape[1], qkv.shape[1], window)
+    if _native(qkv, window=window, seg=qs is not None):
         return _AttnFn.apply("qkv", qkv, None, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
                              kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
-                             window)
+                             window, _on(qs, qkv), _on(ks, qkv))
     return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], **kw)
 
 
@@ -350,8 +429,10 @@ def attention_q_kv(q, kv, **kw):
     window = kw.get("window")
     if window is not None:
         _check_window(window, q.shape[1], kv.shape[1], kw.get("causal", False))
-    if _native(q, kv, window=window):
+    qs, ks = segments(kw.get("q_segments")), segments(kw.get("k_segments"))
+    _check_segments(qs, ks, q.shape[0], q.shape[1], kv.shape[1], window)
+    if _native(q, kv, window=window, seg=qs is not None):
         return _AttnFn.apply("q_kv", q, kv, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
                              kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
-                             window)
+                             window, _on(qs, q), _on(ks, q))
     return attention(q, kv[:, :, 0], kv[:, :, 1], **kw)

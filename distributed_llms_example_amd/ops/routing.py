@@ -49,6 +49,10 @@ sliding-window attention       bf16 at head dims 32 .. 128 (% 8 == 0), 64 includ
                                Their block walks skip the blocks outside the band
                                (O(S·w)); csrc/attn.hip has no window; anything else: the
                                O(S²) composite, with a one-time warning
+segment-masked attention       as the window: bf16 (head dim 64 included) on                 attn_segments_vs_masked.txt
+(sequence packing)             csrc/attn_hd.hip, fp32 at head dim 64 on csrc/attn_f32.hip;
+                               blocks of other segments are skipped by per-block (min,
+                               max) id tables; csrc/attn.hip has no segments
 long-context attention         query chunks of ``attn_chunk`` rows from ``attn_chunk_min``   (parallel/context.py)
 weight gradients, small        side stream for micro-batches <= ``wgrad_stream_max_tokens``  r4_wgrad_stream_ab.txt
 micro-batches                  (``wgrad_stream`` = auto | 1 | 0)
@@ -161,12 +165,14 @@ def get(key: str):
     return ov[key] if key in ov else DEFAULTS[key]
 
 
-def attention_route(head_dim: int, bf16: bool = True, window: int | None = None) -> str:
+def attention_route(head_dim: int, bf16: bool = True, window: int | None = None, *,
+                    segments: bool = False) -> str:
     """Kernel family of an attention call on the GPU by head dim and dtype (bf16, else fp32): ``"attn.hip"``,
     ``"attn_hd.hip"``, ``"attn_f32.hip"`` or ``"composite"`` — the rule ops/attention.py ``_route`` applies.
     ``window``: the call's sliding window (None: full attention).  csrc/attn.hip has no window, so a windowed bf16
-    call at head dim 64 runs csrc/attn_hd.hip's 64-wide instantiation."""
-    if head_dim == 64 and (window is None or not bf16):
+    call at head dim 64 runs csrc/attn_hd.hip's 64-wide instantiation.  ``segments``: the call carries segment ids
+    (sequence packing); csrc/attn.hip has none either, so the same holds.  The fp32 route is unchanged by both."""
+    if head_dim == 64 and (window is None and not segments or not bf16):
         return "attn.hip" if bf16 else ("attn_f32.hip" if get("attn_f32") else "composite")
     if bf16 and 32 <= head_dim <= 128 and head_dim % 8 == 0 and get("attn_hd"):
         return "attn_hd.hip"

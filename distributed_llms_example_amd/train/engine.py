@@ -12,6 +12,7 @@ import os
 
 import torch
 
+from ..data.packing import PACKED_KEYS
 from ..ops import gemm
 from ..ops import rng as rng_mod
 from ..ops import streams
@@ -133,9 +134,11 @@ class TrainEngine:
 
     def forward(self, batch: dict):
         self.flat.reset_pending()
+        # packed rows (data/packing.py) carry their segment and position ids; other batches none of these keys
+        packed = {k: batch[k] for k in PACKED_KEYS if k in batch}
         return self.model(input_ids=batch["input_ids"], attention_mask=batch.get("attention_mask"),
                           decoder_input_ids=batch.get("decoder_input_ids"), labels=batch["labels"],
-                          label_smoothing=self.label_smoothing)
+                          label_smoothing=self.label_smoothing, **packed)
 
     def backward(self, loss: torch.Tensor, scale: float = 1.0, sync: bool = True):
         ctx = contextlib.nullcontext() if sync else self.no_sync()

@@ -198,7 +198,8 @@ class Trainer:
         with the pad token, masks with 0, labels with -100 — what the collator would have produced for one batch)."""
         if len(group) == 1:
             return group[0]
-        fill = {"labels": -100, "attention_mask": 0, "decoder_attention_mask": 0}
+        fill = {"labels": -100, "attention_mask": 0, "decoder_attention_mask": 0, "segment_ids": -1,
+                "decoder_segment_ids": -1, "position_ids": 0, "decoder_position_ids": 0}
         out, padded = {}, False
         for k in group[0]:
             ts = [g[k] for g in group]
@@ -207,7 +208,9 @@ class Trainer:
                 ts = [torch.nn.functional.pad(t, (0, n - t.shape[1]), value=fill.get(k, pad_id)) for t in ts]
                 padded = True
             out[k] = torch.cat(ts, 0)
-        if padded and "labels" in out:  # shift_right(labels) inside the model rebuilds them for the longer labels
+        # shift_right(labels) inside the model rebuilds them for the longer labels; packed rows (data/packing.py) keep
+        # theirs: built per segment, and a tail padded with the pad token is what the packer writes too
+        if padded and "labels" in out and "segment_ids" not in out:
             out.pop("decoder_input_ids", None)
         return out
 
@@ -404,6 +407,14 @@ class Trainer:
             per_step = args.per_device_train_batch_size * ga * self.dp_world
             dt = t_last - t_warm
             metrics["train_steady_samples_per_second"] = round(per_step * (self.state.global_step - warm_step) / dt, 3)
+        if hasattr(self.train_dataset, "examples_per_row"):
+            # packed rows (data/packing.py): the keys above count rows; examples at the dataset's mean per row
+            epr = self.train_dataset.examples_per_row
+            metrics["train_examples_per_second"] = round(metrics["train_samples_per_second"] * epr, 3)
+            if "train_steady_samples_per_second" in metrics:
+                metrics["train_steady_examples_per_second"] = round(metrics["train_steady_samples_per_second"] * epr, 3)
+            metrics["packing_examples_per_row"] = round(epr, 3)
+            metrics["packing_efficiency"] = round(self.train_dataset.efficiency, 4)
         if self._batch_shape is not None:  # what the throughput was measured on: per-GPU micro-batch, padded lengths
             metrics["batch_shape"] = self._batch_shape
             metrics["hip_graph_replays"] = self.step_runner.replays
