@@ -8,6 +8,9 @@
 // the blocks that intersect the band (attn_small.h band_range) and the element mask gains |key - row| > w (off_band).
 // Segments (AttnParamsT::q_seg / k_seg, sequence packing): as in csrc/attn_hd.hip, blocks of other segments are skipped
 // by their (min, max) id tables (seg_apart) and the element mask gains "same non-negative id" (seg_bits).
+// Global keys (AttnParamsT::k_glob / k_gblk, only with a window): as in csrc/attn_hd.hip, forward and dQ walk the band
+// merged with the listed blocks that hold a global key (BlockWalk), dK / dV every query block from a key block with
+// one.
 //
 // Layout trick (no transposes through LDS for P or dS): the 16x16x4 f32 MFMA's C/D map puts rows 4g .. 4g+3
 // (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction index k = g from
@@ -116,18 +119,20 @@ __global__ __launch_bounds__(NT, 3) void attn_f32_fwd_kernel(AttnF32Params P) {
   if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
   int kstart = 0;
   band_range(P, q0, kstart, kend);
-  for (int k0 = kstart; k0 < kend; k0 += BKY) {
-    if (seg_apart(P, b, q0, k0)) continue;
+  // one 64-key block of the walk.  Expanded twice on purpose, once per loop below, as in csrc/attn_hd.hip: calls
+  // without global keys keep the affine loop they had
+  auto block = [&](int k0) __attribute__((always_inline)) {
     __syncthreads();  // the previous block's LDS reads are done
     stage<true, false>(kb, P.k_ss, k0, P.Sk, Ks, nullptr, tid);
     stage<false, true>(vb, P.v_ss, k0, P.Sk, nullptr, Vt, tid);
     stage_bias(P, h, q0, k0, Ls, tid, 1.f);
     if (tid < BKY) {
-      Mk[tid] = key_ok(P, b, k0 + tid);
+      Mk[tid] = key_byte(P, b, k0 + tid);
       if (P.q_seg) Sg[tid] = seg_at(P.k_seg, b, P.Sk, k0 + tid);
     }
     __syncthreads();
-    const uint32_t vis = key_bits(P, Mk, Sg, qsg, g);  // key valid and of the row's segment
+    // key valid and of the row's segment (low half); key global (high half)
+    const uint32_t vis = key_bits(P, Mk, Sg, qsg, g) | glob_bits(P, Mk, g);
     f32x4 st[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -146,7 +151,8 @@ __global__ __launch_bounds__(NT, 3) void attn_f32_fwd_kernel(AttnF32Params P) {
         const int key = k0 + 16 * t + 4 * g + i;
         float x = st[t][i] * P.scale;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        if (hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key)) x = -INFINITY;
+        if (hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key, vis, t, i))
+          x = -INFINITY;
         st[t][i] = x;
         mx = fmaxf(mx, x);
       }
@@ -182,6 +188,15 @@ __global__ __launch_bounds__(NT, 3) void attn_f32_fwd_kernel(AttnF32Params P) {
         acc[dt] = mma(va.w, st[t][3], acc[dt]);
       }
     }
+  };
+  if (P.k_glob == nullptr) {  // the walk as it was before the global keys: the band (or everything), segment skips
+    for (int k0 = kstart; k0 < kend; k0 += BKY) {
+      if (seg_apart(P, b, q0, k0)) continue;
+      block(k0);
+    }
+  } else {  // the band merged with the listed blocks outside it (no segments with global keys)
+    BlockWalk walk(P, b, kstart, kend);
+    for (int k0 = walk.next(P, -BKY); k0 != BlockWalk::DONE; k0 = walk.next(P, k0)) block(k0);
   }
   if (row < P.Sq) {
     const float inv = l > 0.f ? 1.f / l : 0.f;
@@ -246,6 +261,10 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
   const uint32_t rh = DROP ? mix32(eff_seed(P.seed), (uint32_t)((long)bh * P.Sq + rowc)) : 0u;
   const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
   const bool want_dlut = P.dlut != nullptr && P.lut != nullptr;
+  // the row's dQ address, formed here as in csrc/attn_hd.hip: two vector registers through the walk instead of the
+  // eight scalar ones of the base and strides, which the walk's own scalars would otherwise push out to spills
+  float* dqp = P.dq + (long)b * P.dq_sb + (long)rowc * P.dq_ss + (long)h * P.dq_sh;
+  asm volatile("" : "+v"(dqp));  // formed here, not sunk to the epilogue
   f32x4 acc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -255,18 +274,20 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
   if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
   int kstart = 0;
   band_range(P, q0, kstart, kend);
-  for (int k0 = kstart; k0 < kend; k0 += BKY) {
-    if (seg_apart(P, b, q0, k0)) continue;
+  // one 64-key block of the walk.  Expanded twice on purpose, once per loop below, as in csrc/attn_hd.hip: calls
+  // without global keys keep the affine loop they had
+  auto block = [&](int k0) __attribute__((always_inline)) {
     __syncthreads();
     stage<true, true>(kb, P.k_ss, k0, P.Sk, Ks, Kt, tid);
     stage<true, false>(vb, P.v_ss, k0, P.Sk, Vs, nullptr, tid);
     stage_bias(P, h, q0, k0, Ls, tid, 1.f);
     if (tid < BKY) {
-      Mk[tid] = key_ok(P, b, k0 + tid);
+      Mk[tid] = key_byte(P, b, k0 + tid);
       if (P.q_seg) Sg[tid] = seg_at(P.k_seg, b, P.Sk, k0 + tid);
     }
     __syncthreads();
-    const uint32_t vis = key_bits(P, Mk, Sg, qsg, g);  // key valid and of the row's segment
+    // key valid and of the row's segment (low half); key global (high half)
+    const uint32_t vis = key_bits(P, Mk, Sg, qsg, g) | glob_bits(P, Mk, g);
     f32x4 st[4], dpt[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -290,7 +311,8 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
         const int di = key - row - (k0 - q0 - 63);
         float x = st[t][i] * P.scale;
         if (P.lut) x += Ls[di];
-        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
+        const bool msk =
+            hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key, vis, t, i);
         const float pr = msk ? 0.f : __expf(x - lse);
         const float dpk = DROP ? (((kb4 >> i) & 1u) ? dpt[t][i] * dscale : 0.f) : dpt[t][i];
         const float ds = pr * (dpk - dlt);
@@ -313,9 +335,17 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
       __syncthreads();  // the block's dS tile is complete
       dlut_add_diagonals(P, h, q0, k0, Ds, tid);
     }
+  };
+  if (P.k_glob == nullptr) {  // the walk as it was before the global keys: the band (or everything), segment skips
+    for (int k0 = kstart; k0 < kend; k0 += BKY) {
+      if (seg_apart(P, b, q0, k0)) continue;
+      block(k0);
+    }
+  } else {  // the band merged with the listed blocks outside it (no segments with global keys)
+    BlockWalk walk(P, b, kstart, kend);
+    for (int k0 = walk.next(P, -BKY); k0 != BlockWalk::DONE; k0 = walk.next(P, k0)) block(k0);
   }
   if (row_ok) {
-    float* dqp = P.dq + (long)b * P.dq_sb + (long)row * P.dq_ss + (long)h * P.dq_sh;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(dqp + 16 * dt + 4 * g) = acc[dt] * P.scale;
   }
@@ -363,7 +393,9 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dkdv_kernel(AttnF32Params P) {
   int qstart = 0;
   if (P.causal) qstart = max(0, (k0 - P.causal_off) / BQ * BQ);
   int qend = P.Sq;
-  band_range(P, k0, qstart, qend);
+  bool glob_blk;  // the block holds a valid global key: every query block sees it
+  const int kwin = key_window(P, b, k0, key, kok, glob_blk);
+  if (!glob_blk) band_range(P, k0, qstart, qend);
   for (int q0 = qstart; q0 < qend; q0 += BQ) {
     if (seg_apart(P, b, q0, k0)) continue;
     __syncthreads();
@@ -403,7 +435,8 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dkdv_kernel(AttnF32Params P) {
         const int rl = 16 * t + 4 * g + i, row = q0 + rl;
         float x = sc[t][i] * P.scale;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
+        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) ||
+                         (P.window >= 0 && off_band_w(kwin, row, key));
         const float pr = msk ? 0.f : __expf(x - Rl[rl]);
         const bool kp = DROP ? keep_key(Rh[rl], key, P.thr) : true;
         const float dpk = kp ? dp[t][i] * dscale : 0.f;

@@ -21,6 +21,13 @@
 // uniform per workgroup, so the barriers stay matched).  A runtime flag like the window; packed calls at head dim 64
 // run here too.
 //
+// Global keys (AttnParamsT::k_glob / k_gblk, Longformer / LED; only with a window): a global key is visible to every
+// query, in its band or not.  Forward and dQ walk the band blocks merged with the batch row's list of blocks that hold
+// a global key (attn_small.h BlockWalk: each block once, ascending, so an all-zero k_glob is the window-only call bit
+// for bit); dK / dV walk every query block from a key block with a valid global key (key_window: a vote over the
+// block's flags) and the band from the others.  Blocks neither in the band nor listed are never loaded.  A runtime
+// flag like the window.
+//
 // Layout trick of csrc/attn_f32.hip, carried over to the 16x16x32 bf16 MFMA: its C/D map puts rows 4g .. 4g+3
 // (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction indices k = 8g + j
 // (j = 0 .. 7) from lane group g.  S^T = K Q^T leaves each lane with keys 16t + 4g + i of ONE query row; two such
@@ -117,16 +124,26 @@ DLLM_DEVICE bf16x8v pack8(f32x4 a, f32x4 b) {
 DLLM_DEVICE void st4(uint16_t* p, f32x4 v) { Elem<uint16_t>::store4(p, v); }
 
 // Waves per SIMD each instantiation is held to (the second __launch_bounds__ argument): what its register count gave
-// before the segment hooks, so that the runtime flags added since cannot cost the unsegmented calls their occupancy.
-constexpr int occ_fwd(int DP) { return DP == 32 ? 5 : DP == 64 ? 4 : 3; }
+// before the segment hooks, so that the runtime flags added since cannot cost the unsegmented calls their occupancy —
+// raised, where the segment hooks' build ran at more, to what it ran at before the global keys
+// (profiles/attn_global_keys.txt).
+// Head dim 32 serves no global keys, and its three kernels are the code they were, under the floors they had: its
+// dropout forward runs at 6 waves in 80 registers, and every form of a second walk tried there either spilled into
+// the loop of the calls without global keys or slowed them by 2 - 29 % (profiles/attn_global_keys.txt, section 5).
+// The launchers refuse k_glob at DP = 32 and the op sends such a call to the composite; forward and dQ include their
+// block body in place there, and the global-key terms are compiled out by `DP != 32` constants inside the
+// short-circuit mask chain (evaluated before the chain they cost a branch sequence per element).
+constexpr int occ_fwd(int DP, bool DROP) {
+  return DP == 32 ? 5 : DP == 64 ? 4 : DP == 96 ? (DROP ? 3 : 4) : 3;
+}
 constexpr int occ_dq(int DP, bool DROP) {
   return DP == 32 ? 4 : DP == 64 ? (DROP ? 3 : 4) : DP == 96 ? 3 : (DROP ? 3 : 2);
 }
-constexpr int occ_dkdv(int DP) { return DP == 32 ? 3 : 2; }
+constexpr int occ_dkdv(int DP) { return DP == 32 ? 3 : DP == 64 ? 3 : 2; }
 
 // ================================================================================================ forward
 template <int DP, bool DROP>
-__global__ __launch_bounds__(NT, occ_fwd(DP)) void attn_hd_fwd_kernel(AttnHdParams P) {
+__global__ __launch_bounds__(NT, occ_fwd(DP, DROP)) void attn_hd_fwd_kernel(AttnHdParams P) {
   constexpr int KS = DP / 32, DT = DP / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[Img<DP>::SIZE];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[Img<DP>::SIZE];
@@ -154,64 +171,28 @@ __global__ __launch_bounds__(NT, occ_fwd(DP)) void attn_hd_fwd_kernel(AttnHdPara
   if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
   int kstart = 0;
   band_range(P, q0, kstart, kend);
-  for (int k0 = kstart; k0 < kend; k0 += BKY) {
-    if (seg_apart(P, b, q0, k0)) continue;
-    __syncthreads();  // the previous block's LDS reads are done
-    stage<DP>(kb, P.k_ss, k0, P.Sk, P.D, Ks, tid);
-    stage<DP>(vb, P.v_ss, k0, P.Sk, P.D, Vs, tid);
-    stage_bias(P, h, q0, k0, Ls, tid, LOG2E);
-    if (tid < BKY) {
-      Mk[tid] = key_ok(P, b, k0 + tid);
-      if (P.q_seg) Sg[tid] = seg_at(P.k_seg, b, P.Sk, k0 + tid);
+  if constexpr (DP == 32) {
+    // Head dim 32 has no global keys (above): the loop and the block body as they were, in place.  (Through the lambda
+    // below its dropout instantiation no longer fits the 80 registers of its 6 waves, with or without a second loop.)
+    for (int k0 = kstart; k0 < kend; k0 += BKY) {
+      if (seg_apart(P, b, q0, k0)) continue;
+#include "attn_hd_fwd_block.h"
     }
-    __syncthreads();
-    const uint32_t vis = key_bits(P, Mk, Sg, qsg, g);  // key valid and of the row's segment
-    f32x4 st[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) st[t] = mma(ld_row<DP>(Ks, 16 * t + c, ks, g), qf[ks], st[t]);
-    }
-    // st[t][i] = S[row][key = k0 + 16 t + 4 g + i]
-    float mx = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int key = k0 + 16 * t + 4 * g + i;
-        float x = st[t][i] * scale2;
-        if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        if (hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key)) x = -INFINITY;
-        st[t][i] = x;
-        mx = fmaxf(mx, x);
+  } else {
+    // one 64-key block of the walk.  Expanded twice on purpose, once per loop below: calls without global keys keep
+    // the affine loop they had (a single data-dependent walk for both cost the segment calls 9 - 17 %,
+    // profiles/attn_global_keys.txt)
+    auto block = [&](int k0) __attribute__((always_inline)) {
+#include "attn_hd_fwd_block.h"
+    };
+    if (P.k_glob == nullptr) {  // the walk as it was before the global keys: the band (or all), segment skips
+      for (int k0 = kstart; k0 < kend; k0 += BKY) {
+        if (seg_apart(P, b, q0, k0)) continue;
+        block(k0);
       }
-    }
-    mx = grp_max(mx);
-    const float mn = fmaxf(m, mx);
-    const float mu = mn == -INFINITY ? 0.f : mn;
-    const float alpha = ex2(m - mu);
-    float ls = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const uint32_t kb4 = DROP ? keep4(rh, k0 + 16 * t + 4 * g, P.thr) : 0xFu;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float pr = ex2(st[t][i] - mu);
-        ls += pr;
-        st[t][i] = DROP ? (((kb4 >> i) & 1u) ? pr * dscale : 0.f) : pr;
-      }
-    }
-    ls = grp_sum(ls);
-    l = l * alpha + ls;
-    m = mn;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) acc[dt] *= alpha;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const bf16x8v pb = pack8(st[2 * u], st[2 * u + 1]);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) acc[dt] = mma(ld_tr2<DP>(Vs, 32 * u, 16 * dt, c, g), pb, acc[dt]);
+    } else {  // the band merged with the listed blocks outside it (no segments with global keys)
+      BlockWalk walk(P, b, kstart, kend);
+      for (int k0 = walk.next(P, -BKY); k0 != BlockWalk::DONE; k0 = walk.next(P, k0)) block(k0);
     }
   }
   // acc[dt][i] = O[row][d = 16 dt + 4 g + i] (unnormalised)
@@ -272,6 +253,10 @@ __global__ __launch_bounds__(NT, occ_dq(DP, DROP)) void attn_hd_dq_kernel(AttnHd
   const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
   const float scale2 = P.scale * LOG2E;
   const bool want_dlut = P.dlut != nullptr && P.lut != nullptr;
+  // the row's dQ address, formed here: two vector registers through the walk instead of the eight scalar ones of the
+  // base and strides, which the walk's own scalars would otherwise push out to spills
+  uint16_t* dqp = P.dq + (long)b * P.dq_sb + (long)rowc * P.dq_ss + (long)h * P.dq_sh;
+  if constexpr (DP != 32) asm volatile("" : "+v"(dqp));  // formed here, not sunk to the epilogue (DP = 32: no walk)
   f32x4 acc[DT];
 #pragma unroll
   for (int i = 0; i < DT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -281,60 +266,31 @@ __global__ __launch_bounds__(NT, occ_dq(DP, DROP)) void attn_hd_dq_kernel(AttnHd
   if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
   int kstart = 0;
   band_range(P, q0, kstart, kend);
-  for (int k0 = kstart; k0 < kend; k0 += BKY) {
-    if (seg_apart(P, b, q0, k0)) continue;
-    __syncthreads();
-    stage<DP>(kb, P.k_ss, k0, P.Sk, P.D, Ks, tid);
-    stage<DP>(vb, P.v_ss, k0, P.Sk, P.D, Vs, tid);
-    stage_bias(P, h, q0, k0, Ls, tid, LOG2E);
-    if (tid < BKY) {
-      Mk[tid] = key_ok(P, b, k0 + tid);
-      if (P.q_seg) Sg[tid] = seg_at(P.k_seg, b, P.Sk, k0 + tid);
+  if constexpr (DP == 32) {
+    // Head dim 32 has no global keys: the loop and the block body of before, in place, as in the forward
+    for (int k0 = kstart; k0 < kend; k0 += BKY) {
+      if (seg_apart(P, b, q0, k0)) continue;
+#include "attn_hd_dq_block.h"
     }
-    __syncthreads();
-    const uint32_t vis = key_bits(P, Mk, Sg, qsg, g);  // key valid and of the row's segment
-    f32x4 st[4], dpt[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dpt[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        st[t] = mma(ld_row<DP>(Ks, 16 * t + c, ks, g), qf[ks], st[t]);
-        dpt[t] = mma(ld_row<DP>(Vs, 16 * t + c, ks, g), dof[ks], dpt[t]);
+  } else {
+    // one 64-key block of the walk.  Expanded twice on purpose, once per loop below: calls without global keys keep
+    // the affine loop they had (a single data-dependent walk for both cost the segment calls 9 - 17 %,
+    // profiles/attn_global_keys.txt)
+    auto block = [&](int k0) __attribute__((always_inline)) {
+#include "attn_hd_dq_block.h"
+    };
+    if (P.k_glob == nullptr) {  // the walk as it was before the global keys: the band (or all), segment skips
+      for (int k0 = kstart; k0 < kend; k0 += BKY) {
+        if (seg_apart(P, b, q0, k0)) continue;
+        block(k0);
       }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const uint32_t kb4 = DROP ? keep4(rh, k0 + 16 * t + 4 * g, P.thr) : 0xFu;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int key = k0 + 16 * t + 4 * g + i;
-        const int di = key - row - (k0 - q0 - 63);
-        float x = st[t][i] * scale2;
-        if (P.lut) x += Ls[di];
-        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
-        const float pr = msk ? 0.f : ex2(x - lse);
-        const float dpk = DROP ? (((kb4 >> i) & 1u) ? dpt[t][i] * dscale : 0.f) : dpt[t][i];
-        const float ds = pr * (dpk - dlt);
-        st[t][i] = ds;
-        if (want_dlut) Ds[(16 * w + c) * (BKY + 1) + 16 * t + 4 * g + i] = ds;  // 0 for rows >= Sq (lse = inf)
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const bf16x8v sb = pack8(st[2 * u], st[2 * u + 1]);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) acc[dt] = mma(ld_tr2<DP>(Ks, 32 * u, 16 * dt, c, g), sb, acc[dt]);
-    }
-    if (want_dlut) {
-      __syncthreads();  // the block's dS tile is complete
-      dlut_add_diagonals(P, h, q0, k0, Ds, tid);
+    } else {  // the band merged with the listed blocks outside it (no segments with global keys)
+      BlockWalk walk(P, b, kstart, kend);
+      for (int k0 = walk.next(P, -BKY); k0 != BlockWalk::DONE; k0 = walk.next(P, k0)) block(k0);
     }
   }
   // acc[dt][i] = dQ[row][d = 16 dt + 4 g + i] / scale
   if (row_ok) {
-    uint16_t* dqp = P.dq + (long)b * P.dq_sb + (long)row * P.dq_ss + (long)h * P.dq_sh;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
       if (16 * dt + 4 * g < P.D) st4(dqp + 16 * dt + 4 * g, acc[dt] * P.scale);
@@ -374,7 +330,10 @@ __global__ __launch_bounds__(NT, occ_dkdv(DP)) void attn_hd_dkdv_kernel(AttnHdPa
   int qstart = 0;
   if (P.causal) qstart = max(0, (k0 - P.causal_off) / BQ * BQ);
   int qend = P.Sq;
-  band_range(P, k0, qstart, qend);
+  bool glob_blk = false;  // the block holds a valid global key: every query block sees it
+  int kwin = P.window;
+  if constexpr (DP != 32) kwin = key_window(P, b, k0, key, kok, glob_blk);  // no global keys at head dim 32
+  if (!glob_blk) band_range(P, k0, qstart, qend);
   for (int q0 = qstart; q0 < qend; q0 += BQ) {
     if (seg_apart(P, b, q0, k0)) continue;
     __syncthreads();
@@ -411,7 +370,8 @@ __global__ __launch_bounds__(NT, occ_dkdv(DP)) void attn_hd_dkdv_kernel(AttnHdPa
         const int rl = 16 * t + 4 * g + i, row = q0 + rl;
         float x = sc[t][i] * scale2;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key);
+        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) ||
+                         (DP == 32 ? off_band(P, row, key) : (P.window >= 0 && off_band_w(kwin, row, key)));
         const float pr = msk ? 0.f : ex2(x - Rl[rl]);
         const bool kp = DROP ? keep_key(Rh[rl], key, P.thr) : true;
         const float dpk = kp ? dp[t][i] * dscale : 0.f;
@@ -473,6 +433,7 @@ int launch_bwd(const AttnHdParams& P, hipStream_t st) {
 extern "C" int dllm_attn_hd_fwd(AttnHdParams* pp, hipStream_t st) {
   const AttnHdParams& P = *pp;
   if (P.D < 32 || P.D > 128 || P.D % 8) return -1;
+  if (P.D == 32 && P.k_glob != nullptr) return -2;  // the binding checks it first
   switch ((P.D + 31) / 32) {
     case 1: return launch_fwd<32>(P, st);
     case 2: return launch_fwd<64>(P, st);
@@ -484,6 +445,7 @@ extern "C" int dllm_attn_hd_fwd(AttnHdParams* pp, hipStream_t st) {
 extern "C" int dllm_attn_hd_bwd(AttnHdParams* pp, hipStream_t st) {
   const AttnHdParams& P = *pp;
   if (P.D < 32 || P.D > 128 || P.D % 8) return -1;
+  if (P.D == 32 && P.k_glob != nullptr) return -2;
   const long rows = (long)P.B * P.H * P.Sq;
   hipLaunchKernelGGL(attn_hd_delta_kernel, dim3((unsigned)((rows + NT / 16 - 1) / (NT / 16))), dim3(NT), 0, st, P);
   DLLM_CHECK_LAUNCH();

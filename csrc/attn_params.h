@@ -24,6 +24,17 @@
 // is correct for any ids and exact for non-decreasing ones (what data/packing.py emits).  Segments compose with kpm,
 // causal, the bias and dropout (the keep hash still indexes (b, h, row, key)), not with a window (the binding
 // rejects it); csrc/attn.hip has no segments and is never given any.
+// Global keys (Longformer / LED): k_glob is given only with window >= 0, together with k_gblk. With it key j is visible
+// to query i iff key_ok && (!off_band || k_glob[b][j]): a global key is seen by every query, inside its window or not
+// (and counts once where it lies inside). k_gblk lists, per batch row, the 64-key blocks that hold a global key: [b][0]
+// = their number n, [b][1 .. n] their indices, ascending (the rest of the row is not read). Forward and dQ walk the
+// band blocks and the listed blocks outside it, each block once and in ascending key order, so a call whose k_glob is
+// all zero is the window-only call, bit for bit; dK / dV walk every query block from a key block that holds a valid
+// global key (every wave reads the block's 64 flags and votes, so uniform) and the band from any other. Blocks neither
+// in the band nor listed are never loaded: work and traffic are O(S * (window + 64 * listed blocks)). Global keys
+// compose with kpm, the bias LUT (indexed by j - i as always) and dropout (the keep hash still indexes (b, h, row,
+// key)), not with causal or segments (the binding rejects both); csrc/attn.hip has none, and csrc/attn_hd.hip none at
+// head dim 32 (the binding rejects it).
 // Bias: lut[h][(j - i) + Sq - 1] is added to the scaled score.
 // LSE: [B, H, Sq] fp32, forward writes and backward reads; +inf marks a row without a visible key (its output row is
 // 0).  The bf16 families store it in log2 units (scores are scaled by log2(e), softmax by exp2), fp32 in natural-log
@@ -55,6 +66,10 @@ struct AttnParamsT {
   const int* k_seg;    // [B, Sk]; given with q_seg
   const int* q_blk;    // [B, ceil(Sq / 64), 2] (min, max) of the ids >= 0 of each 64-block of q_seg; given with q_seg
   const int* k_blk;    // [B, ceil(Sk / 64), 2]
+  const uint8_t* k_glob;  // [B, Sk] 1 = global key; nullptr: none; only with window >= 0 (csrc/attn_hd.hip,
+                          // csrc/attn_f32.hip only)
+  const int* k_gblk;   // [B, 1 + ceil(Sk / 64)]: the number of 64-key blocks with a global key, then their indices
+                       // (ascending); given with k_glob
   long q_sb, q_ss, q_sh;
   long k_sb, k_ss, k_sh;
   long v_sb, v_ss, v_sh;

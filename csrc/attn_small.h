@@ -64,6 +64,82 @@ DLLM_DEVICE void band_range(const Params& P, int x0, int& lo, int& hi) {
   }
 }
 
+// Global keys (attn_params.h k_glob / k_gblk, nullptr: none).  The block walk of forward and dQ: the 64-blocks of the
+// band [lo, hi) (lo % 64 == 0) merged with the batch row's ascending list gl[0 .. n) of blocks that hold a global key,
+// each once and in ascending order.  next() returns the first such block start after `prev` (-64 to begin), DONE after
+// the last.  Without a list it is the plain walk of [lo, hi).  Everything here is uniform over the workgroup, so the
+// barriers of the walked blocks stay matched.  Entries outside [0, ceil(S / 64)) are passed over.
+struct BlockWalk {
+  static constexpr int DONE = 0x7FFFFFFF;
+  int gi, ge, lo, hi;  // the list as indices gi .. ge - 1 into k_gblk (no pointer kept: fewer scalar registers)
+  template <class Params>
+  DLLM_DEVICE BlockWalk(const Params& P, int b, int lo_, int hi_) : gi(0), ge(0), lo(lo_), hi(hi_) {
+    if (P.k_glob != nullptr) {
+      const int nblk = (P.Sk + 63) / 64;
+      gi = b * (nblk + 1) + 1;
+      ge = gi + min(P.k_gblk[gi - 1], nblk);
+    }
+  }
+  template <class Params>
+  DLLM_DEVICE int next(const Params& P, int prev) {
+    const int cand = prev + 64;
+    int nb = max(cand, lo);
+    if (nb >= hi) nb = DONE;
+    while (gi < ge) {
+      const int e = P.k_gblk[gi];
+      if ((unsigned)e < ((unsigned)P.Sk + 63u) / 64u && e * 64 >= cand) {
+        nb = min(nb, e * 64);
+        break;
+      }
+      ++gi;
+    }
+    return nb;
+  }
+};
+// The staged key bytes of forward / dQ carry the global flag in bit 1 (bit 0: key valid).
+template <class Params>
+DLLM_DEVICE uint8_t key_byte(const Params& P, int b, int key) {
+  uint8_t m = key_ok(P, b, key) ? 1 : 0;
+  if (P.k_glob != nullptr && key < P.Sk && P.k_glob[(long)b * P.Sk + key] != 0) m |= 2;
+  return m;
+}
+// glob_bits: bit 16 + 4 t + i <-> the key at 16 t + 4 g + i is global; OR-ed into the visibility word of key_bits
+template <class Params>
+DLLM_DEVICE uint32_t glob_bits(const Params& P, const uint8_t* mk, int g) {
+  uint32_t m = 0u;
+  if (P.k_glob != nullptr) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t w = *reinterpret_cast<const uint32_t*>(mk + 16 * t + 4 * g) >> 1;
+      m |= ((w & 1u) | ((w >> 7) & 2u) | ((w >> 14) & 4u) | ((w >> 21) & 8u)) << (16 + 4 * t);
+    }
+  }
+  return m;
+}
+// element predicate of forward / dQ: the pair at (t, i) lies outside the band and its key is not global
+template <class Params>
+DLLM_DEVICE bool off_band(const Params& P, int row, int key, uint32_t bits, int t, int i) {
+  return off_band(P, row, key) && ((bits >> (16 + 4 * t + i)) & 1u) == 0u;
+}
+// dK / dV: the window of the lane's key — none (INT_MAX) for a valid global key, else P.window — and whether the
+// workgroup's key block at k0 holds a valid global key (the block then walks every query block).  Every wave reads the
+// block's 64 flags, one per lane, and votes: the same answer in all four waves without a barrier or LDS, so uniform
+// over the workgroup.  (Plain loads and a ballot only: nothing here that would keep the compiler from reading the
+// segment tables through the scalar cache.)
+template <class Params>
+DLLM_DEVICE int key_window(const Params& P, int b, int k0, int key, bool kok, bool& any) {
+  any = false;
+  if (P.k_glob == nullptr) return P.window;
+  const int kl = k0 + (int)(threadIdx.x & 63u);
+  const bool g = key_ok(P, b, kl) && P.k_glob[(long)b * P.Sk + kl] != 0;  // key_ok: kl < Sk
+  any = __ballot(g) != 0ull;
+  const bool kg = kok && P.k_glob[(long)b * P.Sk + key] != 0;  // kok: key < Sk
+  return kg ? 0x7FFFFFFF : P.window;
+}
+// off_band against a lane's own window wl >= 0 (the caller tests P.window >= 0 first: uniform, so calls without a
+// window skip the per-element work as before)
+DLLM_DEVICE bool off_band_w(int wl, int row, int key) { return (key > row ? key - row : row - key) > wl; }
+
 // Segments (attn_params.h q_seg / k_seg, nullptr: none).  Id of position x of a [B, S] id tensor; padding (-1) past S
 DLLM_DEVICE int seg_at(const int* seg, int b, int S, int x) { return x < S ? seg[(long)b * S + x] : -1; }
 // Visibility of the lane's 16 pairs of a block as one word: bit 4 t + i <-> the partner at 16 t + 4 g + i.  One

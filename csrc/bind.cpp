@@ -2,6 +2,7 @@
 // Host-side validation lives here: every shape / dtype / stride / alignment a kernel assumes is checked
 // BEFORE launch (a kernel that faults can reset every GPU on the node), then the C-ABI launchers in
 // csrc/*.hip run on the current torch HIP stream.
+#include <type_traits>
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
@@ -423,6 +424,8 @@ void fill_common(P& p, const AttnFamily<P>& f, int64_t D, const Tensor& q, const
   p.causal_off = Sk - Sq;
   p.window = -1;  // set_window: csrc/attn_f32.hip and csrc/attn_hd.hip only
   p.q_seg = p.k_seg = p.q_blk = p.k_blk = nullptr;  // set_segments: the same two families only
+  p.k_glob = nullptr;  // set_global: the same two families only
+  p.k_gblk = nullptr;
   p.p_drop = (float)drop;
   p.seed = (uint32_t)seed;
   p.thr = drop > 0.0 ? (uint32_t)std::min(65535.0, drop * 65536.0) : 0u;  // ops/rng.py threshold16
@@ -531,16 +534,45 @@ void set_segments(P& p, const optional<Tensor>& q_seg, const optional<Tensor>& k
   p.k_blk = k_blk->data_ptr<int>();
 }
 
+// the global keys of csrc/attn_params.h: flags [B, Sk] and the per-batch list of the 64-key blocks that hold one, both
+// or neither, only with a window
+template <class P>
+void set_global(P& p, const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
+  auto has = [](const optional<Tensor>& t) { return t.has_value() && t->defined(); };
+  if (!has(k_glob) && !has(k_gblk)) return;
+  TORCH_CHECK(has(k_glob) && has(k_gblk), "attention: k_glob and k_gblk are given together or not at all");
+  TORCH_CHECK(!p.causal, "attention: global keys with causal are unsupported");
+  TORCH_CHECK(p.q_seg == nullptr, "attention: global keys with segments are unsupported");
+  TORCH_CHECK(p.window >= 0, "attention: global keys need a window");
+  TORCH_CHECK(!(std::is_same<P, AttnHdParams>::value && p.D == 32),
+              "attn_hd: global keys at head dim 32 are not served (csrc/attn_hd.hip)");
+  const int64_t nb = (p.Sk + 63) / 64;
+  check_gpu(*k_glob, "k_glob");
+  check_gpu(*k_gblk, "k_gblk");
+  TORCH_CHECK(k_glob->scalar_type() == at::kByte, "k_glob must be uint8");
+  TORCH_CHECK(k_gblk->scalar_type() == at::kInt, "k_gblk must be int32");
+  TORCH_CHECK(k_glob->dim() == 2 && k_glob->size(0) == p.B && k_glob->size(1) == p.Sk, "k_glob: expected [", p.B, ", ",
+              p.Sk, "], got ", k_glob->sizes());
+  TORCH_CHECK(k_gblk->dim() == 2 && k_gblk->size(0) == p.B && k_gblk->size(1) == nb + 1, "k_gblk: expected [", p.B,
+              ", ", nb + 1, "], got ", k_gblk->sizes());
+  TORCH_CHECK(k_glob->is_contiguous(), "k_glob must be contiguous");
+  TORCH_CHECK(k_gblk->is_contiguous(), "k_gblk must be contiguous");
+  p.k_glob = k_glob->data_ptr<uint8_t>();
+  p.k_gblk = k_gblk->data_ptr<int>();
+}
+
 template <class P>
 std::vector<Tensor> attn_small_fwd(const AttnFamily<P>& f, int64_t D, const Tensor& q, const Tensor& k,
                                    const Tensor& v, const optional<Tensor>& kpm, const optional<Tensor>& lut,
                                    double scale, bool causal, double p, int64_t seed, int64_t window,
                                    const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
-                                   const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
+                                   const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
+                                   const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
   P prm{};
   fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
   set_window(prm, window);
   set_segments(prm, q_seg, k_seg, q_blk, k_blk);
+  set_global(prm, k_glob, k_gblk);
   check_limits_small(prm);
   auto out = fill_fwd(prm, q);
   check_rc(f.fwd(&prm, stream()), f.fwd_name);
@@ -554,11 +586,13 @@ std::vector<Tensor> attn_small_bwd(const AttnFamily<P>& f, int64_t D, const Tens
                                    double p, int64_t seed, bool need_dlut, const optional<Tensor>& dq_out,
                                    const optional<Tensor>& dk_out, const optional<Tensor>& dv_out, int64_t window,
                                    const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
-                                   const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
+                                   const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
+                                   const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
   P prm{};
   fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
   set_window(prm, window);
   set_segments(prm, q_seg, k_seg, q_blk, k_blk);
+  set_global(prm, k_glob, k_gblk);
   check_limits_small(prm);
   auto r = fill_bwd(prm, f, q, o, dout, lse, dq_out, dk_out, dv_out, need_dlut);
   check_rc(f.bwd(&prm, stream()), f.bwd_name);
@@ -569,9 +603,10 @@ std::vector<Tensor> attn_f32_fwd(const Tensor& q, const Tensor& k, const Tensor&
                                  const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
                                  int64_t window,
                                  const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
-                                 const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
+                                 const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
+                                 const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
   return attn_small_fwd(kAttnF32, 64, q, k, v, kpm, lut, scale, causal, p, seed, window, q_seg, k_seg, q_blk,
-                        k_blk);
+                        k_blk, k_glob, k_gblk);
 }
 
 std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
@@ -580,9 +615,10 @@ std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tens
                                  bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
                                  const optional<Tensor>& dv_out, int64_t window,
                                  const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
-                                 const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
+                                 const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
+                                 const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
   return attn_small_bwd(kAttnF32, 64, dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed, need_dlut, dq_out,
-                        dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk);
+                        dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk, k_glob, k_gblk);
 }
 
 // the head dim of an attn_hd call: what csrc/attn_hd.hip is instantiated for (padded to 32, 16-B rows)
@@ -597,9 +633,10 @@ std::vector<Tensor> attn_hd_fwd(const Tensor& q, const Tensor& k, const Tensor& 
                                 const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
                                 int64_t window,
                                 const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
-                                const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
+                                const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
+                                const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
   return attn_small_fwd(kAttnHd, attn_hd_dim(q, k), q, k, v, kpm, lut, scale, causal, p, seed, window, q_seg, k_seg,
-                        q_blk, k_blk);
+                        q_blk, k_blk, k_glob, k_gblk);
 }
 
 std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
@@ -608,9 +645,10 @@ std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tenso
                                 bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
                                 const optional<Tensor>& dv_out, int64_t window,
                                 const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
-                                const optional<Tensor>& q_blk, const optional<Tensor>& k_blk) {
+                                const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
+                                const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
   return attn_small_bwd(kAttnHd, attn_hd_dim(q, k), dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed,
-                        need_dlut, dq_out, dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk);
+                        need_dlut, dq_out, dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk, k_glob, k_gblk);
 }
 
 // ---- csrc/attn.hip: the same helpers, plus its extras (dropout bit planes, saturated-bias ranges, rowrec, column sums)
@@ -1405,20 +1443,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("csv") = py::none());
   m.def("attn_f32_fwd", &attn_f32_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
         py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1,
-        py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none());
+        py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
+        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none());
   m.def("attn_f32_bwd", &attn_f32_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
         py::arg("dv_out") = py::none(), py::arg("window") = -1, py::arg("q_seg") = py::none(),
-        py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none());
+        py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
+        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none());
   m.def("attn_hd_fwd", &attn_hd_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
         py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1,
-        py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none());
+        py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
+        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none());
   m.def("attn_hd_bwd", &attn_hd_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
         py::arg("dv_out") = py::none(), py::arg("window") = -1, py::arg("q_seg") = py::none(),
-        py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none());
+        py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
+        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none());
   m.def("gemm_wgrad_segs", &gemm_wgrad_segs, "c (+)= sum_i a_i^T b_i (deferred micro-batch segments, w4)",
         py::arg("a"), py::arg("b"), py::arg("c"), py::arg("beta") = true);
   m.def("gemm_wgrad", &gemm_wgrad, "c (+)= a^T b (token-major bf16 operands)", py::arg("a"), py::arg("b"), py::arg("c"),

@@ -8,6 +8,11 @@
 Packed rows (data/packing.py: features that carry ``segment_ids``) have one fixed shape and their decoder inputs were
 built per segment by the packer, so they are stacked key by key as they are.
 
+LED (``model_type == "led"``): transformers' summarization recipe, the first token of every example is global.  The
+batch carries it twice, as ``global_attention_mask`` ``[B, S]`` (1 = global) and as ``global_index`` ``[B, 1]`` (the
+position, here 0): the index has a shape that does not depend on the data, so the model needs no host sync to size
+its global rows and a graphed step replays on it (models/bart.py).
+
 Returns int64 CPU tensors; ``pin_memory`` lets the device copy run async (non_blocking).
 """
 from __future__ import annotations
@@ -18,17 +23,20 @@ import torch
 
 class DataCollatorForSeq2Seq:
     def __init__(self, pad_token_id: int = 0, decoder_start_token_id: int = 0, pad_to_multiple_of: int | None = None,
-                 label_pad_token_id: int = -100, with_decoder_inputs: bool = True, pin_memory: bool = False):
+                 label_pad_token_id: int = -100, with_decoder_inputs: bool = True, pin_memory: bool = False,
+                 global_first_token: bool = False):
         self.pad_token_id = pad_token_id
         self.decoder_start_token_id = decoder_start_token_id
         self.pad_to_multiple_of = pad_to_multiple_of
         self.label_pad_token_id = label_pad_token_id
         self.with_decoder_inputs = with_decoder_inputs
         self.pin_memory = pin_memory
+        self.global_first_token = global_first_token  # LED
 
     @classmethod
     def for_model(cls, model_or_cfg, **kw):
         cfg = getattr(model_or_cfg, "config", model_or_cfg)
+        kw.setdefault("global_first_token", getattr(cfg, "model_type", None) == "led")
         return cls(pad_token_id=cfg.pad_token_id, decoder_start_token_id=cfg.decoder_start_token_id, **kw)
 
     def _target(self, n):
@@ -44,6 +52,8 @@ class DataCollatorForSeq2Seq:
 
     def __call__(self, features):
         if "segment_ids" in features[0]:  # packed rows: fixed shape, nothing to pad or shift
+            if self.global_first_token:
+                raise NotImplementedError("LED: packed inputs (--pack-sequences, segment ids) are not implemented")
             batch = {k: torch.from_numpy(np.stack([np.asarray(f[k]) for f in features]).astype(np.int64))
                      for k in features[0]}
             if self.pin_memory and torch.cuda.is_available():
@@ -55,6 +65,11 @@ class DataCollatorForSeq2Seq:
         else:
             am = (ids != self.pad_token_id).long()
         batch = {"input_ids": ids, "attention_mask": am}
+        if self.global_first_token:
+            gm = torch.zeros_like(ids)
+            gm[:, 0] = 1
+            batch["global_attention_mask"] = gm
+            batch["global_index"] = torch.zeros(ids.shape[0], 1, dtype=torch.int64)
         if "labels" in features[0]:
             labels = self._pad([np.asarray(f["labels"]) for f in features], self.label_pad_token_id)
             batch["labels"] = labels

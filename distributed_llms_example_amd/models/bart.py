@@ -22,6 +22,20 @@ decoder_position_ids=)`` runs rows that hold several examples.  Attention is con
 segment-masked kernels (ops/attention.py) — (seg, seg) in the encoder, (dseg, dseg) with causal in the decoder, (dseg,
 seg) across — and every position kind reads the row of its table at ``position_ids``, the index within the example,
 in place of the running index.
+
+LED (``model_type: "led"``, transformers modeling_led.py): the BART stack whose ENCODER self-attention is Longformer's.
+With ``w = attention_window[layer] // 2``, the key-padding mask ``valid`` and the global flags ``glob`` (on valid tokens
+only), every encoder query row ``i`` takes one softmax, scale ``head_dim**-0.5``, over the keys with ``valid[b, j] and
+(|j - i| <= w or glob[b, j])`` through the ordinary query / key / value projections — one launch of the windowed
+kernels with global keys (ops/attention.py) at any length, never chunked, O(S·w) — and the rows ``i`` with
+``glob[b, i]`` have their output replaced by full attention over all valid keys through projections of their own
+(``query_global`` / ``key_global`` / ``value_global``): a few query rows against every key, which is the
+cross-attention kernels' shape.  transformers pads the input to a multiple of the window and cuts it off again; with
+the rule above that changes nothing, so nothing is padded here.  Its padded query rows are 0, ours may hold anything
+finite: nothing reads them.  ``forward`` / ``encode`` / ``generate`` take ``global_attention_mask`` ``[B, S]`` (1 =
+global; None: no global token) and / or ``global_index`` ``[B, n]`` int64 (-1 = none), the same information in a shape
+that does not depend on the data: given both (data/collator.py emits both), the step has no host sync and replays
+from a HIP graph.  Packed inputs and context parallelism are not implemented for LED.
 """
 from __future__ import annotations
 
@@ -101,12 +115,61 @@ class BartAttention(nn.Module):
         return (out, res) if residual else out
 
 
+class LEDEncoderSelfAttention(nn.Module):
+    """LED's encoder self-attention (modeling_led.py LEDEncoderSelfAttention): sliding window + global tokens, see the
+    module docstring.  ``qkv_proj`` is query | key | value, ``kv_global`` key_global | value_global (models/hf_io.py
+    splits them into transformers' names)."""
+
+    def __init__(self, cfg: Seq2SeqConfig, attention_window: int):
+        super().__init__()
+        d = cfg.d_model
+        self.n_heads = cfg.num_heads
+        self.head_dim = d // cfg.num_heads
+        self.scaling = self.head_dim ** -0.5
+        self.window = attention_window // 2  # keys on either side
+        self.qkv_proj = Linear(d, 3 * d)
+        self.q_global = Linear(d, d)
+        self.kv_global = Linear(d, 2 * d)
+        self.out_proj = Linear(d, d)
+
+    def forward(self, x, mask=None, p=0.0, residual=False, glob=None):
+        """``glob``: None, or (ops/attention.py GlobalKeys, global_index [B, n] with -1 = none) of the batch."""
+        B, S, _ = x.shape
+        H, D = self.n_heads, self.head_dim
+        rng = default_rng()
+        gk, gidx = glob if glob is not None else (None, None)
+        if residual:
+            qkv, res = linear_res(x, self.qkv_proj)
+        else:
+            qkv, res = self.qkv_proj(x), x
+        o = attn_ops.attention_qkv(qkv.view(B, S, 3, H, D), scale=self.scaling, key_padding_mask=mask, dropout_p=p,
+                                   seed=rng.next_seed() if p > 0 else 0, window=self.window, global_keys=gk)
+        o = o.reshape(B, S, H * D)
+        if gidx is not None:
+            # the rows at the global positions: full attention through the global projections, scattered over the
+            # windowed result.  Entries -1 gather row 0 and scatter into a spare row S that is cut off again
+            n = gidx.shape[1]
+            hg = torch.gather(x, 1, gidx.clamp_min(0)[:, :, None].expand(B, n, x.shape[2]))
+            qg = self.q_global(hg).view(B, n, H, D)
+            kvg = self.kv_global(x).view(B, S, 2, H, D)
+            og = attn_ops.attention_q_kv(qg, kvg, scale=self.scaling, key_padding_mask=mask, dropout_p=p,
+                                         seed=rng.next_seed() if p > 0 else 0)
+            to = torch.where(gidx >= 0, gidx, torch.full_like(gidx, S))[:, :, None].expand(B, n, H * D)
+            o = torch.cat((o, o.new_zeros(B, 1, H * D)), 1).scatter(1, to, og.reshape(B, n, H * D))[:, :S]
+        out = self.out_proj(o)
+        return (out, res) if residual else out
+
+
 class BartLayer(nn.Module):
-    def __init__(self, cfg, is_decoder):
+    def __init__(self, cfg, is_decoder, index=0):
         super().__init__()
         d = cfg.d_model
         self.is_decoder = is_decoder
-        self.self_attn = BartAttention(cfg, cross=False)
+        self.led_encoder = cfg.model_type == "led" and not is_decoder
+        if self.led_encoder:
+            self.self_attn = LEDEncoderSelfAttention(cfg, cfg.attention_window[index])
+        else:
+            self.self_attn = BartAttention(cfg, cross=False)
         self.self_attn_layer_norm = nn.LayerNorm(d)
         if is_decoder:
             self.encoder_attn = BartAttention(cfg, cross=True)
@@ -116,7 +179,8 @@ class BartLayer(nn.Module):
         self.final_layer_norm = nn.LayerNorm(d)
         self.cfg = cfg
 
-    def forward(self, h, mask=None, enc_out=None, enc_mask=None, cache=None, cross_kv=None, seg=None, cross_seg=None):
+    def forward(self, h, mask=None, enc_out=None, enc_mask=None, cache=None, cross_kv=None, seg=None, cross_seg=None,
+                glob=None):
         cfg = self.cfg
         tr = self.training
         p = cfg.dropout_rate if tr else 0.0
@@ -126,8 +190,11 @@ class BartLayer(nn.Module):
         rng = default_rng()
         # post-LN blocks: each block's input is both the sublayer input and the residual; the sublayers hand the
         # residual back from their input projection so its gradient is summed inside that projection's dgrad GEMM
-        a, h = self.self_attn(h, mask=None if self.is_decoder else mask, causal=self.is_decoder, p=pa, cache=cache,
-                              residual=True, seg=seg)
+        if self.led_encoder:
+            a, h = self.self_attn(h, mask=mask, p=pa, residual=True, glob=glob)
+        else:
+            a, h = self.self_attn(h, mask=None if self.is_decoder else mask, causal=self.is_decoder, p=pa, cache=cache,
+                                  residual=True, seg=seg)
         xb = _NORM_BIAS_COLSUM  # out_proj / fc2 bias gradients summed by the norm backward kernel (ops/norms.py)
         h = norms.add_dropout_layer_norm(h, a, self.self_attn_layer_norm.weight, self.self_attn_layer_norm.bias, eps,
                                          p, rng.next_seed() if p > 0 else 0, xb)
@@ -235,10 +302,13 @@ class BartStack(nn.Module):
         else:
             pos_cls = {"sinusoidal": SinusoidalPositions, "learned0": LearnedPositionalEmbedding0}.get(
                 cfg.position_embedding, BartLearnedPositionalEmbedding)
-            self.embed_positions = pos_cls(cfg.max_position_embeddings, cfg.d_model)
+            # LED: the encoder's table has a size of its own; max_position_embeddings is the decoder's
+            n_pos = (cfg.max_encoder_position_embeddings if cfg.model_type == "led" and not is_decoder
+                     else cfg.max_position_embeddings)
+            self.embed_positions = pos_cls(n_pos, cfg.d_model)
             self._pos_offset = pos_cls.offset
         n = cfg.num_decoder_layers if is_decoder else cfg.num_layers
-        self.layers = nn.ModuleList([BartLayer(cfg, is_decoder) for _ in range(n)])
+        self.layers = nn.ModuleList([BartLayer(cfg, is_decoder, i) for i in range(n)])
         if cfg.layernorm_embedding:
             self.layernorm_embedding = nn.LayerNorm(cfg.d_model)
         if cfg.normalize_before:  # pre-LN stacks end with a LayerNorm (modeling_mbart.py MBartEncoder.layer_norm)
@@ -255,10 +325,16 @@ class BartStack(nn.Module):
         return stacked_linear(enc_out, self.cross_kv_linears(), (B, S, 2, H, self.cfg.d_model // H))
 
     def forward(self, input_ids, attention_mask=None, enc_out=None, enc_mask=None, caches=None, q_offset=0,
-                cross_kv=None, seg=None, cross_seg=None, position_ids=None):
+                cross_kv=None, seg=None, cross_seg=None, position_ids=None, glob=None):
         cfg = self.cfg
         p = cfg.dropout_rate if self.training else 0.0
         B, S = input_ids.shape
+        if cfg.model_type == "led":
+            if seg is not None or cross_seg is not None or position_ids is not None:
+                raise NotImplementedError("LED: packed inputs (--pack-sequences, segment ids) are not implemented")
+            if not self.is_decoder and S > cfg.max_encoder_position_embeddings:
+                raise ValueError(f"LED: input of {S} tokens is longer than max_encoder_position_embeddings = "
+                                 f"{cfg.max_encoder_position_embeddings}")
         if (seg is not None or position_ids is not None) and caches is not None:
             raise NotImplementedError("packed inputs (segment / position ids) are not implemented with a generation "
                                       "cache")
@@ -288,6 +364,8 @@ class BartStack(nn.Module):
             ckv = cross_kv[i] if cross_kv is not None else None
 
             def run(h, layer=layer, cache=cache, ckv=ckv):
+                if glob is not None:
+                    return layer(h, mask=attention_mask, glob=glob)
                 return layer(h, mask=attention_mask, enc_out=enc_out, enc_mask=enc_mask, cache=cache, cross_kv=ckv,
                              seg=seg, cross_seg=cross_seg)
 
@@ -375,8 +453,49 @@ class BartForConditionalGeneration(nn.Module):
 
     prepare_decoder_input_ids_from_labels = shift_right
 
-    def encode(self, input_ids, attention_mask=None, seg=None, position_ids=None):
-        return self.model.encoder(input_ids, attention_mask=attention_mask, seg=seg, position_ids=position_ids)
+    def encode(self, input_ids, attention_mask=None, seg=None, position_ids=None, global_attention_mask=None,
+               global_index=None):
+        glob = self._global_tokens(input_ids, attention_mask, global_attention_mask, global_index)
+        return self.model.encoder(input_ids, attention_mask=attention_mask, seg=seg, position_ids=position_ids,
+                                  glob=glob)
+
+    def _global_tokens(self, input_ids, attention_mask, gmask, gidx):
+        """LED's global tokens as the encoder layers take them: (ops/attention.py GlobalKeys, global_index [B, n]),
+        built once per batch; None without any.  The mask ``[B, S]`` (1 = global) and the index ``[B, n]`` (int64,
+        -1 = none) carry the same information: either is derived from the other — the index from the mask with a host
+        sync (its width is the largest number of global tokens of a row), the mask from the index without one.
+        Given both, they are NOT compared (that would cost the host sync the pair exists to avoid): the windowed call's
+        global keys come from the mask and the replaced rows from the index, so the caller keeps them naming the same
+        tokens, each position at most once per row (data/collator.py does); duplicates make the scatter's winner
+        undefined.  An index that is all -1 (given without a mask) still runs the global projections and the short
+        call of every layer into the spare row: correct, and wasted work that only a host sync could skip."""
+        if gmask is None and gidx is None:
+            return None
+        if self.config.model_type != "led":
+            raise ValueError(f"global_attention_mask / global_index are LED's; this model is a "
+                             f"{self.config.model_type}")
+        B, S = input_ids.shape
+        if gmask is None:
+            to = torch.where(gidx >= 0, gidx, torch.full_like(gidx, S))
+            on = torch.zeros(B, S + 1, dtype=torch.bool, device=gidx.device).scatter(1, to, True)[:, :S]
+        else:
+            on = gmask != 0
+        if attention_mask is not None:  # global flags live on valid tokens only
+            on = on & (attention_mask != 0)
+        if gidx is None:
+            count = on.sum(1, keepdim=True)
+            n = int(count.max())
+            if n == 0:
+                return None
+            order = torch.argsort((~on).to(torch.uint8), dim=1, stable=True)[:, :n]
+            gidx = torch.where(torch.arange(n, device=on.device)[None, :] < count, order, torch.full_like(order, -1))
+        elif tuple(gidx.shape[:1]) != (B,) or gidx.dim() != 2:
+            raise ValueError(f"global_index must be [B, n] = [{B}, n], got {tuple(gidx.shape)}")
+        if gidx.shape[1] == 0:
+            return None
+        if tuple(on.shape) != (B, S):
+            raise ValueError(f"global_attention_mask must be [B, S] = [{B}, {S}], got {tuple(on.shape)}")
+        return attn_ops.global_keys(on), gidx.long()
 
     def decode(self, decoder_input_ids, enc_out, enc_mask=None, caches=None, q_offset=0, cross_kv=None, seg=None,
                cross_seg=None, position_ids=None):
@@ -411,6 +530,9 @@ class BartForConditionalGeneration(nn.Module):
     def enable_context_parallel(self, group=None, enable: bool = True):
         """BART is capped at 1024 learned positions (configuration_bart.py:50), so it has no long-sequence
         config to shard; context parallelism is implemented for the T5 family (models/t5.py)."""
+        if enable and self.config.model_type == "led":
+            raise NotImplementedError("LED: context parallelism is not implemented (its windowed encoder with global "
+                                      "tokens is not sharded); it is implemented for T5 / FLAN-T5 encoders only")
         if enable:
             raise NotImplementedError("context parallelism is implemented for T5 / FLAN-T5 encoders only")
         return self
@@ -425,8 +547,11 @@ class BartForConditionalGeneration(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, labels=None,
                 label_smoothing: float = 0.0, return_logits: bool = False, encoder_outputs=None, segment_ids=None,
-                decoder_segment_ids=None, position_ids=None, decoder_position_ids=None):
+                decoder_segment_ids=None, position_ids=None, decoder_position_ids=None, global_attention_mask=None,
+                global_index=None):
         packed = [segment_ids, decoder_segment_ids, position_ids, decoder_position_ids]
+        if any(t is not None for t in packed) and self.config.model_type == "led":
+            raise NotImplementedError("LED: packed inputs (--pack-sequences, segment ids) are not implemented")
         if any(t is not None for t in packed):
             # packed rows (data/packing.py): several examples per row; the block tables are built once per batch
             if any(t is None for t in packed) or decoder_input_ids is None:
@@ -440,7 +565,8 @@ class BartForConditionalGeneration(nn.Module):
             dec = self.decode(decoder_input_ids, enc, attention_mask, seg=(ds, ds), cross_seg=(ds, es),
                               position_ids=decoder_position_ids)
         else:
-            enc = encoder_outputs if encoder_outputs is not None else self.encode(input_ids, attention_mask)
+            enc = encoder_outputs if encoder_outputs is not None else self.encode(
+                input_ids, attention_mask, global_attention_mask=global_attention_mask, global_index=global_index)
             if decoder_input_ids is None:
                 decoder_input_ids = self.shift_right(labels)
             dec = self.decode(decoder_input_ids, enc, attention_mask)

@@ -19,7 +19,8 @@ from dataclasses import dataclass, field
 
 @dataclass
 class Seq2SeqConfig:
-    model_type: str = "t5"  # "t5" | BART family: "bart" | "mbart" | "pegasus" | "marian" | "m2m_100" | "plbart" | "blenderbot"
+    # "t5" | BART family: "bart" | "mbart" | "pegasus" | "marian" | "m2m_100" | "plbart" | "blenderbot" | "led"
+    model_type: str = "t5"
     # T5 implementation variants: "t5" / "mt5" (same layers), "umt5" (every self-attention layer owns its
     # relative-position bias table: modeling_umt5.py UMT5LayerSelfAttention, has_relative_attention_bias=True),
     # "longt5" (T5 v1.1 layers whose ENCODER self-attention is a sliding window: modeling_longt5.py)
@@ -64,6 +65,12 @@ class Seq2SeqConfig:
     layernorm_embedding: bool = True
     position_embedding: str = "learned"  # "learned" (offset 2) | "learned0" | "sinusoidal" | "sinusoidal_m2m"
     shift_mode: str = "standard"  # "standard" | "mbart"
+    # LED (model_type="led", modeling_led.py): BART layers whose ENCODER self-attention is Longformer's — a sliding
+    # window of attention_window[layer] // 2 keys on either side plus global tokens (models/bart.py).  One even,
+    # positive window per encoder layer (an int is expanded); the encoder's learned positions have a table of their
+    # own size, and max_position_embeddings stays the decoder's (config.json: max_decoder_position_embeddings)
+    attention_window: list | int | None = None
+    max_encoder_position_embeddings: int | None = None
     # special tokens
     pad_token_id: int = 0
     eos_token_id: int = 1
@@ -74,6 +81,19 @@ class Seq2SeqConfig:
     # generation defaults written to generation_config.json
     generation: dict = field(default_factory=dict)
     name: str = ""
+
+    def __post_init__(self):
+        if self.model_type == "led":
+            w = self.attention_window if self.attention_window is not None else 512
+            w = [w] * self.num_layers if isinstance(w, int) else list(w)
+            if len(w) != self.num_layers:
+                raise ValueError(f"LED: attention_window needs one value per encoder layer ({self.num_layers}), got "
+                                 f"{len(w)}")
+            if any((not isinstance(x, int)) or x <= 0 or x % 2 for x in w):
+                raise ValueError(f"LED: every attention_window value must be even and positive, got {w}")
+            self.attention_window = w
+            if self.max_encoder_position_embeddings is None:
+                self.max_encoder_position_embeddings = 16384
 
     @property
     def inner_dim(self) -> int:
@@ -101,11 +121,15 @@ class Seq2SeqConfig:
         return a
 
     def replace(self, **kw) -> "Seq2SeqConfig":
+        """A copy with the fields of ``kw`` set, validated again by ``__post_init__``.  For LED that means
+        ``attention_window`` must fit the copy's ``num_layers``: ``replace(num_layers=2)`` on a 6-layer preset raises
+        unless ``attention_window`` (a list of 2, or an int, which is expanded) is given with it."""
         c = copy.deepcopy(self)
         for k, v in kw.items():
             if not hasattr(c, k):
                 raise AttributeError(k)
             setattr(c, k, v)
+        c.__post_init__()
         return c
 
     # ---------------------------------------------------------------- HF config.json I/O
@@ -142,7 +166,8 @@ class Seq2SeqConfig:
             arch = {"bart": "BartForConditionalGeneration", "mbart": "MBartForConditionalGeneration",
                     "pegasus": "PegasusForConditionalGeneration", "marian": "MarianMTModel",
                     "m2m_100": "M2M100ForConditionalGeneration", "plbart": "PLBartForConditionalGeneration",
-                    "blenderbot": "BlenderbotForConditionalGeneration"}[self.model_type]
+                    "blenderbot": "BlenderbotForConditionalGeneration",
+                    "led": "LEDForConditionalGeneration"}[self.model_type]
             d = {
                 "architectures": [arch],
                 "model_type": self.model_type,
@@ -175,6 +200,11 @@ class Seq2SeqConfig:
             if self.model_type == "marian":
                 d["decoder_vocab_size"] = self.vocab_size
                 d["share_encoder_decoder_embeddings"] = True
+            if self.model_type == "led":  # LEDConfig: two position tables, no scale_embedding
+                del d["max_position_embeddings"], d["scale_embedding"]
+                d.update(attention_window=list(self.attention_window),
+                         max_encoder_position_embeddings=self.max_encoder_position_embeddings,
+                         max_decoder_position_embeddings=self.max_position_embeddings)
         d["torch_dtype"] = "float32"
         return d
 
@@ -209,6 +239,10 @@ class Seq2SeqConfig:
             )
         if mt in _FAMILY:
             fam = {"final_logits_bias": True, **_FAMILY[mt]}
+            if mt == "led":
+                fam.update(attention_window=d.get("attention_window", 512),
+                           max_encoder_position_embeddings=d.get("max_encoder_position_embeddings", 16384))
+                d = {**d, "max_position_embeddings": d.get("max_decoder_position_embeddings", 1024)}
             return cls(
                 model_type=mt, vocab_size=d.get("vocab_size", 50265), d_model=d.get("d_model", 1024),
                 d_kv=d.get("d_model", 1024) // d.get("encoder_attention_heads", 16),
@@ -221,9 +255,9 @@ class Seq2SeqConfig:
                 scale_embedding=d.get("scale_embedding", False),
                 tie_word_embeddings=True, scale_decoder_outputs=False,
                 pad_token_id=d.get("pad_token_id", 1), eos_token_id=_first(d.get("eos_token_id", 2)),
-                bos_token_id=d.get("bos_token_id", 0 if mt in ("bart", "mbart") else None),
+                bos_token_id=d.get("bos_token_id", 0 if mt in ("bart", "mbart", "led") else None),
                 decoder_start_token_id=d.get("decoder_start_token_id") if d.get("decoder_start_token_id") is not None
-                else (d.get("pad_token_id", 1) if mt != "bart" else 2),
+                else (d.get("pad_token_id", 1) if mt not in ("bart", "led") else 2),
                 forced_bos_token_id=d.get("forced_bos_token_id"), forced_eos_token_id=d.get("forced_eos_token_id", 2),
                 **fam,
             )
@@ -268,6 +302,8 @@ _FAMILY = {
     # Blenderbot: pre-LN, learned positions without offset, no embedding LayerNorm (modeling_blenderbot.py)
     "blenderbot": dict(normalize_before=True, layernorm_embedding=False, position_embedding="learned0",
                        shift_mode="standard"),
+    # LED: BART layers, learned positions without offset (modeling_led.py LEDLearnedPositionalEmbedding)
+    "led": dict(normalize_before=False, layernorm_embedding=True, position_embedding="learned0", shift_mode="standard"),
     # M2M100 / NLLB: pre-LN, padding-aware sinusoidal positions (modeling_m2m_100.py), no final_logits_bias
     "m2m_100": dict(normalize_before=True, layernorm_embedding=False, position_embedding="sinusoidal_m2m",
                     shift_mode="standard", final_logits_bias=False),
@@ -275,14 +311,16 @@ _FAMILY = {
 
 
 def _bartlike(mt, name, vocab, d_model, layers, heads, d_ff, act, max_pos, scale_emb, pad, eos, bos, start,
-              dropout=0.1, attn_dropout=0.0, act_dropout=0.0, forced_bos=None, forced_eos=None, dec_layers=None):
+              dropout=0.1, attn_dropout=0.0, act_dropout=0.0, forced_bos=None, forced_eos=None, dec_layers=None,
+              **extra):
     return Seq2SeqConfig(
         model_type=mt, name=name, vocab_size=vocab, d_model=d_model, d_kv=d_model // heads, d_ff=d_ff,
         num_layers=layers, num_decoder_layers=dec_layers or layers, num_heads=heads, feed_forward_proj=act, dropout_rate=dropout,
         attention_dropout=attn_dropout, activation_dropout=act_dropout, layer_norm_epsilon=1e-5,
         scale_decoder_outputs=False, max_position_embeddings=max_pos,
         scale_embedding=scale_emb, pad_token_id=pad, eos_token_id=eos, bos_token_id=bos, decoder_start_token_id=start,
-        forced_bos_token_id=forced_bos, forced_eos_token_id=forced_eos, **{"final_logits_bias": True, **_FAMILY[mt]})
+        forced_bos_token_id=forced_bos, forced_eos_token_id=forced_eos,
+        **{"final_logits_bias": True, **_FAMILY[mt], **extra})
 
 
 def _t5(name, d_model, d_ff, layers, heads, ff="relu", tie=True, vocab=32128, d_kv=64, flavor="t5"):
@@ -352,6 +390,14 @@ PRESETS["blenderbot-400m-distill"] = _bartlike("blenderbot", "blenderbot-400m-di
                                                "gelu", 128, True, pad=0, eos=2, bos=1, start=1, forced_eos=2,
                                                dec_layers=12)
 PRESETS["nllb-200-distilled-600m"] = PRESETS["m2m100_418m"].replace(name="nllb-200-distilled-600m", vocab_size=256206)
+# LED (allenai/led-{base,large}-16384): the BART shapes with a 16384-position windowed encoder.  Written down without
+# the published config.json at hand; a checkpoint directory's own config.json overrides them
+PRESETS["led-base-16384"] = _bartlike("led", "led-base-16384", 50265, 768, 6, 12, 3072, "gelu", 1024, False, pad=1,
+                                      eos=2, bos=0, start=2, attention_window=1024,
+                                      max_encoder_position_embeddings=16384)
+PRESETS["led-large-16384"] = _bartlike("led", "led-large-16384", 50265, 1024, 12, 16, 4096, "gelu", 1024, False, pad=1,
+                                       eos=2, bos=0, start=2, attention_window=1024,
+                                       max_encoder_position_embeddings=16384)
 # tiny configs for CPU tests
 PRESETS["t5-tiny"] = _t5("t5-tiny", 64, 128, 2, 4, vocab=512, d_kv=16)
 PRESETS["t5-tiny-gated"] = _t5("t5-tiny-gated", 64, 96, 2, 4, ff="gated-gelu", tie=False, vocab=512, d_kv=16)
@@ -360,6 +406,9 @@ PRESETS["umt5-tiny"] = _t5("umt5-tiny", 64, 96, 2, 4, ff="gated-gelu", tie=True,
 PRESETS["longt5-tiny"] = _t5("longt5-tiny", 64, 128, 2, 4, vocab=512, d_kv=16, flavor="longt5").replace(local_radius=5)
 PRESETS["longt5-tiny-gated"] = _t5("longt5-tiny-gated", 64, 96, 2, 4, ff="gated-gelu", tie=False, vocab=512, d_kv=16,
                                    flavor="longt5").replace(local_radius=5)
+# window 8 (4 keys on either side): a 23-token input spans several windows
+PRESETS["led-tiny"] = _bartlike("led", "led-tiny", 512, 64, 2, 4, 128, "gelu", 64, False, pad=1, eos=2, bos=0, start=2,
+                                attention_window=8, max_encoder_position_embeddings=256)
 PRESETS["bart-tiny"] = PRESETS["bart-base"].replace(name="bart-tiny", vocab_size=512, d_model=64, d_kv=16, d_ff=128,
                                                     num_layers=2, num_decoder_layers=2, num_heads=4,
                                                     max_position_embeddings=256)

@@ -250,7 +250,7 @@ def _beam_search_device(model, seqs, enc, attention_mask, caches, cross, B, nb, 
 def generate(model, input_ids, attention_mask=None, max_length: int | None = None, num_beams: int | None = None,
              min_length: int | None = None, length_penalty: float | None = None, no_repeat_ngram_size=None,
              early_stopping=None, forced_bos_token_id=None, forced_eos_token_id=None, max_new_tokens=None,
-             **_unused):
+             global_attention_mask=None, global_index=None, **_unused):
     cfg = model.config
     gen = dict(cfg.generation)
     max_length = max_length if max_length is not None else gen.get("max_length", 20)
@@ -270,7 +270,11 @@ def generate(model, input_ids, attention_mask=None, max_length: int | None = Non
     try:
         B = input_ids.shape[0]
         dev = input_ids.device
-        enc = model.encode(input_ids, attention_mask)
+        if global_attention_mask is not None or global_index is not None:  # LED's global tokens (models/bart.py)
+            enc = model.encode(input_ids, attention_mask, global_attention_mask=global_attention_mask,
+                               global_index=global_index)
+        else:
+            enc = model.encode(input_ids, attention_mask)
         nb = max(1, num_beams)
         # cross-attention K/V projected once per batch entry and shared by its nb hypotheses: the decoder's
         # cross-attention runs the beams as nb query rows of one (entry, head) — K/V read once per step, not nb times

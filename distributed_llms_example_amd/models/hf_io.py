@@ -21,6 +21,28 @@ from .t5 import T5ForConditionalGeneration
 
 _FUSED_T5 = {".qkv.weight": [".q.weight", ".k.weight", ".v.weight"], ".kv.weight": [".k.weight", ".v.weight"]}
 _FUSED_BART = {".qkv_proj.": [".q_proj.", ".k_proj.", ".v_proj."], ".kv_proj.": [".k_proj.", ".v_proj."]}
+# LED's encoder self-attention (modeling_led.py LEDEncoderAttention: longformer_self_attn + output), tried first
+_LS = ".self_attn.longformer_self_attn."
+_FUSED_LED = {".self_attn.qkv_proj.": [_LS + "query.", _LS + "key.", _LS + "value."],
+              ".self_attn.kv_global.": [_LS + "key_global.", _LS + "value_global."],
+              ".self_attn.q_global.": [_LS + "query_global."],
+              ".self_attn.out_proj.": [".self_attn.output."]}
+
+
+def _hf_names(cfg, name):
+    """(transformers' parameter names that our ``name`` is the concatenation of, along dim 0) — or None when it maps
+    to itself.  LED: transformers' prefix is ``led.`` and its encoder self-attention has names of its own."""
+    if cfg.model_type == "led":
+        if name.startswith("model."):
+            name = "led." + name[len("model."):]
+        if name.startswith("led.encoder."):
+            for key, parts in _FUSED_LED.items():
+                if key in name:
+                    return [name.replace(key, p) for p in parts]
+    for key, parts in _FUSED_BART.items():
+        if key in name:
+            return [name.replace(key, p) for p in parts]
+    return [name] if cfg.model_type == "led" else None
 
 
 def build_model(cfg_or_name, dtype=torch.float32, device="cpu"):
@@ -51,14 +73,12 @@ def to_hf_state_dict(model) -> dict[str, torch.Tensor]:
             if not done:
                 out[name] = t
         else:
-            done = False
-            for key, parts in _FUSED_BART.items():
-                if key in name:
-                    for part, piece in zip(parts, t.chunk(len(parts), dim=0)):
-                        out[name.replace(key, part)] = piece
-                    done = True
-            if not done:
+            names = _hf_names(cfg, name)
+            if names is None:
                 out[name] = t
+            else:
+                for part, piece in zip(names, t.chunk(len(names), dim=0)):
+                    out[part] = piece
     if cfg.local_encoder and not cfg.tie_word_embeddings:
         # transformers' LongT5 ties encoder / decoder embed_tokens to `shared` only under tie_word_embeddings, so an
         # untied checkpoint carries them (as the published LongT5 checkpoints do); without them it would load random
@@ -89,15 +109,14 @@ def from_hf_state_dict(model, sd: dict[str, torch.Tensor], strict: bool = True):
             elif name == "lm_head.weight" and "shared.weight" in sd:
                 new[name] = sd["shared.weight"]
         else:
-            hit = None
-            for key, parts in _FUSED_BART.items():
-                if key in name:
-                    hit = torch.cat([sd[name.replace(key, p)] for p in parts], 0)
-            if hit is not None:
-                new[name] = hit
-            elif name in sd:
+            names = _hf_names(cfg, name)
+            if names is not None and all(p in sd for p in names):
+                new[name] = torch.cat([sd[p] for p in names], 0) if len(names) > 1 else sd[names[0]]
+            elif names is not None and len(names) > 1:
+                raise KeyError(f"missing keys in checkpoint: {[p for p in names if p not in sd]}")
+            elif names is None and name in sd:
                 new[name] = sd[name]
-            elif name.endswith("shared.weight") and "model.shared.weight" not in sd and "lm_head.weight" in sd:
+            elif name.endswith("shared.weight") and "lm_head.weight" in sd:
                 new[name] = sd["lm_head.weight"]
     # fixed sinusoidal position tables are a function of (max_position_embeddings, d_model): transformers' Marian drops
     # them on save (_keys_to_ignore_on_save) and our module already holds the exact table, so their absence is not an

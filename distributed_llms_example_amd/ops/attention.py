@@ -32,6 +32,15 @@ negative id is padding; a query row with one sees no key: output row 0).  Pass i
 per-64-block tables once per batch instead of once per call, a :class:`Segments` from :func:`segments`.
 csrc/attn_hd.hip (bf16, head dim 64 included) and csrc/attn_f32.hip skip the blocks of other segments; csrc/attn.hip has
 no segments.  They compose with causal, the key-padding mask, the bias and dropout, not with ``window``.
+
+Global keys (Longformer / LED encoder self-attention): with ``window=w`` and ``global_keys`` ``[B, Sk]`` (nonzero =
+global) key ``j`` is visible to query ``i`` when it is valid and ``|j - i| <= w`` or it is global; a global key inside
+the window counts once. Pass the flags or, to build the kernels' block list once per batch instead of once per call, a
+:class:`GlobalKeys` from :func:`global_keys`. The same two kernel files walk the band plus the 64-key blocks that hold
+a global key, O(S·(w + 64·such blocks)); they compose with the key-padding mask, the bias and dropout, need a
+``window`` and do not go with ``causal`` or segments; bf16 at head dim 32 takes the composite (csrc/attn_hd.hip). (The
+rows AT the global positions attend to everything through projections of their own: the model runs them as a second,
+ordinary call — models/bart.py.)
 """
 from __future__ import annotations
 
@@ -136,6 +145,48 @@ def segments(ids) -> "Segments | None":
     return Segments(ids, torch.stack((lo, hi), -1).contiguous())
 
 
+class GlobalKeys:
+    """Global-key flags of a batch as the kernels take them: ``flags`` uint8 ``[B, Sk]`` contiguous (1 = global) and
+    ``blk`` int32 ``[B, 1 + ceil(Sk / 64)]``: per batch row the number of 64-key blocks that hold a global key, then
+    their indices in ascending order (the rest of the row is not read; csrc/attn_params.h).  Built once per batch by
+    :func:`global_keys`, without a host sync."""
+
+    __slots__ = ("flags", "blk")
+
+    def __init__(self, flags: torch.Tensor, blk: torch.Tensor):
+        self.flags, self.blk = flags, blk
+
+
+def global_keys(flags) -> "GlobalKeys | None":
+    """:class:`GlobalKeys` of flags ``[B, Sk]`` (bool or integer, nonzero = global; None and a ``GlobalKeys`` pass
+    through)."""
+    if flags is None or isinstance(flags, GlobalKeys):
+        return flags
+    if flags.dim() != 2 or flags.dtype.is_floating_point or flags.dtype.is_complex:
+        raise ValueError(f"attention: global_keys must be bool or integer [B, Sk], got {flags.dtype} "
+                         f"{tuple(flags.shape)}")
+    on = flags != 0
+    B, S = on.shape
+    hit = torch.nn.functional.pad(on, (0, -S % 64)).view(B, -1, 64).any(-1)  # [B, blocks]
+    order = torch.argsort((~hit).to(torch.uint8), dim=1, stable=True)  # the flagged blocks first, ascending
+    blk = torch.cat((hit.sum(1, keepdim=True), order), 1).to(torch.int32).contiguous()
+    return GlobalKeys(on.to(torch.uint8).contiguous(), blk)
+
+
+def _check_global(gk, B, Sk, window, causal, q_seg) -> None:
+    """Global keys need a window and go with neither causal nor segments; flags are [B, Sk]."""
+    if gk is None:
+        return
+    if q_seg is not None:
+        raise ValueError("attention: global_keys with segments are unsupported")
+    if causal:
+        raise ValueError("attention: global_keys with causal are unsupported")
+    if window is None:
+        raise ValueError("attention: global_keys need a window")
+    if tuple(gk.flags.shape) != (B, Sk):
+        raise ValueError(f"attention: global_keys must be [B, Sk] = [{B}, {Sk}], got {tuple(gk.flags.shape)}")
+
+
 def _check_segments(q_seg, k_seg, B, Sq, Sk, window) -> None:
     """Segments come for both sides or neither, as ids [B, Sq] / [B, Sk], and not with a window."""
     if q_seg is None and k_seg is None:
@@ -149,9 +200,11 @@ def _check_segments(q_seg, k_seg, B, Sq, Sk, window) -> None:
             raise ValueError(f"attention: {name} must be [B, S] = [{B}, {S}], got {tuple(sg.ids.shape)}")
 
 
-def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None, q_seg=None, k_seg=None):
+def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None, q_seg=None, k_seg=None, gk=None):
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
+    gk = global_keys(gk)
+    _check_global(gk, B, Sk, window, causal, q_seg)
     qf = q.float().permute(0, 2, 1, 3)
     kf = k.float().permute(0, 2, 1, 3)
     vf = v.float().permute(0, 2, 1, 3)
@@ -169,7 +222,10 @@ def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None, q_seg=Non
     if window is not None:
         _check_window(window, Sq, Sk, causal)
         dist = torch.arange(Sk, device=q.device)[None, :] - torch.arange(Sq, device=q.device)[:, None]
-        s = s.masked_fill(dist.abs() > window, neg)
+        off = (dist.abs() > window)[None, None]
+        if gk is not None:  # a global key is visible off the band too
+            off = off & (gk.flags.to(q.device) == 0)[:, None, None, :]
+        s = s.masked_fill(off, neg)
     q_seg, k_seg = segments(q_seg), segments(k_seg)
     _check_segments(q_seg, k_seg, B, Sq, Sk, window)
     if q_seg is not None:
@@ -218,13 +274,18 @@ def _seg_args(q_seg, k_seg) -> tuple:
     return () if q_seg is None else (q_seg.ids, k_seg.ids, q_seg.blk, k_seg.blk)
 
 
+def _glob_args(gk) -> dict:
+    """The global-key keyword arguments of attn_hd_* / attn_f32_* (csrc/bind.cpp): flags and block list, or nothing."""
+    return {} if gk is None else {"k_glob": gk.flags, "k_gblk": gk.blk}
+
+
 class _AttnFn(torch.autograd.Function):
     """Inputs are packed the way the projections produce them (``qkv`` = one [B,S,3,H,D] tensor for
     self-attention, ``q`` + ``kv`` [B,Sk,2,H,D] for cross-attention) so backward writes ONE packed
     gradient buffer through strided views instead of three zero-padded slice gradients."""
 
     @staticmethod
-    def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed, window=None, q_seg=None, k_seg=None):
+    def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed, window=None, q_seg=None, k_seg=None, gk=None):
         C = _ext.native()
         q, k, v = _split(mode, a, b, c)
         args = (q, k, v, kpm, lut, float(scale), bool(causal), float(p), int(seed))
@@ -237,10 +298,11 @@ class _AttnFn(torch.autograd.Function):
             o, lse, dmask = C.attn_fwd(*args, sat_lo, sat_hi)
         else:
             o, lse = (C.attn_f32_fwd if q.dtype == torch.float32 else C.attn_hd_fwd)(
-                *args, -1 if window is None else int(window), *_seg_args(q_seg, k_seg))
+                *args, -1 if window is None else int(window), *_seg_args(q_seg, k_seg), **_glob_args(gk))
         ctx.save_for_backward(a, b, c, o, lse, lut, kpm, dmask)
         ctx.cfg = (mode, scale, causal, p, seed, lut is not None and lut.requires_grad, sat_lo, sat_hi, window)
         ctx.seg = (q_seg, k_seg)  # plain int tensors, no graph: kept as they are
+        ctx.gk = gk
         # packed inputs straight from a biased projection (ops/linear.py marks its output): the backward kernels also
         # sum dQ / dK / dV over tokens for that projection's bias gradient (colsum_record).  csrc/attn.hip only (the
         # partials hard-code H * 64) and bias-LUT-free calls only (its column-sum variants exist for those); everything
@@ -291,7 +353,7 @@ class _AttnFn(torch.autograd.Function):
             rq, rk, rv, dlut = C.attn_bwd(*args, dmask, sat_lo, sat_hi, csq, csk, csv)
         else:
             rq, rk, rv, dlut = (C.attn_f32_bwd if q.dtype == torch.float32 else C.attn_hd_bwd)(
-                *args, -1 if window is None else int(window), *_seg_args(*ctx.seg))
+                *args, -1 if window is None else int(window), *_seg_args(*ctx.seg), **_glob_args(ctx.gk))
         if part is not None:  # per-block partials, reduced by the consumer into the bias gradient (ops/gemm.py)
             colsum_record(da, part)
         if pq is not None:
@@ -301,7 +363,7 @@ class _AttnFn(torch.autograd.Function):
         if mode == "sep":
             da, db, dc = rq, rk, rv
         streams.pair_join()  # side-stream weight gradients paired with these VALU-bound kernels (ops/streams.py)
-        return None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None, None, None, None
+        return None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None, None, None, None, None
 
 
 # False: the projections' bias gradients from a separate column reduction of dQKV (tests flip the module attribute)
@@ -346,7 +408,7 @@ def _aligned(t) -> bool:
     return t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
 
 
-def _route(t, *rest, window=None, seg=False):
+def _route(t, *rest, window=None, seg=False, glob=False):
     """Which kernel family serves a call whose q (or packed qkv) is ``t`` — by ops/routing.py ``attention_route``:
 
     * ``"attn.hip"``: bf16, head dim 64, no ``window`` (csrc/attn.hip, the tuned kernels);
@@ -366,6 +428,9 @@ def _route(t, *rest, window=None, seg=False):
     if not bf16 and t.dtype != torch.float32:
         _warn_composite("this dtype", t)
         return None
+    if glob and bf16 and D == 32:  # csrc/attn_hd.hip serves no global keys at head dim 32 (its header says why)
+        _warn_composite("global keys at head dim 32", t)
+        return None
     r = routing.attention_route(D, bf16, window, segments=seg)
     if r == "attn_hd.hip" and not all(_aligned(x) for x in (t,) + rest if x is not None):
         _warn_composite("unaligned rows", t)
@@ -379,32 +444,42 @@ def _route(t, *rest, window=None, seg=False):
     return r
 
 
-def _native(t, *rest, window=None, seg=False) -> bool:
-    return _route(t, *rest, window=window, seg=seg) is not None
+def _native(t, *rest, window=None, seg=False, glob=False) -> bool:
+    return _route(t, *rest, window=window, seg=seg, glob=glob) is not None
 
 
 def _on(sg, t):
     """``sg`` with its tensors on ``t``'s device (a no-op for what :func:`segments` built there)."""
+    if isinstance(sg, GlobalKeys):
+        return sg if sg.flags.device == t.device else GlobalKeys(sg.flags.to(t.device), sg.blk.to(t.device))
     if sg is None or sg.ids.device == t.device:
         return sg
     return Segments(sg.ids.to(t.device), sg.blk.to(t.device))
 
 
+_global_keys = global_keys  # the function, where a parameter of the same name shadows it
+
+
 def attention(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_mask=None, bias_lut=None,
-              dropout_p: float = 0.0, seed: int = 0, window: int | None = None, q_segments=None, k_segments=None):
+              dropout_p: float = 0.0, seed: int = 0, window: int | None = None, q_segments=None, k_segments=None,
+              global_keys=None):
     """Multi-head attention.  q ``[B,Sq,H,D]``, k/v ``[B,Sk,H,D]``; ``key_padding_mask`` bool
     ``[B,Sk]`` (True = attend); ``bias_lut`` from :func:`relative_bias_lut`; ``window``: keys with
     ``|j - i| > window`` are masked (needs ``Sq == Sk`` and ``causal=False``; None: full attention);
     ``q_segments`` / ``k_segments``: ids ``[B,Sq]`` / ``[B,Sk]`` or :class:`Segments` (both or neither, not with
-    ``window``): a key is visible only to the queries of its own non-negative id."""
+    ``window``): a key is visible only to the queries of its own non-negative id; ``global_keys``: flags ``[B,Sk]``
+    (nonzero = global) or :class:`GlobalKeys` (needs ``window``; not with ``causal`` or segments): such a key is
+    visible to every query, inside its window or not."""
     if window is not None:
         _check_window(window, q.shape[1], k.shape[1], causal)
     qs, ks = segments(q_segments), segments(k_segments)
     _check_segments(qs, ks, q.shape[0], q.shape[1], k.shape[1], window)
-    if _native(q, k, v, window=window, seg=qs is not None):
+    gk = _global_keys(global_keys)
+    _check_global(gk, q.shape[0], k.shape[1], window, causal, qs)
+    if _native(q, k, v, window=window, seg=qs is not None, glob=gk is not None):
         return _AttnFn.apply("sep", q, k, v, bias_lut, _prep_kpm(key_padding_mask), scale, causal, dropout_p, seed,
-                             window, _on(qs, q), _on(ks, q))
-    return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed, window, qs, ks)
+                             window, _on(qs, q), _on(ks, q), _on(gk, q))
+    return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed, window, qs, ks, gk)
 
 
 def attention_qkv(qkv, **kw):
@@ -417,10 +492,12 @@ def attention_qkv(qkv, **kw):
         _check_window(window, qkv.shape[1], qkv.shape[1], kw.get("causal", False))
     qs, ks = segments(kw.get("q_segments")), segments(kw.get("k_segments"))
     _check_segments(qs, ks, qkv.shape[0], qkv.shape[1], qkv.shape[1], window)
-    if _native(qkv, window=window, seg=qs is not None):
+    gk = kw["global_keys"] = _global_keys(kw.get("global_keys"))
+    _check_global(gk, qkv.shape[0], qkv.shape[1], window, kw.get("causal", False), qs)
+    if _native(qkv, window=window, seg=qs is not None, glob=gk is not None):
         return _AttnFn.apply("qkv", qkv, None, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
                              kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
-                             window, _on(qs, qkv), _on(ks, qkv))
+                             window, _on(qs, qkv), _on(ks, qkv), _on(gk, qkv))
     return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], **kw)
 
 
@@ -431,8 +508,12 @@ def attention_q_kv(q, kv, **kw):
         _check_window(window, q.shape[1], kv.shape[1], kw.get("causal", False))
     qs, ks = segments(kw.get("q_segments")), segments(kw.get("k_segments"))
     _check_segments(qs, ks, q.shape[0], q.shape[1], kv.shape[1], window)
-    if _native(q, kv, window=window, seg=qs is not None):
+    gk = _global_keys(kw.get("global_keys"))
+    _check_global(gk, q.shape[0], kv.shape[1], window, kw.get("causal", False), qs)
+    if gk is not None:
+        kw = dict(kw, global_keys=gk)
+    if _native(q, kv, window=window, seg=qs is not None, glob=gk is not None):
         return _AttnFn.apply("q_kv", q, kv, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
                              kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
-                             window, _on(qs, q), _on(ks, q))
+                             window, _on(qs, q), _on(ks, q), _on(gk, q))
     return attention(q, kv[:, :, 0], kv[:, :, 1], **kw)

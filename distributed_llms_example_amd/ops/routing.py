@@ -49,6 +49,12 @@ sliding-window attention       bf16 at head dims 32 .. 128 (% 8 == 0), 64 includ
                                Their block walks skip the blocks outside the band
                                (O(S·w)); csrc/attn.hip has no window; anything else: the
                                O(S²) composite, with a one-time warning
+window + global keys           as the window (same route; bf16 head dim 32: composite): the   attn_global_keys.txt
+(LED encoder)                  walks cover the band plus the 64-key blocks that hold a
+                               global key, skipping the rest,
+                               O(S·(w + 64·such blocks)); the rows at the global positions
+                               are an ordinary short-query call (csrc/attn.hip at head dim
+                               64)
 segment-masked attention       as the window: bf16 (head dim 64 included) on                 attn_segments_vs_masked.txt
 (sequence packing)             csrc/attn_hd.hip, fp32 at head dim 64 on csrc/attn_f32.hip;
                                blocks of other segments are skipped by per-block (min,
@@ -171,7 +177,9 @@ def attention_route(head_dim: int, bf16: bool = True, window: int | None = None,
     ``"attn_hd.hip"``, ``"attn_f32.hip"`` or ``"composite"`` — the rule ops/attention.py ``_route`` applies.
     ``window``: the call's sliding window (None: full attention).  csrc/attn.hip has no window, so a windowed bf16
     call at head dim 64 runs csrc/attn_hd.hip's 64-wide instantiation.  ``segments``: the call carries segment ids
-    (sequence packing); csrc/attn.hip has none either, so the same holds.  The fp32 route is unchanged by both."""
+    (sequence packing); csrc/attn.hip has none either, so the same holds.  The fp32 route is unchanged by both.
+    A windowed call with global keys (LED) routes as the windowed call, except bf16 at head dim 32, where
+    csrc/attn_hd.hip serves no global keys and ops/attention.py ``_route`` takes the composite."""
     if head_dim == 64 and (window is None and not segments or not bf16):
         return "attn.hip" if bf16 else ("attn_f32.hip" if get("attn_f32") else "composite")
     if bf16 and 32 <= head_dim <= 128 and head_dim % 8 == 0 and get("attn_hd"):

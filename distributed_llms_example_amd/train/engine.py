@@ -136,6 +136,8 @@ class TrainEngine:
         self.flat.reset_pending()
         # packed rows (data/packing.py) carry their segment and position ids; other batches none of these keys
         packed = {k: batch[k] for k in PACKED_KEYS if k in batch}
+        # LED batches (data/collator.py) carry their global tokens, as a mask and as an index of fixed shape
+        packed.update({k: batch[k] for k in ("global_attention_mask", "global_index") if k in batch})
         return self.model(input_ids=batch["input_ids"], attention_mask=batch.get("attention_mask"),
                           decoder_input_ids=batch.get("decoder_input_ids"), labels=batch["labels"],
                           label_smoothing=self.label_smoothing, **packed)

@@ -39,8 +39,13 @@ def calculate_metric_on_test_ds(model, tokenizer, dataset, metric=None, *, batch
     for art, ref in zip(generate_batch_sized_chunks(texts, batch_size), generate_batch_sized_chunks(refs, batch_size)):
         enc = tokenizer(list(art), max_length=max_source_length, truncation=True, padding="max_length",
                         return_tensors="pt")
-        out = model.generate(enc["input_ids"].to(device), attention_mask=enc["attention_mask"].to(device),
-                             num_beams=num_beams, length_penalty=length_penalty, max_length=max_length)
+        ids = enc["input_ids"].to(device)
+        glob = {}
+        if getattr(getattr(model, "config", None), "model_type", None) == "led":
+            # LED is scored as it is trained (data/collator.py): the first token of every example is global
+            glob = {"global_index": torch.zeros(ids.shape[0], 1, dtype=torch.long, device=ids.device)}
+        out = model.generate(ids, attention_mask=enc["attention_mask"].to(device), num_beams=num_beams,
+                             length_penalty=length_penalty, max_length=max_length, **glob)
         preds = [tokenizer.decode(s, skip_special_tokens=True, clean_up_tokenization_spaces=True) for s in out]
         metric.add_batch(predictions=preds, references=list(ref))
     model.train(was_training)

@@ -199,7 +199,8 @@ class Trainer:
         if len(group) == 1:
             return group[0]
         fill = {"labels": -100, "attention_mask": 0, "decoder_attention_mask": 0, "segment_ids": -1,
-                "decoder_segment_ids": -1, "position_ids": 0, "decoder_position_ids": 0}
+                "decoder_segment_ids": -1, "position_ids": 0, "decoder_position_ids": 0, "global_attention_mask": 0,
+                "global_index": -1}
         out, padded = {}, False
         for k in group[0]:
             ts = [g[k] for g in group]

@@ -6,7 +6,10 @@
 ``--window W --shape B,H,S[,bias,p]`` times forward + backward of three arms interleaved in one process: the windowed
 kernels (csrc/attn_hd.hip, ``window=W``), the same kernels walking every block (``window=S``: masks and skips nothing,
 bitwise the unwindowed call) and what a T5 encoder runs for full attention at that length (csrc/attn.hip at head dim
-64: one call, or above ``attn_chunk_min`` tokens the chunked blocks of parallel/context.py)."""
+64: one call, or above ``attn_chunk_min`` tokens the chunked blocks of parallel/context.py).
+``--window W --global-keys N --shape B,H,S[,bias,p]`` times the windowed call (LED's: scale d^-0.5) forward and
+backward apart, with no global key, with key 0 global and with N global keys spread evenly over the sequence, the arms
+interleaved in one process; per arm the median and the spread (min .. max) over the rounds."""
 import argparse
 import json
 import time
@@ -167,6 +170,61 @@ def vs_window(B, H, S, W, bias, p, D, reps=5, iters=5):
             "speedup_vs_routed_full": med["routed_full"] / med["window"]}
 
 
+def vs_global(B, H, S, W, N, bias, p, D, reps=7, iters=5):
+    """Forward and backward (timed apart) of the windowed call without global keys, with key 0 global and with ``N``
+    global keys at multiples of S // N: warm-up, then ``reps`` rounds of ``iters`` calls per arm, the arms interleaved
+    within every round, device-event times."""
+    dev = "cuda"
+    qkv = torch.randn(B, S, 3, H, D, device=dev, dtype=torch.bfloat16, requires_grad=True)
+    tab = torch.randn(32, H, device=dev, requires_grad=True) if bias else None
+    g = torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16)
+
+    def flags(keys):
+        f = torch.zeros(B, S, dtype=torch.bool, device=dev)
+        f[:, keys] = True
+        return A.global_keys(f)
+
+    spread = [i * (S // N) for i in range(N)]
+    arms = {"window_only": None, "key0_global": flags([0]), f"{N}_global_keys": flags(spread)}
+
+    def fwd(gk):
+        lut = A.relative_bias_lut(tab, S, S, True, 32, 128) if bias else None
+        return A.attention_qkv(qkv, scale=D ** -0.5, bias_lut=lut, dropout_p=p, seed=1, window=W, global_keys=gk)
+
+    def timed(gk):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        tf = tb = 0.0
+        for _ in range(iters):
+            ev[0].record()
+            o = fwd(gk)
+            ev[1].record()
+            o.backward(g)
+            ev[2].record()
+            torch.cuda.synchronize()
+            tf += ev[0].elapsed_time(ev[1])
+            tb += ev[1].elapsed_time(ev[2])
+            qkv.grad = None
+        return tf / iters, tb / iters
+
+    for _ in range(2):
+        for gk in arms.values():
+            timed(gk)
+    ms = {n: {"fwd": [], "bwd": []} for n in arms}
+    for _ in range(reps):
+        for n, gk in arms.items():
+            f, b = timed(gk)
+            ms[n]["fwd"].append(f)
+            ms[n]["bwd"].append(b)
+    stat = lambda t: {"median": round(sorted(t)[len(t) // 2], 4), "min": round(min(t), 4), "max": round(max(t), 4)}
+    nb = (S + 63) // 64
+    band = min(2 * ((W + 63) // 64) + 1, nb)
+    return {"B": B, "H": H, "S": S, "D": D, "window": W, "bias": bias, "p": p,
+            "global_keys": {"key0": [0], "spread": spread},
+            "route": A._route(qkv, window=W),
+            "ms": {n: {k: stat(t) for k, t in v.items()} for n, v in ms.items()},
+            "key_blocks_per_query_block": {"window_only": band, "key0_global": band + 1, f"{N}_global_keys": band + N}}
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -174,8 +232,18 @@ if __name__ == "__main__":
     ap.add_argument("--head-dim", type=int, default=64)
     ap.add_argument("--vs-composite", default="", help="B,H,S,bias,kpm,causal,p: kernel against the composite")
     ap.add_argument("--window", type=int, default=None, help="with --shape: windowed against full attention")
+    ap.add_argument("--global-keys", type=int, default=None,
+                    help="with --window and --shape: the windowed call without, with one and with N global keys")
     ap.add_argument("--shape", default="1,32,4096,1,0.1", help="B,H,S[,bias,p] of the --window run")
     a = ap.parse_args()
+    if a.global_keys is not None:
+        if a.window is None or a.global_keys < 1:
+            ap.error("--global-keys N (N >= 1) goes with --window")
+        f = a.shape.split(",")
+        print(json.dumps(vs_global(int(f[0]), int(f[1]), int(f[2]), a.window, a.global_keys,
+                                   f[3] == "1" if len(f) > 3 else False, float(f[4]) if len(f) > 4 else 0.0,
+                                   a.head_dim)), flush=True)
+        sys.exit(0)
     if a.window is not None:
         f = a.shape.split(",")
         print(json.dumps(vs_window(int(f[0]), int(f[1]), int(f[2]), a.window, f[3] == "1" if len(f) > 3 else True,
