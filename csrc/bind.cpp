@@ -62,6 +62,9 @@ int dllm_ce_merge(const float*, int, long, const float*, const int64_t*, float*,
 int dllm_kv_reorder(void*, const int64_t*, int, int, int, int, int, int, hipStream_t);
 int dllm_beam_topk(const void*, long, int, const float*, const int64_t*, long, int, int, int, int, int, int, int, int,
                    float*, int64_t*, hipStream_t);
+int dllm_sample_list_cap();
+int dllm_sample_step(const void*, long, int, const int64_t*, long, int, int, int, int, int, int, float, float, int, float,
+                     uint32_t, uint32_t, int64_t*, float*, float*, int*, hipStream_t);
 }
 
 namespace {
@@ -1067,6 +1070,36 @@ std::vector<Tensor> beam_topk(const Tensor& logits, const Tensor& beam_scores, c
   return {top_s, top_i};
 }
 
+// One sampling step (csrc/sample.hip): (rc, token [rows] int64, thresholds [rows, 2] fp32).  rc -4: arguments the
+// kernel does not take (the caller runs the composite); thresholds: the top-k one (-inf: off) and the final one — the
+// kept set is x >= it and x > -inf on the processed scores (the tests compare it with the composite's).
+std::tuple<int64_t, Tensor, Tensor> sample_step(const Tensor& logits, const Tensor& seqs, int64_t cur, int64_t ngram,
+                                                int64_t ban_tok, int64_t force_tok, double penalty, double temperature,
+                                                int64_t top_k, double top_p, int64_t seed, int64_t step) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1 &&
+                  (logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat),
+              "sample_step: logits must be a 2-D bf16 / fp32 GPU tensor with unit inner stride");
+  TORCH_CHECK(seqs.is_cuda() && seqs.scalar_type() == at::kLong && seqs.dim() == 2 && seqs.stride(1) == 1 &&
+                  seqs.size(0) == logits.size(0) && cur >= 0 && cur <= seqs.size(1),
+              "sample_step: seqs must be an int64 [rows, L >= cur] GPU tensor with unit inner stride");
+  const int64_t rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(force_tok < V && ban_tok < V, "sample_step: token id out of range");
+  auto tok = at::empty({rows}, seqs.options());
+  auto thr = at::empty({rows, 2}, logits.options().dtype(at::kFloat));
+  if (rows == 0) return {0, tok, thr};
+  if (V >= (1LL << 30) || rows >= (1LL << 30) || top_k >= (1LL << 31) || ngram >= (1LL << 30)) return {-4, tok, thr};
+  const int64_t cap = dllm_sample_list_cap();
+  auto list_v = at::empty({rows, cap}, thr.options());
+  auto list_i = at::empty({rows, cap}, thr.options().dtype(at::kInt));
+  const int rc = dllm_sample_step(logits.data_ptr(), logits.stride(0), logits.scalar_type() == at::kBFloat16,
+                                  seqs.data_ptr<int64_t>(), seqs.stride(0), (int)cur, (int)ngram, (int)ban_tok,
+                                  (int)force_tok, (int)rows, (int)V, (float)penalty, (float)temperature, (int)top_k,
+                                  (float)top_p, (uint32_t)seed, (uint32_t)step, tok.data_ptr<int64_t>(),
+                                  thr.data_ptr<float>(), list_v.data_ptr<float>(), list_i.data_ptr<int>(), stream());
+  if (rc != -4) check_rc(rc, "sample_step");
+  return {rc, tok, thr};
+}
+
 // In-place beam reorder of a [layers * 2, rows, max_len, hd] bf16 cache's live prefix (csrc/beam.hip kv_reorder).
 void kv_reorder(Tensor& cache, const Tensor& src, int64_t nb, int64_t n) {
   TORCH_CHECK(cache.is_cuda() && cache.scalar_type() == at::kBFloat16 && cache.is_contiguous() && cache.dim() == 4,
@@ -1485,6 +1518,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_w4_supported", &gemm_w4_supported);
   m.def("beam_topk", &beam_topk);
   m.def("kv_reorder", &kv_reorder);
+  m.def("sample_step", &sample_step);
   m.def("colsum_partials_acc", &colsum_partials_acc, "out += part.sum(0) for fp32 partial column sums [G, d]");
   m.def("colsum_acc", &colsum_acc, "out += x.sum(0) for a token-major bf16 x (bias gradients)");
   dllm::bind_reducer(m);

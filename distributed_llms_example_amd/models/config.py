@@ -438,7 +438,9 @@ def resolve_config(name_or_path: str) -> Seq2SeqConfig:
             with open(gpath) as f:
                 g = json.load(f)
             keep = {"min_length", "max_length", "length_penalty", "no_repeat_ngram_size", "num_beams",
-                    "early_stopping"}
+                    "early_stopping", "do_sample", "temperature", "top_k", "top_p", "repetition_penalty",
+                    # not implemented: generate() names them in a warning (models/generation.py)
+                    "encoder_no_repeat_ngram_size", "bad_words_ids", "num_return_sequences"}
             cfg.generation = {k: v for k, v in g.items() if k in keep}
         return cfg
     key = (name_or_path or "t5-small").split("/")[-1].lower()

@@ -115,18 +115,107 @@ def _apply_processors_device(logp, seqs, cur_len, min_length, no_repeat_ngram_si
     return logp
 
 
-def _fused_beam_ok(logits, nb: int) -> bool:
+def _penalize(scores, seqs, cur_len: int, penalty: float):
+    """transformers' RepetitionPenaltyLogitsProcessor: every token id in the row's decoder prefix ``seqs[row, :cur]``
+    (start token included) has its score multiplied by ``penalty`` when negative and divided by it otherwise."""
+    if penalty == 1.0:
+        return scores
+    prev = seqs[:, :cur_len]
+    s = scores.gather(1, prev)
+    r = torch.full((), penalty, dtype=scores.dtype, device=scores.device)  # a tensor: a true division on every device
+    return scores.scatter(1, prev, torch.where(s < 0, s * r, s / r))
+
+
+def _warp(scores, temperature: float, top_k: int, top_p: float):
+    """Temperature, top-k, top-p on fp32 scores [N, V] (transformers' warpers, in their order); removed tokens become
+    -inf.  Top-k keeps every tie with the k-th largest value.  Top-p is stated by value: on the softmax of the top-k
+    survivors a token is kept iff the probability mass of the tokens with a STRICTLY larger score is < ``top_p``, so
+    tied scores are kept or dropped together and the maximum always stays (TopPLogitsWarper wherever the scores at
+    the boundary are distinct)."""
+    V = scores.shape[-1]
+    ninf = float("-inf")
+    if temperature != 1.0:  # divided by a tensor: torch turns a division by a Python scalar into a multiplication
+        scores = scores / torch.full((), temperature, dtype=scores.dtype, device=scores.device)
+    if 0 < top_k < V:
+        kth = scores.topk(top_k, dim=-1).values[:, -1:]
+        scores = scores.masked_fill(scores < kth, ninf)
+    if top_p < 1.0:
+        srt = scores.sort(dim=-1, descending=True).values
+        cum = srt.softmax(dim=-1).cumsum(dim=-1)
+        excl = torch.cat([torch.zeros_like(cum[:, :1]), cum[:, :-1]], 1)  # mass at earlier sort positions
+        first = torch.ones_like(srt, dtype=torch.bool)  # first position of each run of equal scores
+        first[:, 1:] = srt[:, 1:] != srt[:, :-1]
+        above = torch.where(first, excl, torch.zeros_like(excl)).cummax(dim=-1).values  # mass of strictly larger scores
+        keep = above < top_p
+        keep[:, 0] = True
+        thr = srt.gather(1, keep.sum(-1, keepdim=True) - 1)
+        scores = scores.masked_fill(scores < thr, ninf)
+    return scores
+
+
+def _sample_scores(logits, seqs, cur, proc, penalty, temperature, top_k, top_p):
+    """The scores one sampling step draws from (torch composite): fp32 logits -> repetition penalty -> n-gram /
+    min-length bans and forced tokens -> temperature, top-k, top-p.  -inf marks a removed token."""
+    min_length, ngram, forced_bos, forced_eos, max_length, eos = proc
+    x = _penalize(logits.float(), seqs, cur, penalty)
+    if x.data_ptr() == logits.data_ptr():
+        x = x.clone()  # the processors write in place
+    x = _apply_processors_device(x, seqs, cur, min_length, ngram, forced_bos, forced_eos, max_length, eos)
+    return _warp(x, temperature, top_k, top_p)
+
+
+def _gumbel_argmax(scores, seed: int, step: int):
+    """Gumbel-max draw over the kept tokens: argmax of ``x - log(-log u)`` with the counter-based uniforms of
+    ops/rng.py ``sample_uniform`` (fp64; ties resolve to the lower index)."""
+    from ..ops import rng
+    N, V = scores.shape
+    dev = scores.device
+    u = rng.sample_uniform(seed, step, N, torch.arange(N, device=dev).view(N, 1),
+                           torch.arange(V, device=dev).view(1, V))
+    return (scores.double() - torch.log(-torch.log(u))).argmax(-1)
+
+
+def _fused_sample_ok(logits) -> bool:
     from .. import _ext
-    return (bool(routing.get("gen_fused_beam")) and nb <= 8 and 2 * nb <= 16 and logits.dim() == 2
+    return (bool(routing.get("gen_fused_sample")) and logits.dim() == 2
             and logits.dtype in (torch.bfloat16, torch.float32) and _ext.use_native(logits))
 
 
-def _beam_candidates(logits, beam_scores, seqs, cur, B, nb, proc):
+def _sample_step(logits, seqs, cur, proc, penalty, temperature, top_k, top_p, seed, step):
+    """One sampling step: the token per row, int64 [N].  On the GPU one csrc/sample.hip launch (penalty, bans, forced
+    token, temperature, top-k and top-p thresholds by radix select, Gumbel-max draw); otherwise, and for arguments the
+    kernel does not take, the torch composite of the same ops."""
+    if _fused_sample_ok(logits):
+        from .. import _ext
+        min_length, ngram, forced_bos, forced_eos, max_length, eos = proc
+        ban = eos if (min_length is not None and cur < min_length and eos is not None) else -1
+        force = -1
+        if forced_bos is not None and cur == 1:
+            force = forced_bos
+        if forced_eos is not None and cur == max_length - 1:
+            force = forced_eos
+        rc, tok, _thr = _ext.native().sample_step(logits, seqs, cur, ngram or 0, ban, force, float(penalty),
+                                                  float(temperature), int(top_k), float(top_p), int(seed), int(step))
+        if rc == 0:
+            return tok
+        if rc != -4:
+            raise RuntimeError(f"sample_step failed: rc={rc}")
+    return _gumbel_argmax(_sample_scores(logits, seqs, cur, proc, penalty, temperature, top_k, top_p), seed, step)
+
+
+def _fused_beam_ok(logits, nb: int, penalty: float = 1.0) -> bool:
+    from .. import _ext
+    return (bool(routing.get("gen_fused_beam")) and penalty == 1.0 and nb <= 8 and 2 * nb <= 16 and logits.dim() == 2
+            and logits.dtype in (torch.bfloat16, torch.float32) and _ext.use_native(logits))
+
+
+def _beam_candidates(logits, beam_scores, seqs, cur, B, nb, proc, penalty: float = 1.0):
     """Top-2·nb candidates over nb·V per batch entry: (scores [B, 2nb], flat indices beam·V + token).  On the GPU one
     csrc/beam.hip launch (log_softmax normaliser + processors + beam score + top-k in one pass over the logits);
-    otherwise the torch composite of the same ops."""
+    otherwise the torch composite of the same ops.  A repetition penalty acts on the log-probabilities, before the
+    bans (transformers' beam search), on the torch path only."""
     min_length, ngram, forced_bos, forced_eos, max_length, eos = proc
-    if _fused_beam_ok(logits, nb):
+    if _fused_beam_ok(logits, nb, penalty):
         from .. import _ext
         ban = eos if (min_length is not None and cur < min_length and eos is not None) else -1
         force = -1
@@ -137,8 +226,8 @@ def _beam_candidates(logits, beam_scores, seqs, cur, B, nb, proc):
         top_s, top_i = _ext.native().beam_topk(logits.contiguous(), beam_scores.reshape(-1).float().contiguous(), seqs,
                                                cur, ngram or 0, ban, force, nb, 2 * nb)
         return top_s, top_i
-    logp = _apply_processors_device(torch.log_softmax(logits.float(), dim=-1), seqs, cur, min_length, ngram,
-                                    forced_bos, forced_eos, max_length, eos)
+    logp = _penalize(torch.log_softmax(logits.float(), dim=-1), seqs, cur, penalty)
+    logp = _apply_processors_device(logp, seqs, cur, min_length, ngram, forced_bos, forced_eos, max_length, eos)
     V = logp.shape[-1]
     return (beam_scores.view(-1, 1) + logp).view(B, nb * V).topk(2 * nb, dim=1)
 
@@ -169,7 +258,7 @@ def _apply_processors(logp, seqs, cur_len, cfg, min_length, no_repeat_ngram_size
 
 
 def _beam_search_device(model, seqs, enc, attention_mask, caches, cross, B, nb, max_length, proc, eos, pad,
-                        length_penalty, early_stopping, check_every):
+                        length_penalty, early_stopping, check_every, penalty: float = 1.0):
     """Beam search with all bookkeeping on the device (transformers BeamSearchScorer semantics): top-2·nb candidates
     over nb·V, eos candidates ranked < nb scored ``sum_logprobs / len**length_penalty`` into a per-batch top-nb of
     finished hypotheses, the first nb non-eos candidates become the next beams, ``is_done`` per batch; the host only
@@ -201,7 +290,7 @@ def _beam_search_device(model, seqs, enc, attention_mask, caches, cross, B, nb, 
         h = model.decode(seqs[:, cur - 1:cur], enc, attention_mask, caches=caches, q_offset=cur - 1, cross_kv=cross)
         logits = model.lm_logits(h[:, -1])
         V = logits.shape[-1]
-        top_s, top_i = _beam_candidates(logits, beam_scores, seqs, cur, B, nb, proc)
+        top_s, top_i = _beam_candidates(logits, beam_scores, seqs, cur, B, nb, proc, penalty)
         src = base + top_i // V
         tok = top_i % V
         is_eos = tok == eos if eos is not None else torch.zeros_like(tok, dtype=torch.bool)
@@ -246,13 +335,57 @@ def _beam_search_device(model, seqs, enc, attention_mask, caches, cross, B, nb, 
     return best[:, :int(best_len.max())]
 
 
+# transformers' generation keys that generate() does not implement, with the value at which each one does nothing
+# (GenerationConfig._get_default_generation_params() of transformers 5.15; None where it sets none).  A key that
+# arrives with another value is named in a one-time warning: the output then differs from transformers'.
+_IGNORED_KEYS = {
+    "encoder_no_repeat_ngram_size": 0, "bad_words_ids": None, "num_return_sequences": 1, "typical_p": 1.0,
+    "min_p": None, "epsilon_cutoff": 0.0, "eta_cutoff": 0.0, "encoder_repetition_penalty": 1.0, "num_beam_groups": 1,
+    "diversity_penalty": 0.0, "penalty_alpha": None, "suppress_tokens": None, "begin_suppress_tokens": None,
+    "sequence_bias": None, "exponential_decay_length_penalty": None, "renormalize_logits": False,
+    "remove_invalid_values": False, "min_new_tokens": None, "guidance_scale": None, "use_cache": True,
+    "output_scores": False, "return_dict_in_generate": False,
+}
+_warned_keys: set = set()
+
+
+def _warn_ignored(given: dict) -> None:
+    names = sorted(k for k, v in given.items() if v is not None and not (k in _IGNORED_KEYS and v == _IGNORED_KEYS[k]))
+    new = [k for k in names if k not in _warned_keys]
+    if not new:
+        return
+    _warned_keys.update(new)
+    from ..utils.logging import get_logger
+    get_logger().warning("generate(): ignoring %s (not implemented: the tokens may differ from transformers')",
+                         ", ".join(f"{k}={given[k]!r}" for k in new))
+
+
 @torch.no_grad()
 def generate(model, input_ids, attention_mask=None, max_length: int | None = None, num_beams: int | None = None,
              min_length: int | None = None, length_penalty: float | None = None, no_repeat_ngram_size=None,
              early_stopping=None, forced_bos_token_id=None, forced_eos_token_id=None, max_new_tokens=None,
-             global_attention_mask=None, global_index=None, **_unused):
+             global_attention_mask=None, global_index=None, do_sample: bool | None = None,
+             temperature: float | None = None, top_k: int | None = None, top_p: float | None = None,
+             repetition_penalty: float | None = None, seed: int | None = None, **_unused):
+    """Greedy search, beam search or multinomial sampling with a KV cache.
+
+    Every option resolves as: the explicit argument, then ``model.config.generation``, then the default of the
+    installed transformers (5.15: ``GenerationConfig()`` leaves every attribute None and ``generate()`` fills them from
+    ``GenerationConfig._get_default_generation_params()``): ``max_length=20, num_beams=1, min_length=0,
+    length_penalty=1.0, no_repeat_ngram_size=0, early_stopping=False, do_sample=False, temperature=1.0, top_k=50,
+    top_p=1.0, repetition_penalty=1.0``.
+
+    ``repetition_penalty`` r != 1: every token id in the row's decoder prefix (start token included) gets
+    ``x * r if x < 0 else x / r`` — on the raw logits in greedy search and sampling, on the log-probabilities in beam
+    search (as transformers), before the n-gram / min-length bans and the forced tokens.  ``do_sample``: after those,
+    temperature (``x / T``), top-k (ties with the k-th value kept; 0 or >= V: off) and top-p by value (kept iff the
+    softmax mass of the strictly larger scores is < ``top_p``; >= 1: off), then a Gumbel-max draw from the
+    counter-based uniforms of ops/rng.py ``sample_uniform(seed, step, rows, row, token)``: the same ``seed`` gives the
+    same tokens (None: the next seed of the default seed stream).  Beam sampling is not implemented.  Keys of
+    transformers' generation config that are not implemented are ignored with a one-time warning that names them."""
     cfg = model.config
     gen = dict(cfg.generation)
+    _warn_ignored({**{k: v for k, v in gen.items() if k in _IGNORED_KEYS}, **_unused})
     max_length = max_length if max_length is not None else gen.get("max_length", 20)
     if max_new_tokens is not None:
         max_length = max_new_tokens + 1
@@ -264,6 +397,24 @@ def generate(model, input_ids, attention_mask=None, max_length: int | None = Non
     early_stopping = early_stopping if early_stopping is not None else gen.get("early_stopping", False)
     forced_bos = forced_bos_token_id if forced_bos_token_id is not None else cfg.forced_bos_token_id
     forced_eos = forced_eos_token_id if forced_eos_token_id is not None else cfg.forced_eos_token_id
+    do_sample = bool(do_sample if do_sample is not None else gen.get("do_sample", False))
+    temperature = float(temperature if temperature is not None else gen.get("temperature", 1.0))
+    top_k = int(top_k if top_k is not None else gen.get("top_k", 50))
+    top_p = float(top_p if top_p is not None else gen.get("top_p", 1.0))
+    repetition_penalty = float(repetition_penalty if repetition_penalty is not None
+                               else gen.get("repetition_penalty", 1.0))
+    if repetition_penalty <= 0:
+        raise ValueError(f"repetition_penalty must be > 0, got {repetition_penalty}")
+    if do_sample:
+        if max(1, num_beams) > 1:
+            raise ValueError("do_sample with num_beams > 1 (beam sampling) is not implemented")
+        if temperature <= 0 or top_k < 0 or not 0 < top_p <= 1:
+            raise ValueError(f"sampling needs temperature > 0, top_k >= 0 and 0 < top_p <= 1; got {temperature}, "
+                             f"{top_k}, {top_p}")
+        if seed is None:
+            from ..ops import rng
+            seed = rng.default_rng().next_seed()
+        seed = int(seed) & 0xFFFFFFFF
     eos, pad, start = cfg.eos_token_id, cfg.pad_token_id, cfg.decoder_start_token_id
     was_training = model.training
     model.eval()
@@ -297,14 +448,21 @@ def generate(model, input_ids, attention_mask=None, max_length: int | None = Non
             return _apply_processors_device(logp, sq, c, min_length, no_repeat_ngram_size, forced_bos, forced_eos,
                                             max_length, eos)
 
-        if nb == 1:  # greedy: device-side done flags, one host check every check_every steps
+        proc = (min_length, no_repeat_ngram_size, forced_bos, forced_eos, max_length, eos)
+        if nb == 1:  # greedy / sampling: device-side done flags, one host check every check_every steps
             done = torch.zeros(B, dtype=torch.bool, device=dev)
             all_done_at = []
             while cur < max_length:
                 h = model.decode(seqs[:, cur - 1:cur], enc, attention_mask, caches=caches, q_offset=cur - 1,
                                  cross_kv=cross)
-                logp = process(torch.log_softmax(model.lm_logits(h[:, -1]).float(), dim=-1), seqs, cur)
-                nxt = logp.argmax(-1)
+                logits = model.lm_logits(h[:, -1])
+                if do_sample:
+                    nxt = _sample_step(logits, seqs, cur, proc, repetition_penalty, temperature, top_k, top_p, seed,
+                                       cur - 1)
+                else:
+                    logp = process(torch.log_softmax(_penalize(logits.float(), seqs, cur, repetition_penalty),
+                                                     dim=-1), seqs, cur)
+                    nxt = logp.argmax(-1)
                 nxt = torch.where(done, torch.full_like(nxt, pad), nxt)
                 seqs[:, cur] = nxt
                 if eos is not None:
@@ -318,9 +476,8 @@ def generate(model, input_ids, attention_mask=None, max_length: int | None = Non
             end = next((i + 2 for i, f in enumerate(flags) if f), cur)
             return seqs[:, :end]
         if not routing.get("gen_host"):
-            proc = (min_length, no_repeat_ngram_size, forced_bos, forced_eos, max_length, eos)
             return _beam_search_device(model, seqs, enc, attention_mask, caches, cross, B, nb, max_length, proc,
-                                       eos, pad, length_penalty, early_stopping, check_every)
+                                       eos, pad, length_penalty, early_stopping, check_every, repetition_penalty)
         # ---------------------------------------------------------------- beam search, host bookkeeping
         # (routing gen_host=1: the original per-step host loop, kept as the A/B oracle of the device version)
         beam_scores = torch.zeros(B, nb, device=dev)
@@ -332,7 +489,8 @@ def generate(model, input_ids, attention_mask=None, max_length: int | None = Non
         while cur < max_length:
             h = model.decode(seqs[:, cur - 1:cur], enc, attention_mask, caches=caches, q_offset=cur - 1,
                              cross_kv=cross)
-            logp = torch.log_softmax(model.lm_logits(h[:, -1]).float(), dim=-1)
+            logp = _penalize(torch.log_softmax(model.lm_logits(h[:, -1]).float(), dim=-1), seqs, cur,
+                             repetition_penalty)
             logp = _apply_processors(logp, seqs[:, :cur], cur, cfg, min_length, no_repeat_ngram_size, forced_bos,
                                      forced_eos, max_length, eos)
             V = logp.shape[-1]

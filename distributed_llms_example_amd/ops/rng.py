@@ -87,6 +87,24 @@ def attention_keep_mask(seed: int, p: float, B: int, H: int, Sq: int, Sk: int, d
     return rowwise_keep_mask(seed, p, B * H * Sq, Sk, device).view(B, H, Sq, Sk)
 
 
+def sample_uniform(seed: int, step: int, rows: int, row: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+    """The uniforms of the sampling draw (models/generation.py, csrc/sample.hip): one per (decode step, row, token),
+    a pure function of the counters, so the kernel, the torch composite and the tests draw the same numbers.
+
+    ``row_key = mix32(seed, step * rows + row)`` (mod 2^32), ``h = mix32(row_key, token)`` and
+    ``u = ((h >> 8) + 0.5) * 2**-24`` as float64: exact, and strictly inside (0, 1).  ``row`` and ``tokens`` are int64
+    tensors that broadcast against each other (``row`` [N, 1] against ``tokens`` [1, V] gives [N, V])."""
+    ctr = (int(step) * int(rows) + row.to(torch.int64)) & _MASK
+    key = mix32(seed, ctr)
+    idx = ((tokens.to(torch.int64) * _C1) & _MASK) ^ key
+    h = idx ^ (idx >> 16)
+    h = (h * _M1) & _MASK
+    h = h ^ (h >> 13)
+    h = (h * _M2) & _MASK
+    h = h ^ (h >> 16)
+    return ((h >> 8).to(torch.float64) + 0.5) * 2.0 ** -24
+
+
 def mix_host(seed: int, idx: int) -> int:
     x = ((idx * _C1) & _MASK) ^ (seed & _MASK)
     x ^= x >> 16

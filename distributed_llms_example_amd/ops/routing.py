@@ -64,6 +64,10 @@ weight gradients, small        side stream for micro-batches <= ``wgrad_stream_m
 micro-batches                  (``wgrad_stream`` = auto | 1 | 0)
 beam search                    fused device-side beam step (``gen_fused_beam``), encoder K/V  r3_eval_beam_fused.jsonl
                                shared by a batch entry's beams (``gen_shared_cross``)
+sampling                       one launch per decode step (``gen_fused_sample``): penalty,    sample_step.txt
+                               bans, temperature, top-k / top-p thresholds by radix select
+                               and the Gumbel-max draw in csrc/sample.hip (0: the torch
+                               composite, a sort of [rows, V] per step)
 gradient reducer               native C++ engine (``reducer`` = native | python), buckets     r5_gloo2_gpu.txt
                                re-laid in gradient-ready order (``rebuild_buckets``)
 HIP-graph DP schedule          overlap: backward segments cut at bucket readiness            r5_gloo2_gpu_final.txt
@@ -113,6 +117,7 @@ DEFAULTS: dict = {
     "wgrad_stream_sites": "",     # comma list of layer roles ("" = the default pairing policy)
     # generation (models/generation.py)
     "gen_fused_beam": 1,
+    "gen_fused_sample": 1,        # sampling step on csrc/sample.hip (0: the torch composite)
     "gen_shared_cross": 1,
     "gen_check_every": 8,
     "gen_host": 0,

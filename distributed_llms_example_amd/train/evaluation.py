@@ -25,8 +25,11 @@ def generate_batch_sized_chunks(items: Sequence, batch_size: int) -> Iterator[Se
 def calculate_metric_on_test_ds(model, tokenizer, dataset, metric=None, *, batch_size: int = 8,
                                 column_text: str = "article", column_summary: str = "highlights",
                                 max_source_length: int = 1024, num_beams: int = 8, length_penalty: float = 0.8,
-                                max_length: int = 128, device=None):
-    """Generate a summary for every row of ``dataset`` (dict of columns or list of dicts) and score it."""
+                                max_length: int = 128, device=None, do_sample=None, temperature=None, top_k=None,
+                                top_p=None, repetition_penalty=None, seed=None):
+    """Generate a summary for every row of ``dataset`` (dict of columns or list of dicts) and score it.  The sampling
+    options and ``repetition_penalty`` go to ``generate()`` as they are (None: the model's generation config);
+    ``do_sample`` needs ``num_beams=1``."""
     if isinstance(dataset, dict):
         texts, refs = list(dataset[column_text]), list(dataset[column_summary])
     else:
@@ -45,7 +48,9 @@ def calculate_metric_on_test_ds(model, tokenizer, dataset, metric=None, *, batch
             # LED is scored as it is trained (data/collator.py): the first token of every example is global
             glob = {"global_index": torch.zeros(ids.shape[0], 1, dtype=torch.long, device=ids.device)}
         out = model.generate(ids, attention_mask=enc["attention_mask"].to(device), num_beams=num_beams,
-                             length_penalty=length_penalty, max_length=max_length, **glob)
+                             length_penalty=length_penalty, max_length=max_length, do_sample=do_sample,
+                             temperature=temperature, top_k=top_k, top_p=top_p,
+                             repetition_penalty=repetition_penalty, seed=seed, **glob)
         preds = [tokenizer.decode(s, skip_special_tokens=True, clean_up_tokenization_spaces=True) for s in out]
         metric.add_batch(predictions=preds, references=list(ref))
     model.train(was_training)

@@ -1,0 +1,186 @@
+"""csrc/sample.hip (one sampling step: penalty, bans, temperature, top-k / top-p thresholds, Gumbel-max draw) against
+the torch composite of models/generation.py on the same inputs, and whole sampled generation on the GPU."""
+import pytest
+import torch
+
+from distributed_llms_example_amd import _ext
+from distributed_llms_example_amd.models import build_model
+from distributed_llms_example_amd.models import generation as gen
+from distributed_llms_example_amd.ops import rng
+
+pytestmark = pytest.mark.gpu
+
+NINF = float("-inf")
+SHAPES = [(1, 97, torch.float32), (3, 32128, torch.bfloat16), (64, 32128, torch.float32), (2, 250112, torch.bfloat16)]
+# (top_k, top_p, temperature, penalty); 6000 survivors do not fit the kernel's survivor list (it walks the row instead)
+OPTIONS = [(0, 1.0, 1.0, 1.0), (1, 1.0, 1.0, 1.0), (5, 1.0, 0.7, 1.3), ("V+3", 0.9, 1.0, 1.0), (0, 0.9, 0.7, 1.3),
+           (0, 0.3, 1.0, 1.3), (0, 1e-6, 0.7, 1.0), (5, 0.9, 1.0, 1.3), (50, 0.9, 0.7, 1.2), (5, 0.3, 0.7, 1.0),
+           (6000, 0.9, 1.0, 1.0), (1, 1e-6, 1.0, 1.3)]
+PLAIN = (None, 0, None, None, 40, 2)  # (min_length, ngram, forced_bos, forced_eos, max_length, eos)
+
+
+def _make(rows, V, dtype, seed, L=40):
+    """Logits with a geometric head (24 tokens whose probabilities fall by ~0.4 per rank, so that a top-p boundary
+    sits between two clearly different masses) over a unit-normal body, and prefixes that hold head tokens."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(rows, V, generator=g)
+    H = min(24, V // 2)
+    seqs = torch.randint(0, V, (rows, L), generator=g)
+    for r in range(rows):
+        head = torch.randperm(V, generator=g)[:H]
+        x[r, head] = 20.0 - 0.9 * torch.arange(H) + 0.3 * torch.rand(H, generator=g)
+        seqs[r, 2], seqs[r, 5] = head[0], head[3]
+    seqs[:, 7] = seqs[:, 2]
+    return x.to(dtype).cuda(), seqs.cuda()
+
+
+def _margin(pre, k, p):
+    """By value, in fp64: the smallest distance between top_p and the mass of the strictly larger scores, over every
+    distinct surviving value but the maximum (kept whatever its mass)."""
+    x = pre.double()
+    if 0 < k < x.shape[1]:
+        x = x.masked_fill(x < x.topk(k, dim=1).values[:, -1:], NINF)
+    srt = x.sort(dim=1, descending=True).values
+    cum = srt.softmax(1).cumsum(1)
+    excl = torch.cat([torch.zeros_like(cum[:, :1]), cum[:, :-1]], 1)
+    first = torch.ones_like(srt, dtype=torch.bool)
+    first[:, 1:] = srt[:, 1:] != srt[:, :-1]
+    above = torch.where(first, excl, torch.zeros_like(excl)).cummax(1).values
+    live = torch.isfinite(srt) & (srt != srt[:, :1])
+    d = (above - p).abs()[live]
+    return float(d.min()) if d.numel() else float("inf")
+
+
+def _inputs(rows, V, dtype, seqs_cur, proc, k, p, T, r):
+    for seed in range(50):
+        logits, seqs = _make(rows, V, dtype, 100 * rows + seed)
+        pre = gen._sample_scores(logits, seqs, seqs_cur, proc, r, T, 0, 1.0)
+        if p >= 1.0 or _margin(pre, k, p) >= 1e-3:
+            return logits, seqs, pre
+    raise AssertionError("no seed with a clear top-p boundary")
+
+
+@pytest.fixture
+def spy(monkeypatch):
+    """Records every csrc/sample.hip launch: (rc, tokens, thresholds)."""
+    calls = []
+    native = _ext.native()
+    orig = native.sample_step
+
+    def wrapped(*a):
+        out = orig(*a)
+        calls.append(out)
+        return out
+
+    monkeypatch.setattr(native, "sample_step", wrapped)
+    return calls
+
+
+def _check_step(logits, seqs, cur, proc, k, p, T, r, seed, step, tok, thr=None, pre=None):
+    """(a) the kernel's kept set is the composite's, (b) the token is kept, (c) its perturbed score is within 1e-4 of
+    the row's maximum over the kept set, evaluated in fp64 from the same uniforms."""
+    if pre is None:
+        pre = gen._sample_scores(logits, seqs, cur, proc, r, T, 0, 1.0)
+    kept = torch.isfinite(gen._sample_scores(logits, seqs, cur, proc, r, T, k, p))
+    if thr is not None:
+        got = (pre >= thr[:, 1:2]) & torch.isfinite(pre)
+        assert torch.equal(got, kept), (got.sum(1), kept.sum(1), thr)
+    assert kept.gather(1, tok.view(-1, 1)).all()
+    N, V = pre.shape
+    u = rng.sample_uniform(seed, step, N, torch.arange(N, device="cuda").view(N, 1),
+                           torch.arange(V, device="cuda").view(1, V))
+    pert = (pre.double() - torch.log(-torch.log(u))).masked_fill(~kept, NINF)
+    best = pert.max(1).values
+    mine = pert.gather(1, tok.view(-1, 1)).view(-1)
+    assert (mine >= best - 1e-4).all(), (best - mine).max()
+
+
+@pytest.mark.parametrize("rows,V,dtype", SHAPES)
+def test_sample_step_matches_composite(rows, V, dtype, spy):
+    cur = 17
+    for n, (k, p, T, r) in enumerate(OPTIONS):
+        k = V + 3 if k == "V+3" else k
+        logits, seqs, pre = _inputs(rows, V, dtype, cur, PLAIN, k, p, T, r)
+        assert p >= 1.0 or _margin(pre, k, p) >= 1e-3
+        seed, step = 1234 + n, 5 + n
+        tok = gen._sample_step(logits, seqs, cur, PLAIN, r, T, k, p, seed, step)
+        assert len(spy) == n + 1 and spy[-1][0] == 0  # the kernel ran and took the arguments
+        assert tok.dtype == torch.long and torch.equal(tok, spy[-1][1])
+        _check_step(logits, seqs, cur, PLAIN, k, p, T, r, seed, step, tok, spy[-1][2], pre)
+
+
+@pytest.mark.parametrize("rows,V,dtype", SHAPES[:2])
+@pytest.mark.parametrize("case", ["ngram", "minlen", "force_bos", "force_eos", "only_one"])
+def test_sample_step_processors(rows, V, dtype, case, spy):
+    L, eos = 40, 2
+    cur = 1 if case == "force_bos" else (L - 1 if case == "force_eos" else 17)
+    k, p, T, r = 50, 0.9, 0.7, 1.2
+    proc = (cur + 1 if case == "minlen" else None, 3 if case in ("ngram", "force_eos") else 0,
+            0 if case == "force_bos" else None, eos if case == "force_eos" else None, L, eos)
+    logits, seqs = _make(rows, V, dtype, 7)
+    seqs = seqs % 12  # small token alphabet so earlier n-grams repeat and bans actually fire
+    if case == "minlen":
+        logits[:, eos] = 100.0  # would win every draw without the ban
+    if case == "ngram":  # make a banned completion the best token of every row
+        seqs[:, 3:5] = seqs[:, cur - 2:cur]
+        seqs[:, 5] = 7
+        logits[:, 7] = 50.0
+    if case == "only_one":
+        only = torch.tensor([(31 * i + 5) % V for i in range(rows)], device="cuda")
+        keep = logits.gather(1, only.view(-1, 1))
+        logits = torch.full_like(logits, NINF).scatter(1, only.view(-1, 1), keep)
+    tok = gen._sample_step(logits, seqs, cur, proc, r, T, k, p, 77, cur - 1)
+    assert len(spy) == 1 and spy[0][0] == 0
+    if case == "force_bos":
+        assert (tok == 0).all()
+    elif case == "force_eos":
+        assert (tok == eos).all()
+    else:
+        _check_step(logits, seqs, cur, proc, k, p, T, r, 77, cur - 1, tok, spy[0][2])
+        if case == "ngram":
+            assert not (tok == 7).any()
+        if case == "minlen":
+            assert not (tok == eos).any()
+        if case == "only_one":
+            assert torch.equal(tok, only)
+
+
+def _model(name):
+    torch.manual_seed(0)
+    m = build_model(name).cuda().to(torch.bfloat16).eval()
+    ids = torch.randint(4, m.config.vocab_size, (3, 12), generator=torch.Generator().manual_seed(1)).cuda()
+    return m, ids
+
+
+@pytest.mark.parametrize("name", ["t5-tiny", "bart-tiny"])
+def test_generate_top_k_1_is_greedy(name, spy):
+    m, ids = _model(name)
+    greedy = m.generate(ids, max_length=16)
+    got = m.generate(ids, max_length=16, do_sample=True, top_k=1, seed=3)
+    assert spy and all(c[0] == 0 for c in spy)
+    assert torch.equal(greedy, got), (greedy, got)
+
+
+@pytest.mark.parametrize("name", ["t5-tiny", "bart-tiny"])
+def test_generate_sampled_steps_fused_and_composite(name, spy, monkeypatch):
+    """Every step of a sampled generate() draws a kept token whose perturbed score is the maximum to 1e-4, with the
+    kernel and with the composite (whole sequences may differ: a near-tie may resolve differently)."""
+    m, ids = _model(name)
+    orig = gen._sample_step
+    steps = []
+
+    def checked(logits, seqs, cur, proc, penalty, temperature, top_k, top_p, seed, step):
+        tok = orig(logits, seqs, cur, proc, penalty, temperature, top_k, top_p, seed, step)
+        _check_step(logits, seqs, cur, proc, top_k, top_p, temperature, penalty, seed, step, tok)
+        steps.append(step)
+        return tok
+
+    monkeypatch.setattr(gen, "_sample_step", checked)
+    launches = []
+    for flag in ("0", "1"):
+        monkeypatch.setenv("DLLM_ROUTE", f"gen_fused_sample={flag}")
+        out = m.generate(ids, max_length=16, do_sample=True, top_k=50, top_p=0.9, temperature=0.7,
+                         repetition_penalty=1.2, no_repeat_ngram_size=2, min_length=4, seed=11)
+        assert out.shape[0] == 3 and out.shape[1] <= 16
+        launches.append(len(spy))
+    assert launches[0] == 0 and launches[1] >= 8 and len(steps) >= 16
