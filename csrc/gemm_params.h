@@ -33,8 +33,13 @@ struct GemmW4Params {
   int grp;         // tile order: groups of grp 256-row blocks, column-major inside a group; 0 = row-major
   int accumulate;  // 1: C += A . B (bf16 read-modify-write), 0: C = A . B
   // epilogue (csrc/gemm_w4.hip W4_EPI_*): ReLU + dropout forward writing the keep-and-positive bit mask, or the input
-  // gradient through that mask.  mask: 8 words per thread per 256x256 tile (tile-major, thread-minor), bit 4 j + r of
-  // word i <-> accumulator acc[i][j][r]
+  // gradient through that mask.  mask: 8 words per thread per 256x256 tile (tile-major, thread-minor): word
+  // ((tile_row * tn + tile_col) * 256 + tid) * 8 + i.  Thread tid = 64 w + 16 qd + rl (wave w = 2 wm + wn covers the
+  // tile's rows [128 wm, +128) x columns [128 wn, +128)); word i holds tile row 128 wm + 16 i + rl, and the element at
+  // tile column 128 wn + 16 j + 4 qd + r (j < 8, r < 4) is bit 2 j + (r >> 1) + 16 (r & 1) (csrc/gemm_w4.hip mbit: even
+  // columns in the low half word, odd columns in the high one).  After the forward, bits of columns >= N are 0 and bits
+  // of rows >= M are unspecified (relu(bias) and a keep decision of a row that does not exist); every word of every
+  // tile is written, words past the last tile are not touched.
   uint32_t* mask;
   float p, scale;  // dropout probability, 1 / (1 - p)
   uint32_t seed, thr;
@@ -93,6 +98,10 @@ struct GemmFusedParams {
   float scale; // 1 / (1 - p), or 1
   uint32_t seed, thr;
   int grp;     // tile order (gemm_pp_kernel): groups of grp 256-row blocks, column-major inside a group; 0 = row-major
-  uint32_t* mask;  // ReLU derivative bits (ping-pong kernel): written by epi 1 when non-null, read by epi 7; M*N/32 words
+  // ReLU derivative bits (ping-pong kernel): written by epi 1 when non-null, read by epi 7; M*N/32 words: word
+  // ((tile_row * tn + tile_col) * 512 + tid) * 4 + (i >> 1).  Thread tid = 64 w + 16 q + rl (wave w = 4 wm + wn covers
+  // the tile's rows [128 wm, +128) x columns [64 wn, +64)); the element at tile row 128 wm + 16 i + rl (i < 8), tile
+  // column 64 wn + 16 j + 4 q + r (j < 4, r < 4) is bit 16 (i & 1) + 4 j + r of that word
+  uint32_t* mask;
   float* colsum;   // optional (ping-pong kernel, epi 4 / 6): [M / 128][N] per-128-row column sums of the output C
 };

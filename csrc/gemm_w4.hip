@@ -693,7 +693,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_w4_kernel(GemmW4Params P) {
       for (int j = 0; j < 8; ++j) csum[j] = f32x4{0.f, 0.f, 0.f, 0.f};
       const int mr = wm * 128 + 16 * (qd & 1) + rl;  // tile-local row of ii = 0
       const int nc = wn * 128 + 8 * (qd >> 1);       // tile-local column of j = 0
-      uint32_t mw[8];  // mask words: bit 4 j + r of word i <-> acc[i][j][r]
+      uint32_t mw[8];  // mask words: bit mbit(j, r) of word i <-> acc[i][j][r] (layout: gemm_params.h)
       if constexpr (EPI == W4_EPI_DRELU_M) {
         // the tile's mask DMA is older than every DMA of the last k-tile: at most those 16 are still outstanding
         asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
@@ -728,14 +728,6 @@ __global__ __launch_bounds__(NT, 1) void gemm_w4_kernel(GemmW4Params P) {
         return f32x4{bf2f((uint16_t)(bv[j].x & 0xFFFFu)), bf2f((uint16_t)(bv[j].x >> 16)),
                      bf2f((uint16_t)(bv[j].y & 0xFFFFu)), bf2f((uint16_t)(bv[j].y >> 16))};
       };
-      auto add_c = [&](u32x4 o, uint32_t off) {  // ACC: o + C, in fp32, rounded once
-        const u32x4 c = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(srdC, off, 0, 0));
-        auto add2 = [](uint32_t u, uint32_t v) {
-          return pk2(bf2f((uint16_t)(u & 0xFFFFu)) + bf2f((uint16_t)(v & 0xFFFFu)),
-                     bf2f((uint16_t)(u >> 16)) + bf2f((uint16_t)(v >> 16)));
-        };
-        return u32x4{add2(o.x, c.x), add2(o.y, c.y), add2(o.z, c.z), add2(o.w, c.w)};
-      };
       const int rowL = 16 * (qd & 1) + rl;                       // staging row written by this lane
       // CEB: this lane's 8 rows (ii, half): lse, label column relative to the tile's column 0, row gradient scale
       float ce_lse[8], ce_g[8];
@@ -766,6 +758,20 @@ __global__ __launch_bounds__(NT, 1) void gemm_w4_kernel(GemmW4Params P) {
             rwy = rw_gbase(mix32(seed, rx + 16u), kp0);
           }
         }
+        // ACC: C at this lane's accumulator positions (rows ii, ii + 16), added to the fp32 accumulators BEFORE the
+        // store's rounding: out = bf16(acc + C), one rounding (adding to the packed bf16 product rounded twice)
+        u32x2 cin[8][2];
+        if constexpr (ACC) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int col = n0 + wn * 128 + 16 * j + 4 * qd;
+            const int row = wm * 128 + 32 * ii + rl;  // tile-local; rows >= M fall out of srdC's range and read 0
+            const uint32_t o0 = col < P.N ? (uint32_t)(row * P.ldc + col) * 2u : kOOB;
+            const uint32_t o1 = col < P.N ? (uint32_t)((row + 16) * P.ldc + col) * 2u : kOOB;
+            cin[j][0] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(srdC, o0, 0, 0));
+            cin[j][1] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(srdC, o1, 0, 0));
+          }
+        }
         u32x2 ga[8][2];  // GELU backward: the saved derivative at this lane's accumulator positions (rows ii, ii + 16)
         if constexpr (EPI == W4_EPI_DGELU) {
 #pragma unroll
@@ -788,6 +794,14 @@ __global__ __launch_bounds__(NT, 1) void gemm_w4_kernel(GemmW4Params P) {
             const f32x4 b4 = bias4(j);
             xv += b4;
             yv += b4;
+          }
+          if constexpr (ACC) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const uint32_t wx = cin[j][0][r >> 1], wy = cin[j][1][r >> 1];
+              xv[r] += bf2f((uint16_t)((r & 1) ? (wx >> 16) : (wx & 0xFFFFu)));
+              yv[r] += bf2f((uint16_t)((r & 1) ? (wy >> 16) : (wy & 0xFFFFu)));
+            }
           }
           if constexpr (EPI == W4_EPI_RELU) {
             // scaled in fp32 (rounded once, as before); ReLU, dropout and the mask bits follow on the packed pairs
@@ -895,7 +909,6 @@ __global__ __launch_bounds__(NT, 1) void gemm_w4_kernel(GemmW4Params P) {
           } else {
             const int nl = nc + 16 * j;
             const uint32_t off = n0 + nl < P.N ? (uint32_t)((mr + 32 * ii) * P.ldc + n0 + nl) * 2u : kOOB;
-            if constexpr (ACC) o = add_c(o, off);
             if constexpr ((RS & 128) == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), srdC, off, 0, 0);
           }
           // bound the live ranges
@@ -911,7 +924,6 @@ __global__ __launch_bounds__(NT, 1) void gemm_w4_kernel(GemmW4Params P) {
             u32x4 o = *reinterpret_cast<const u32x4*>(scr + r * 256 + ((c ^ (r & 15)) << 4));
             const int col = wn * 128 + 8 * c;
             const uint32_t off = n0 + col < P.N ? (uint32_t)((wm * 128 + 32 * ii + r) * P.ldc + n0 + col) * 2u : kOOB;
-            if constexpr (ACC) o = add_c(o, off);
             if constexpr ((RS & 128) == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), srdC, off, 0, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -936,7 +948,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_w4_kernel(GemmW4Params P) {
             csum[j][r] = v;
           }
         }
-        if (rl == 0) {
+        if (rl == 0 && m0 + wm * 128 < P.M) {  // M % 256 == 128: the last tile's lower waves have no partial row
           float* cp = P.colsum + (long)(m0 / 128 + wm) * P.N + n0 + wn * 128 + 4 * qd;
 #pragma unroll
           for (int j = 0; j < 8; ++j)

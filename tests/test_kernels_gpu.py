@@ -486,9 +486,11 @@ def test_gemm_pp_tile_order_groups(grp, monkeypatch):
 @pytest.mark.parametrize("K", [128, 192, 768])
 @pytest.mark.parametrize("kmajor", [False, True])
 def test_gemm_pp_persistent(K, kmajor):
-    """Persistent ping-pong kernel (variant 9: one workgroup per CU walking >= 2 tiles, the DMA stream running across
-    tile boundaries, epilogue stores queued between units): 528 tiles (uneven per CU), relu+dropout forward (NT) or
-    d-relu backward (k-major B), vs the fp32 reference."""
+    """Variant 9 at 528 tiles.  kmajor=False: the relu+dropout forward (NT, epilogue 1) runs the persistent ping-pong
+    kernel (one workgroup per CU walking 2-3 tiles, the DMA stream running across tile boundaries, epilogue stores
+    queued between units).  kmajor=True: the d-relu backward from the saved activation (k-major B, epilogue 3) loads
+    aux in its epilogue, is not in launch_pp's persistent list and runs ONE TILE PER WORKGROUP whatever the variant; the
+    persistent backward is epilogue 7 (tests/test_gemm_exact_gpu.py test_pp_persistent).  Both vs the fp32 reference."""
     from distributed_llms_example_amd.ops.rng import keep_mask
     torch.manual_seed(4)
     M, N, p = 8448, 4096, 0.1
