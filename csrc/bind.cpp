@@ -57,6 +57,15 @@ int dllm_embed_bwd(const int64_t*, const int64_t*, const void*, long, long, int,
                    hipStream_t);
 int dllm_colsum_acc(const void*, long, long, int, float*, void*, int, hipStream_t);
 int dllm_colsum_partials_acc(const float*, void*, int, int, int, hipStream_t);
+int dllm_set_seed_step_lora(const uint32_t*);
+int dllm_lora_wgrad_rows();
+int dllm_lora_wgrad_max_splits();
+int dllm_lora_wgrad_split_rows(long);
+int dllm_lora_down(const void*, long, const void*, void*, int, int, int, float, float, uint32_t, uint32_t, hipStream_t);
+int dllm_lora_up(const void*, int, const void*, int, void*, long, int, int, int, float, float, uint32_t, uint32_t,
+                 hipStream_t);
+int dllm_lora_wgrad(const void*, long, int, const void*, int, float*, int, int, int, void*, int, float, int, float,
+                    uint32_t, uint32_t, hipStream_t);
 int dllm_ce_merge(const float*, int, long, const float*, const int64_t*, float*, float*, long, int, float, long,
                   hipStream_t);
 int dllm_kv_reorder(void*, const int64_t*, int, int, int, int, int, int, hipStream_t);
@@ -1422,6 +1431,89 @@ void embed_bwd(const Tensor& ids_sorted, const Tensor& perm, const Tensor& dy, T
            "embed_bwd");
 }
 
+// ------------------------------------------------------------------------------------------- LoRA (csrc/lora.hip)
+// A bf16 GPU matrix whose rows are 16-B aligned vectors of a multiple of 8 columns (unit inner stride, row stride a
+// multiple of 8): a contiguous tensor or a column slice of one.
+void check_lora_wide(const Tensor& t, const char* fn, const char* n) {
+  TORCH_CHECK(t.is_cuda(), fn, ": ", n, " must be a GPU tensor");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, fn, ": ", n, " must be bf16");
+  TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1, fn, ": ", n, " must be 2-D with unit inner stride");
+  TORCH_CHECK(t.size(1) % 8 == 0 && t.stride(0) % 8 == 0, fn, ": ", n,
+              " needs a column count and a row stride that are multiples of 8, got ", t.size(1), " / ", t.stride(0));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, fn, ": ", n, " must be 16-byte aligned");
+  TORCH_CHECK(t.size(0) < INT_MAX && t.size(1) < INT_MAX, fn, ": ", n, " too large");
+}
+
+// A contiguous bf16 GPU matrix with the rank on one side (1 .. 64)
+void check_lora_small(const Tensor& t, int64_t r, const char* fn, const char* n) {
+  TORCH_CHECK(t.is_cuda(), fn, ": ", n, " must be a GPU tensor");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, fn, ": ", n, " must be bf16");
+  TORCH_CHECK(t.dim() == 2 && t.is_contiguous(), fn, ": ", n, " must be a contiguous matrix");
+  TORCH_CHECK(r >= 1 && r <= 64, fn, ": the rank must be 1 .. 64, got ", r);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, fn, ": ", n, " must be 16-byte aligned");
+}
+
+// t[N, r] = bf16(alpha * (keep . x) A^T): x [N, K] (rows may be strided: a column slice), A [r, K]
+Tensor lora_down(const Tensor& x, const Tensor& A, double alpha, double p, int64_t seed, int64_t row0) {
+  check_lora_wide(x, "lora_down", "x");
+  check_lora_small(A, A.dim() == 2 ? A.size(0) : 0, "lora_down", "A");
+  TORCH_CHECK(A.size(1) == x.size(1), "lora_down: A must be [r, K] with x's K, got ", A.sizes(), " for x ", x.sizes());
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "lora_down: p must be in [0, 1)");
+  const int N = x.size(0), K = x.size(1), r = A.size(0);
+  auto t = at::empty({N, r}, x.options());
+  check_rc(dllm_lora_down(x.data_ptr(), x.stride(0), A.data_ptr(), t.data_ptr(), N, K, r, (float)alpha, (float)p,
+                          (uint32_t)seed, (uint32_t)row0, stream()),
+           "lora_down");
+  return t;
+}
+
+// y[:, c0:c0+n] += alpha * (keep .) (t M): t [N, r]; M [n, r], or [r, n] with kmajor; y [N, ld] in place
+void lora_up(const Tensor& t, const Tensor& M, bool kmajor, double alpha, Tensor& y, int64_t c0, int64_t n, double p,
+             int64_t seed, int64_t row0) {
+  check_lora_wide(y, "lora_up", "y");
+  check_lora_small(t, t.dim() == 2 ? t.size(1) : 0, "lora_up", "t");
+  const int64_t r = t.size(1);
+  check_lora_small(M, r, "lora_up", "M");
+  TORCH_CHECK(t.size(0) == y.size(0), "lora_up: t and y need the same rows");
+  TORCH_CHECK(n > 0 && n % 8 == 0 && c0 >= 0 && c0 % 8 == 0 && c0 + n <= y.size(1),
+              "lora_up: the slice [c0, c0 + n) must lie inside y's columns with c0 and n multiples of 8, got c0 ", c0,
+              " n ", n, " of ", y.size(1));
+  TORCH_CHECK(kmajor ? (M.size(0) == r && M.size(1) == n) : (M.size(0) == n && M.size(1) == r),
+              "lora_up: M must be ", kmajor ? "[r, n]" : "[n, r]", ", got ", M.sizes());
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "lora_up: p must be in [0, 1)");
+  check_rc(dllm_lora_up(t.data_ptr(), (int)r, M.data_ptr(), kmajor ? 1 : 0, y.data_ptr(), y.stride(0), (int)c0, (int)n,
+                        (int)y.size(0), (float)alpha, (float)p, (uint32_t)seed, (uint32_t)row0, stream()),
+           "lora_up");
+}
+
+std::vector<int64_t> lora_wgrad_splits(int64_t N) {
+  const int64_t rows = dllm_lora_wgrad_split_rows(N);
+  return {N > 0 ? (N + rows - 1) / rows : 0, rows};
+}
+
+// G (+)= alpha * (keep . W)^T S over tokens: W [N, wc] (rows may be strided), S [N, r]; G [wc, r] (wide_major) or
+// [r, wc], fp32 or bf16, contiguous.  Fixed token splits summed in order: bitwise reproducible.
+void lora_wgrad(const Tensor& W, const Tensor& S, double alpha, Tensor& G, bool wide_major, bool beta, double p,
+                int64_t seed, int64_t row0) {
+  check_lora_wide(W, "lora_wgrad", "W");
+  check_lora_small(S, S.dim() == 2 ? S.size(1) : 0, "lora_wgrad", "S");
+  TORCH_CHECK(S.size(0) == W.size(0), "lora_wgrad: W and S need the same rows");
+  const int64_t N = W.size(0), wc = W.size(1), r = S.size(1);
+  TORCH_CHECK(G.is_cuda() && G.dim() == 2 && G.is_contiguous() &&
+                  (G.scalar_type() == at::kFloat || G.scalar_type() == at::kBFloat16),
+              "lora_wgrad: G must be a contiguous fp32 / bf16 GPU matrix");
+  TORCH_CHECK(wide_major ? (G.size(0) == wc && G.size(1) == r) : (G.size(0) == r && G.size(1) == wc),
+              "lora_wgrad: G must be ", wide_major ? "[wc, r]" : "[r, wc]", ", got ", G.sizes());
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "lora_wgrad: p must be in [0, 1)");
+  if (N == 0) return;
+  const auto sp = lora_wgrad_splits(N);
+  auto part = at::empty({sp[0], wc * r}, W.options().dtype(at::kFloat));
+  check_rc(dllm_lora_wgrad(W.data_ptr(), W.stride(0), (int)wc, S.data_ptr(), (int)r, part.data_ptr<float>(), (int)N,
+                           (int)sp[1], wide_major ? 1 : 0, G.data_ptr(), G.scalar_type() == at::kBFloat16 ? 1 : 0,
+                           (float)alpha, beta ? 1 : 0, (float)p, (uint32_t)seed, (uint32_t)row0, stream()),
+           "lora_wgrad");
+}
+
 // Device step counter for graph-replayable dropout (csrc/common.h DLLM_SEED_STEP_TU): every dropout kernel mixes
 // *step into its site seed; None turns it off (site seeds used as given).  The tensor must outlive its use.
 void set_seed_step(const optional<Tensor>& step) {
@@ -1438,6 +1530,7 @@ void set_seed_step(const optional<Tensor>& step) {
   check_rc(dllm_set_seed_step_attn_hd(p), "set_seed_step(attn_hd)");
   check_rc(dllm_set_seed_step_gemm_fused(p), "set_seed_step(gemm_fused)");
   check_rc(dllm_set_seed_step_gemm_w4(p), "set_seed_step(gemm_w4)");
+  check_rc(dllm_set_seed_step_lora(p), "set_seed_step(lora)");
 }
 
 namespace dllm {
@@ -1521,6 +1614,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_step", &sample_step);
   m.def("colsum_partials_acc", &colsum_partials_acc, "out += part.sum(0) for fp32 partial column sums [G, d]");
   m.def("colsum_acc", &colsum_acc, "out += x.sum(0) for a token-major bf16 x (bias gradients)");
+  m.def("lora_down", &lora_down, "t = bf16(alpha * (keep . x) A^T) (csrc/lora.hip)", py::arg("x"), py::arg("A"),
+        py::arg("alpha") = 1.0, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("row0") = 0);
+  m.def("lora_up", &lora_up, "y[:, c0:c0+n] += alpha * (keep .) (t M), in place", py::arg("t"), py::arg("M"),
+        py::arg("kmajor"), py::arg("alpha"), py::arg("y"), py::arg("c0"), py::arg("n"), py::arg("p") = 0.0,
+        py::arg("seed") = 0, py::arg("row0") = 0);
+  m.def("lora_wgrad", &lora_wgrad, "G (+)= alpha * (keep . W)^T S over tokens, fixed splits summed in order",
+        py::arg("W"), py::arg("S"), py::arg("alpha"), py::arg("G"), py::arg("wide_major"), py::arg("beta") = true,
+        py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("row0") = 0);
+  m.def("lora_wgrad_splits", &lora_wgrad_splits, "(splits, tokens per split) of lora_wgrad for N tokens");
+  m.attr("lora_wgrad_rows") = dllm_lora_wgrad_rows();
+  m.attr("lora_wgrad_max_splits") = dllm_lora_wgrad_max_splits();
   dllm::bind_reducer(m);
   m.attr("arch") = "gfx950";
 }

@@ -74,7 +74,31 @@ def base_parser(description: str, defaults: dict | None = None) -> argparse.Argu
                    help="shard the encoder sequence over groups of N ranks (ring attention; T5 family)")
     g.add_argument("--model-overrides", type=str, default=None,
                    help="comma list key=value applied to the model config (e.g. num_layers=2)")
+    g.add_argument("--lora-r", type=int, default=0,
+                   help="LoRA rank (1 .. 64): freeze the model and train low-rank adapters only; 0 (default) = full "
+                        "fine-tuning")
+    g.add_argument("--lora-alpha", type=float, default=16.0, help="LoRA scale numerator (scale = alpha / r)")
+    g.add_argument("--lora-dropout", type=float, default=0.0, help="dropout on the adapter branch's input")
+    g.add_argument("--lora-targets", type=str, default="q,v",
+                   help="comma list of adapted projections out of q,k,v,o,wi,wo")
     return ap
+
+
+def maybe_apply_lora(model, args, log_fn=None):
+    """``--lora-r N``: freeze ``model`` and attach adapters (models/lora.py) — before the engine is built — and log the
+    trainable / total parameter counts once.  Without the flag the model is returned untouched."""
+    if not getattr(args, "lora_r", 0):
+        return model
+    import json
+
+    from .models.lora import LoraConfig, apply_lora, param_counts
+    targets = tuple(t.strip() for t in args.lora_targets.split(",") if t.strip())
+    apply_lora(model, LoraConfig(r=args.lora_r, alpha=args.lora_alpha, dropout=args.lora_dropout, targets=targets))
+    train, total = param_counts(model)
+    if log_fn is not None:
+        log_fn(json.dumps({"trainable_params": train, "total_params": total, "lora_r": args.lora_r,
+                           "lora_targets": list(targets)}))
+    return model
 
 
 # Evaluation / generation batch when --eval-batch-size is not given.  Beam-search generation is launch-bound at small

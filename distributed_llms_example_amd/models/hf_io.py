@@ -10,6 +10,7 @@ Loading uses safetensors only — nothing that can execute code from the file.
 """
 from __future__ import annotations
 
+import json
 import os
 
 import torch
@@ -58,6 +59,8 @@ def to_hf_state_dict(model) -> dict[str, torch.Tensor]:
     out = {}
     for name, t in model.state_dict().items():
         t = t.detach()
+        if _is_adapter_key(name):  # adapters have a checkpoint of their own (save_adapter)
+            continue
         if cfg.model_type == "t5":
             if name.endswith(".wi.weight") and cfg.is_gated:
                 a, b = t.chunk(2, dim=0)
@@ -93,6 +96,8 @@ def from_hf_state_dict(model, sd: dict[str, torch.Tensor], strict: bool = True):
     own = model.state_dict()
     new = {}
     for name in own:
+        if _is_adapter_key(name):
+            continue
         if cfg.model_type == "t5":
             if name.endswith(".wi.weight") and cfg.is_gated:
                 new[name] = torch.cat([sd[name.replace(".wi.weight", ".wi_0.weight")],
@@ -122,7 +127,7 @@ def from_hf_state_dict(model, sd: dict[str, torch.Tensor], strict: bool = True):
     # them on save (_keys_to_ignore_on_save) and our module already holds the exact table, so their absence is not an
     # error (Pegasus checkpoints do carry them and they are loaded like any other key)
     derived = {n + ".weight" for n, m in model.named_modules() if getattr(m, "derived_table", False)}
-    missing = [k for k in own if k not in new and k not in derived]
+    missing = [k for k in own if k not in new and k not in derived and not _is_adapter_key(k)]
     if strict and missing:
         raise KeyError(f"missing keys in checkpoint: {missing[:8]}{'...' if len(missing) > 8 else ''}")
     with torch.no_grad():
@@ -150,3 +155,96 @@ def from_pretrained(name_or_path: str, dtype=torch.float32, device="cpu"):
         if os.path.exists(st):
             from_hf_state_dict(model, load_file(st))
     return model.to(device=device, dtype=dtype)
+
+
+# ------------------------------------------------------------------------------------------------ LoRA adapters
+# PEFT's checkpoint layout, written from its documented format (peft is not installed where this was developed):
+# adapter_config.json (peft_type LORA, task_type SEQ_2_SEQ_LM, r, lora_alpha, lora_dropout, target_modules) and
+# adapter_model.safetensors with keys base_model.model.<HF module path>.lora_A.weight [r, in] / .lora_B.weight [out, r],
+# where the module path is transformers' name of the UNFUSED projection (the mapping of to_hf_state_dict).
+
+
+def _is_adapter_key(name: str) -> bool:
+    leaf = name.rsplit(".", 1)[-1]
+    return leaf.startswith("lora_A_") or leaf.startswith("lora_B_")
+
+
+def hf_param_names(cfg, name: str) -> list[str]:
+    """transformers' names of the parameters our parameter ``name`` is the concatenation of (along dim 0)."""
+    if cfg.model_type == "t5":
+        if name.endswith(".wi.weight") and cfg.is_gated:
+            return [name.replace(".wi.weight", ".wi_0.weight"), name.replace(".wi.weight", ".wi_1.weight")]
+        for suf, parts in _FUSED_T5.items():
+            if name.endswith(suf):
+                return [name[: -len(suf)] + p for p in parts]
+        return [name]
+    names = _hf_names(cfg, name)
+    return [name] if names is None else names
+
+
+# leaf module names of transformers' projections -> our logical LoRA targets (models/lora.py)
+_LEAF_TARGET = {"q": "q", "q_proj": "q", "query": "q", "k": "k", "k_proj": "k", "key": "k", "v": "v", "v_proj": "v",
+                "value": "v", "o": "o", "out_proj": "o", "output": "o", "wi": "wi", "wi_0": "wi", "wi_1": "wi",
+                "fc1": "wi", "wo": "wo", "fc2": "wo"}
+
+
+def adapter_keys(model) -> dict:
+    """{PEFT key: parameter} of every adapter matrix of ``model``."""
+    from .lora import adapted_layers, adapter_slice_index
+    out = {}
+    for name, mod in adapted_layers(model):
+        paths = [n[: -len(".weight")] for n in hf_param_names(model.config, name + ".weight")]
+        for ad in mod._lora[0]:
+            path = paths[adapter_slice_index(ad)]
+            out[f"base_model.model.{path}.lora_A.weight"] = ad.A
+            out[f"base_model.model.{path}.lora_B.weight"] = ad.B
+    return out
+
+
+def save_adapter(model, output_dir: str) -> list[str]:
+    """Write the adapters of a model under ``apply_lora`` in PEFT's layout.  Returns the written file names."""
+    from .lora import has_lora
+    if not has_lora(model):
+        raise RuntimeError("save_adapter: the model carries no adapters (models/lora.py apply_lora)")
+    os.makedirs(output_dir, exist_ok=True)
+    cfg = model._lora_cfg
+    keys = adapter_keys(model)
+    leaves = sorted({k.split(".")[-3] for k in keys})
+    conf = {"peft_type": "LORA", "task_type": "SEQ_2_SEQ_LM", "r": int(cfg.r), "lora_alpha": cfg.alpha,
+            "lora_dropout": float(cfg.dropout), "target_modules": leaves, "bias": "none", "fan_in_fan_out": False,
+            "inference_mode": True, "base_model_name_or_path": None}
+    with open(os.path.join(output_dir, "adapter_config.json"), "w") as f:
+        json.dump(conf, f, indent=2, sort_keys=True)
+    sd = {k: v.detach().to("cpu").contiguous().clone() for k, v in keys.items()}
+    save_file(sd, os.path.join(output_dir, "adapter_model.safetensors"), metadata={"format": "pt"})
+    return ["adapter_config.json", "adapter_model.safetensors"]
+
+
+def load_adapter(model, adapter_dir: str):
+    """Load an adapter checkpoint written by ``save_adapter`` (or PEFT) into ``model``; a model without adapters gets
+    them first (``apply_lora`` with the checkpoint's rank, alpha, dropout and targets)."""
+    from .lora import TARGETS, LoraConfig, apply_lora, has_lora
+    with open(os.path.join(adapter_dir, "adapter_config.json")) as f:
+        conf = json.load(f)
+    if conf.get("peft_type") != "LORA":
+        raise ValueError(f"load_adapter: peft_type {conf.get('peft_type')!r} is not LORA")
+    if not has_lora(model):
+        unknown = [m for m in conf["target_modules"] if m not in _LEAF_TARGET]
+        if unknown:
+            raise ValueError(f"load_adapter: target modules {unknown} have no counterpart here")
+        named = {_LEAF_TARGET[m] for m in conf["target_modules"]}
+        targets = tuple(t for t in TARGETS if t in named)
+        apply_lora(model, LoraConfig(r=int(conf["r"]), alpha=conf["lora_alpha"], dropout=float(conf["lora_dropout"]),
+                                     targets=targets))
+    sd = load_file(os.path.join(adapter_dir, "adapter_model.safetensors"))
+    keys = adapter_keys(model)
+    missing = [k for k in keys if k not in sd]
+    extra = [k for k in sd if k not in keys]
+    if missing or extra:
+        raise KeyError(f"load_adapter: missing keys {missing[:4]}, unexpected keys {extra[:4]}")
+    with torch.no_grad():
+        for k, p in keys.items():
+            if tuple(sd[k].shape) != tuple(p.shape):
+                raise ValueError(f"load_adapter: {k} has shape {tuple(sd[k].shape)}, the model's is {tuple(p.shape)}")
+            p.copy_(sd[k].to(p.dtype))
+    return model

@@ -61,6 +61,30 @@ def _enabled() -> bool:
     return routing.get("ffn") == "fused"
 
 
+def _use_trainable(params) -> None:
+    """``_use`` for the parameters that take a gradient (a frozen FFN, models/lora.py, has none: forward and input
+    gradient only, no ``_use`` / ``_fire``, no hook)."""
+    for q in params:
+        if q is not None and q.requires_grad:
+            _use(q)
+
+
+def _kept(params, x2, h, h_for_wgrad_only: bool):
+    """(x2, h) as saved for backward: both are weight-gradient operands, so a frozen FFN keeps neither — except ``h``
+    where the backward epilogue itself reads it (the ReLU derivative without a bit mask)."""
+    if params[0].requires_grad:
+        return x2, h
+    return None, (None if h_for_wgrad_only else h)
+
+
+def _frozen_ffn(x: torch.Tensor, lin_in, lin_out) -> bool:
+    """A frozen FFN without adapters of its own under a trainable input: the fused kernels run it forward and through
+    the input gradient, and skip every weight / bias gradient."""
+    if not x.requires_grad or getattr(lin_in, "_lora", None) is not None or getattr(lin_out, "_lora", None) is not None:
+        return False
+    return not any(t is not None and t.requires_grad for t in (lin_in.weight, lin_in.bias, lin_out.weight, lin_out.bias))
+
+
 class _FusedFFNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, wi, bi, wo, bo, act, p, seed, params):
@@ -77,10 +101,9 @@ class _FusedFFNFn(torch.autograd.Function):
             h = C.gemm_w4(x2, wi, False, bi, None, False, -1, True, 1, float(p), int(seed), mask)
             y = linear_fwd(h, wo, bo)
             ctx.set_materialize_grads(False)
-            ctx.save_for_backward(x2, h, None, mask)
+            ctx.save_for_backward(*_kept(params, x2, h, True), None, mask)
             ctx.params = params
-            for q in params:
-                _use(q)
+            _use_trainable(params)
             ctx.cfg = (act, float(p), int(seed), shape)
             ctx.w4 = True
             return y.view(*shape[:-1], wo.shape[0]), x.view_as(x)
@@ -94,10 +117,9 @@ class _FusedFFNFn(torch.autograd.Function):
             h = C.gemm_w4(x2, wi, False, bi, None, False, -1, True, 11, float(p), int(seed), None, False, None, u)
             y = linear_fwd(h, wo, bo)
             ctx.set_materialize_grads(False)
-            ctx.save_for_backward(x2, h, u, None)
+            ctx.save_for_backward(*_kept(params, x2, h, True), u, None)
             ctx.params = params
-            for q in params:
-                _use(q)
+            _use_trainable(params)
             ctx.cfg = (act, float(p), int(seed), shape)
             return y.view(*shape[:-1], wo.shape[0]), x.view_as(x)
         if efwd == 1 and _pingpong(C, x2.shape[1]) and _pingpong(C, wo.shape[0]):  # ReLU: mask bits
@@ -105,10 +127,9 @@ class _FusedFFNFn(torch.autograd.Function):
         h = C.gemm_fused(x2, wi, False, efwd, bi, None, u, float(p), int(seed), -1, mask)
         y = linear_fwd(h, wo, bo)
         ctx.set_materialize_grads(False)  # the residual alias's gradient is None when the caller does not use it
-        ctx.save_for_backward(x2, h, u, mask)
+        ctx.save_for_backward(*_kept(params, x2, h, efwd != 1 or mask is not None), u, mask)
         ctx.params = params
-        for q in params:
-            _use(q)
+        _use_trainable(params)
         ctx.cfg = (act, float(p), int(seed), shape)
         return y.view(*shape[:-1], wo.shape[0]), x.view_as(x)
 
@@ -120,6 +141,7 @@ class _FusedFFNFn(torch.autograd.Function):
         C = _ext.native()
         _, ebwd = EPILOGUES[act]
         wo = Wo.detach()
+        train = Wo.requires_grad  # False: a frozen FFN (models/lora.py), input gradient only
         dy2 = dy.reshape(-1, dy.shape[-1])
         if not C.gemm_fused_supported(dy2, wo, True):
             dy2 = dy2.contiguous()
@@ -127,7 +149,7 @@ class _FusedFFNFn(torch.autograd.Function):
         bsum = None
         w4g = (ebwd == 4 and routing.get("ffn_gelu") == "w4" and dy2.shape[0] % 128 == 0
                and C.gemm_w4_supported(dy2, wo, True))
-        if Bi is not None and ebwd in (4, 6) and (w4g or _pingpong(C, wo.shape[0])):
+        if train and Bi is not None and ebwd in (4, 6) and (w4g or _pingpong(C, wo.shape[0])):
             bsum = torch.empty(dy2.shape[0] // 128, wo.shape[1], device=dy2.device, dtype=torch.float32)
         if w4g:  # dU = dH * (stored derivative) + per-128-row column partials, on the w4 kernel
             cs = bsum if bsum is not None else torch.empty(dy2.shape[0] // 128, wo.shape[1], device=dy2.device,
@@ -143,13 +165,14 @@ class _FusedFFNFn(torch.autograd.Function):
             du = C.gemm_fused(dy2, wo, True, 7, None, None, None, p, seed, -1, mask)
         else:
             du = C.gemm_fused(dy2, wo, True, ebwd, None, h if ebwd == 3 else u, None, p, seed, -1, None, bsum)
-        with torch.no_grad():
-            wgrad_accumulate(_gbuf(Wo), dy2, h, async_ok=streams.site_ok(Wo))
+        if train:
+            with torch.no_grad():
+                wgrad_accumulate(_gbuf(Wo), dy2, h, async_ok=streams.site_ok(Wo))
+                if Bo is not None:
+                    bias_grad_accumulate(_gbuf(Bo), dy2, dy, async_ok=streams.site_ok(Bo))
+            _fire(Wo)
             if Bo is not None:
-                bias_grad_accumulate(_gbuf(Bo), dy2, dy, async_ok=streams.site_ok(Bo))
-        _fire(Wo)
-        if Bo is not None:
-            _fire(Bo)
+                _fire(Bo)
         dx = None
         if ctx.needs_input_grad[0]:  # post-LN residual (ffn_res): its gradient accumulated by this GEMM (beta = 1)
             if dres is not None and dres.is_contiguous() and dres.dtype == du.dtype and dres.shape == shape:
@@ -160,6 +183,8 @@ class _FusedFFNFn(torch.autograd.Function):
                 dx = linear_dgrad(du, Wi.detach())
                 if dres is not None:
                     dx = dx + dres.reshape(dx.shape)
+        if not train:
+            return (None if dx is None else dx.view(shape)), None, None, None, None, None, None, None, None
         with torch.no_grad():
             wgrad_accumulate(_gbuf(Wi), du, x2, async_ok=streams.site_ok(Wi))
             if bsum is not None:
@@ -197,10 +222,9 @@ class _FusedGatedFFNFn(torch.autograd.Function):
         x2 = x.reshape(-1, shape[-1])
         h, g1, g2 = C.gemm_geglu(x2, wi, float(p), int(seed))
         y = linear_fwd(h, wo)
-        ctx.save_for_backward(x2, h, g1, g2)
+        ctx.save_for_backward(*_kept(params, x2, h, True), g1, g2)
         ctx.params = params
-        for q in params:
-            _use(q)
+        _use_trainable(params)
         ctx.shape = shape
         return y.view(*shape[:-1], wo.shape[0])
 
@@ -213,13 +237,16 @@ class _FusedGatedFFNFn(torch.autograd.Function):
         if not C.gemm_fused_supported(dy2, Wo.detach(), True):
             dy2 = dy2.contiguous()
         du = C.gemm_dgeglu(dy2, Wo.detach(), g1, g2)
-        with torch.no_grad():
-            wgrad_accumulate(_gbuf(Wo), dy2, h, async_ok=streams.site_ok(Wo))
-        _fire(Wo)
+        train = Wo.requires_grad  # False: a frozen FFN (models/lora.py), input gradient only
+        if train:
+            with torch.no_grad():
+                wgrad_accumulate(_gbuf(Wo), dy2, h, async_ok=streams.site_ok(Wo))
+            _fire(Wo)
         dx = linear_dgrad(du, Wi.detach()) if ctx.needs_input_grad[0] else None
-        with torch.no_grad():
-            wgrad_accumulate(_gbuf(Wi), du, x2, async_ok=streams.site_ok(Wi))
-        _fire(Wi)
+        if train:
+            with torch.no_grad():
+                wgrad_accumulate(_gbuf(Wi), du, x2, async_ok=streams.site_ok(Wi))
+            _fire(Wi)
         return (None if dx is None else dx.view(ctx.shape)), None, None, None, None, None
 
 
@@ -240,7 +267,7 @@ def gated_ffn(x: torch.Tensor, lin_in, lin_out, act: str, p: float = 0.0, seed: 
     wi, wo = lin_in.weight, lin_out.weight
     if (act in ("gelu_new", "gelu_fast") and _enabled() and x.dtype == torch.bfloat16 and _ext.use_native(x)
             and torch.is_grad_enabled() and lin_in.bias is None and lin_out.bias is None
-            and _fusable(wi) and _fusable(wo)):
+            and ((_fusable(wi) and _fusable(wo)) or _frozen_ffn(x, lin_in, lin_out))):
         C = _ext.native()
         x2 = x.reshape(-1, x.shape[-1])
         Fd = wo.shape[1]
@@ -264,7 +291,8 @@ def ffn_res(x: torch.Tensor, lin_in, lin_out, act: str, p: float = 0.0, seed: in
     global fused_calls
     if (act in EPILOGUES and _enabled() and x.dtype == torch.bfloat16 and _ext.use_native(x)
             and torch.is_grad_enabled()
-            and all(_fusable(t) for t in (lin_in.weight, lin_in.bias, lin_out.weight, lin_out.bias))):
+            and (all(_fusable(t) for t in (lin_in.weight, lin_in.bias, lin_out.weight, lin_out.bias))
+                 or _frozen_ffn(x, lin_in, lin_out))):
         x2 = x.reshape(-1, x.shape[-1])
         if x2.shape[0] >= routing.get("ffn_min_rows") and _fusable_shapes(x2, lin_in.weight, lin_out.weight):
             fused_calls += 1

@@ -166,19 +166,46 @@ def _fusable(p: torch.Tensor | None) -> bool:
     return p is None or (getattr(p, "_dllm_fused_wgrad", False) and p.requires_grad and _gbuf(p) is not None)
 
 
+def _frozen(weight: torch.Tensor, bias: torch.Tensor | None) -> bool:
+    """A layer whose parameters take no gradient (the base model under adapters, models/lora.py)."""
+    return not weight.requires_grad and (bias is None or not bias.requires_grad)
+
+
+class _FrozenLinearFn(torch.autograd.Function):
+    """A frozen layer on the tuned GEMM routes: forward through ``linear_fwd``, input gradient through ``linear_dgrad``
+    (ops/gemm.py); no weight / bias gradient, nothing saved but the weight, no reducer hook."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(weight)
+        return linear_fwd(x, weight, bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (w,) = ctx.saved_tensors
+        return linear_dgrad(dy, w), None, None
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = None) -> torch.Tensor:
     """Functional ``F.linear`` with the weight gradient accumulated by the GEMM (e.g. a tied LM head)."""
     if torch.is_grad_enabled() and _fusable(weight) and _fusable(bias):
         y = _LinearAccumFn.apply(x, weight.detach(), None if bias is None else bias.detach(), (weight, bias))
         _mark_bias_out(y, bias is not None)
         return y
+    if torch.is_grad_enabled() and x.requires_grad and _frozen(weight, bias):
+        return _FrozenLinearFn.apply(x, weight, bias)
     return F.linear(x, weight, bias)
 
 
 class Linear(nn.Linear):
     """Drop-in ``nn.Linear`` (same parameters / state-dict keys / init) with GEMM-fused grad accumulation."""
 
+    _lora = None  # (adapters, dropout p) once models/lora.py apply_lora attached low-rank adapters to this layer
+
     def forward(self, x):
+        if self._lora is not None:
+            from .lora import adapted_forward
+            return adapted_forward(self, x)
         return linear(x, self.weight, self.bias)
 
 
@@ -271,9 +298,17 @@ def stacked_linear(x, mods, shape):
     backward is one dgrad GEMM with K = Σ n_l (instead of L GEMMs plus L-1 adds of dX) and one wgrad
     GEMM accumulated into the flat gradient buffer; consumers that know how (ops/attention.py) write
     their input gradient straight into the stacked gradient buffer through ``_dllm_grad_into``."""
+    if any(getattr(m, "_lora", None) is not None for m in mods):  # adapters are per layer: one GEMM each
+        return [m(x).view(shape) for m in mods]
     ws = [m.weight for m in mods]
     bs = [m.bias for m in mods]
     has_b = bs[0] is not None
+    if torch.is_grad_enabled() and x.requires_grad and all(_frozen(w, b) for w, b in zip(ws, bs)):
+        # frozen base without adapters here: one GEMM over the stacked weights, on the tuned routes
+        y = _FrozenLinearFn.apply(x, _adjacent(ws) if _adjacent(ws) is not None else torch.cat(ws),
+                                  None if not has_b else torch.cat(bs))
+        n = ws[0].shape[0]
+        return [y[..., l * n:(l + 1) * n].view(shape) for l in range(len(mods))]
     W = _adjacent(ws)
     B_ = _adjacent(bs) if has_b else None
     if (torch.is_grad_enabled() and W is not None and (B_ is not None or not has_b)

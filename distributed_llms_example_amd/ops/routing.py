@@ -68,6 +68,11 @@ sampling                       one launch per decode step (``gen_fused_sample``)
                                bans, temperature, top-k / top-p thresholds by radix select
                                and the Gumbel-max draw in csrc/sample.hip (0: the torch
                                composite, a sort of [rows, V] per step)
+low-rank adapters (LoRA)       csrc/lora.hip (``lora`` = fused): mask regenerated from the     lora_step.txt
+                               row hash, one pass over x, the output slice read and written
+                               once, split reductions summed in order into the flat
+                               gradient; ``lib``: the composite on torch matmuls (2-9x
+                               slower per adapted projection, 3.3-3.6x per step)
 gradient reducer               native C++ engine (``reducer`` = native | python), buckets     r5_gloo2_gpu.txt
                                re-laid in gradient-ready order (``rebuild_buckets``)
 HIP-graph DP schedule          overlap: backward segments cut at bucket readiness            r5_gloo2_gpu_final.txt
@@ -105,6 +110,8 @@ DEFAULTS: dict = {
     "lmhead": "auto",             # auto | fused | logits
     "lmhead_full_mb": 16384.0,
     "lmhead_chunk_mb": 128.0,
+    # low-rank adapters (ops/lora.py): csrc/lora.hip, or the composite on torch matmuls
+    "lora": "fused",              # fused | lib
     # attention (ops/attention.py, parallel/context.py)
     "attn_f32": 1,
     "attn_hd": 1,                 # bf16 head dims 32 .. 128 other than 64 on csrc/attn_hd.hip (0: composite)

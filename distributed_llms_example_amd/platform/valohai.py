@@ -143,8 +143,11 @@ def save_valohai_metadata(model, output_dir: str, is_main_process: bool = True, 
     """ref/helpers.py:12-28: save the model (HF format) and write per-file metadata sidecars."""
     if not is_main_process:
         return []
-    from ..models.hf_io import save_pretrained
+    from ..models.hf_io import save_adapter, save_pretrained
+    from ..models.lora import has_lora
     save_pretrained(model, output_dir)
+    if has_lora(model):  # a LoRA run (--lora-r): the adapter checkpoint next to the (frozen) base model
+        save_adapter(model, output_dir)
     if tokenizer is not None and hasattr(tokenizer, "save_pretrained"):
         tokenizer.save_pretrained(output_dir)
     return write_metadata_sidecars(output_dir)

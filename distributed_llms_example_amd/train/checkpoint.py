@@ -15,7 +15,8 @@ import re
 
 import torch
 
-from ..models.hf_io import from_hf_state_dict, save_pretrained
+from ..models.hf_io import from_hf_state_dict, load_adapter, save_adapter, save_pretrained
+from ..models.lora import has_lora
 from ..ops import rng as _rng_mod
 from ..ops.rng import default_rng
 from ..parallel import collectives
@@ -26,6 +27,8 @@ def save_checkpoint(path: str, model, optimizer=None, scheduler=None, trainer_st
     os.makedirs(path, exist_ok=True)
     if rank == 0:
         save_pretrained(model, path)
+        if has_lora(model):  # the adapters' own checkpoint (model.safetensors holds the frozen base)
+            save_adapter(model, path)
         state = {}
         if optimizer is not None:
             od = optimizer.state_dict()
@@ -53,6 +56,8 @@ def load_checkpoint(path: str, model=None, optimizer=None, scheduler=None, rank:
     if model is not None:
         from safetensors.torch import load_file
         from_hf_state_dict(model, load_file(os.path.join(path, "model.safetensors")))
+        if has_lora(model):
+            load_adapter(model, path)
     sp = os.path.join(path, "training_state.pt")
     if os.path.exists(sp):
         state = torch.load(sp, map_location="cpu", weights_only=True)

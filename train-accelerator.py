@@ -24,7 +24,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from torch.utils.data import DataLoader  # noqa: E402
 
-from distributed_llms_example_amd.cli import base_parser, build_data, eval_batch_size, model_config  # noqa: E402
+from distributed_llms_example_amd.cli import (base_parser, build_data, eval_batch_size, maybe_apply_lora,  # noqa: E402
+                                              model_config)
 from distributed_llms_example_amd.data.collator import DataCollatorForSeq2Seq  # noqa: E402
 from distributed_llms_example_amd.models import build_model, from_pretrained  # noqa: E402
 from distributed_llms_example_amd.utils import faults  # noqa: E402
@@ -56,6 +57,7 @@ class ModelTrainer:
             build_model(self.cfg)
         if self.cfg.gradient_checkpointing:
             self.model.gradient_checkpointing_enable()
+        maybe_apply_lora(self.model, args, print if self.accelerator.is_main_process else None)
 
     def dump(self, logs):
         if self.accelerator.is_main_process:

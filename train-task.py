@@ -50,7 +50,7 @@ def run(env, args):
     import numpy as np
     from torch.utils.data import DataLoader
 
-    from distributed_llms_example_amd.cli import build_data, model_config
+    from distributed_llms_example_amd.cli import build_data, maybe_apply_lora, model_config
     from distributed_llms_example_amd.data.collator import DataCollatorForSeq2Seq
     from distributed_llms_example_amd.models import build_model, from_pretrained
     from distributed_llms_example_amd.ops.rng import manual_seed
@@ -79,6 +79,7 @@ def run(env, args):
     model = from_pretrained(args.model_ckpt) if os.path.isdir(args.model_ckpt or "") else build_model(cfg)
     if cfg.gradient_checkpointing:
         model.gradient_checkpointing_enable()
+    maybe_apply_lora(model, args, print if env.is_main_process else None)
     dtype = torch.bfloat16 if (args.precision or ("bf16" if env.device.type == "cuda" else "fp32")) == "bf16" \
         else torch.float32
     eng = TrainEngine(model, env, lr=args.learning_rate, weight_decay=0.0, max_grad_norm=None, dtype=dtype,

@@ -20,7 +20,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("TRANSFORMERS_NO_ADVISORY_WARNINGS", "true")
 
-from distributed_llms_example_amd.cli import base_parser, build_data, eval_batch_size, model_config  # noqa: E402
+from distributed_llms_example_amd.cli import (base_parser, build_data, eval_batch_size, maybe_apply_lora,  # noqa: E402
+                                              model_config)
 from distributed_llms_example_amd.data.collator import DataCollatorForSeq2Seq  # noqa: E402
 from distributed_llms_example_amd.models import build_model, from_pretrained  # noqa: E402
 from distributed_llms_example_amd.parallel.env import init_distributed  # noqa: E402
@@ -52,6 +53,7 @@ def run(args):
     model = from_pretrained(args.model_ckpt) if os.path.isdir(args.model_ckpt or "") else build_model(cfg)
     if cfg.gradient_checkpointing:
         model.gradient_checkpointing_enable()
+    maybe_apply_lora(model, args, print if env.is_main_process else None)
     targs = TrainingArguments(
         output_dir=output_dir, num_train_epochs=args.num_epochs, warmup_steps=args.warmup_steps,
         per_device_train_batch_size=args.batch_size, per_device_eval_batch_size=eval_batch_size(args, env.device),
