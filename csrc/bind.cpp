@@ -14,6 +14,7 @@
 #include "attn_params.h"
 #include "gemm_params.h"
 #include "route.h"
+#include "adafactor_params.h"
 
 extern "C" {
 int dllm_norm_fwd(const void*, const void*, const void*, const void*, void*, void*, float*, float*, int, int, float,
@@ -31,6 +32,9 @@ int dllm_ce_bwd(const float*, const void*, const int64_t*, const float*, const f
 int dllm_sq_norm(const void*, long, float*, float*, int, hipStream_t);
 int dllm_adamw(void*, float*, const void*, float*, float*, const uint8_t*, const float*, long, float, float, float,
                float, float, float, float, int, int, const float*, hipStream_t);
+int dllm_adafactor_step(void*, float*, const float*, float*, float*, const long*, int, long, float*, float*, float*,
+                        float*, const float*, float, float, float, float, float, float, int, int, const float*,
+                        hipStream_t);
 int dllm_set_seed_step_norm(const uint32_t*);
 int dllm_set_seed_step_act(const uint32_t*);
 int dllm_set_seed_step_attn(const uint32_t*);
@@ -374,6 +378,111 @@ void adamw_step(Tensor param, const optional<Tensor>& master, const Tensor& grad
                       (float)bc2, is_bf16(param), grad.scalar_type() == at::kFloat,
                       has_hyper ? hyper->data_ptr<float>() : nullptr, stream()),
            "adamw");
+}
+
+// Adafactor (csrc/adafactor.hip).  adafactor_plan lays out the unit table the kernels walk: `units` is a CPU int64
+// [U, 6] of (flat offset, rows, cols, R|V offset, C offset or -1, decay flag) per unit; the result is the [U + 1,
+// AF_FIELDS] table (csrc/adafactor_params.h) with tile prefix sums and scratch offsets, the tile count and the sizes of
+// the column- and row-partial scratch buffers (floats).
+std::tuple<Tensor, int64_t, int64_t, int64_t> adafactor_plan(const Tensor& units) {
+  TORCH_CHECK(!units.is_cuda() && units.scalar_type() == at::kLong && units.dim() == 2 && units.size(1) == 6 &&
+                  units.is_contiguous() && units.size(0) >= 1, "adafactor_plan: units must be a CPU int64 [U, 6]");
+  const int64_t U = units.size(0);
+  const int64_t* u = units.data_ptr<int64_t>();
+  Tensor tab = at::zeros({U + 1, (int64_t)AF_FIELDS}, units.options());
+  int64_t* t = tab.data_ptr<int64_t>();
+  int64_t tiles = 0, colpart = 0, rowpart = 0;
+  for (int64_t i = 0; i < U; ++i) {
+    const int64_t off = u[i * 6 + 0], rows = u[i * 6 + 1], cols = u[i * 6 + 2], rv = u[i * 6 + 3], c = u[i * 6 + 4];
+    TORCH_CHECK(off >= 0 && rows >= 1 && cols >= 1 && rv >= 0 && (c >= 0 || rows == 1), "adafactor_plan: unit ", i);
+    int64_t* r = t + i * AF_FIELDS;
+    const int64_t nchunk = (cols + AF_CC - 1) / AF_CC, nrb = (rows + AF_RB - 1) / AF_RB;
+    r[AF_OFF] = off; r[AF_ROWS] = rows; r[AF_COLS] = cols; r[AF_RV] = rv; r[AF_C] = c < 0 ? -1 : c;
+    r[AF_DECAY] = u[i * 6 + 5] != 0;
+    r[AF_TILE0] = tiles; r[AF_NCHUNK] = nchunk; r[AF_SCAL] = i;
+    r[AF_COLPART] = colpart; r[AF_ROWPART] = rowpart;
+    r[AF_VEC] = cols % 4 == 0 && off % 4 == 0 && rv % 4 == 0 && (c < 0 || c % 4 == 0);
+    tiles += nrb * nchunk;
+    if (c >= 0) {
+      colpart += (nrb * cols + 3) / 4 * 4;
+      rowpart += rows * nchunk;
+    }
+  }
+  t[U * AF_FIELDS + AF_TILE0] = tiles;
+  return {tab, tiles, std::max<int64_t>(colpart, 4), std::max<int64_t>(rowpart, 4)};
+}
+
+std::vector<int64_t> adafactor_geometry() {
+  return {AF_RB, AF_WC, AF_CC, AF_GRID_CAP, AF_FIN_SLICES, AF_FIN_COLS};
+}
+
+void adafactor_step(Tensor param, const optional<Tensor>& master, const Tensor& grad, Tensor rv, Tensor cst,
+                    const Tensor& tab_dev, const Tensor& tab_host, Tensor scal, Tensor colpart, Tensor rowpart,
+                    Tensor tpart, const Tensor& coef, double rel, double b2t, double eps1, double eps2, double clip_thr,
+                    double wd, bool scale_param, const optional<Tensor>& hyper) {
+  check_gpu(param, "param");
+  const int64_t n = param.numel();
+  const bool bf16 = is_bf16(param);
+  const bool has_master = master.has_value() && master->defined();
+  TORCH_CHECK(param.is_contiguous() && grad.is_cuda() && grad.is_contiguous() && grad.numel() == n,
+              "adafactor: param / grad must be contiguous GPU tensors of one size");
+  TORCH_CHECK(grad.scalar_type() == at::kFloat, "adafactor: gradients must be fp32");
+  TORCH_CHECK(bf16 == has_master, "adafactor: bf16 parameters need an fp32 master, fp32 parameters take none");
+  check_aligned(param, 16, "adafactor param");
+  check_aligned(grad, 16, "adafactor grad");
+  if (has_master) {
+    TORCH_CHECK(master->numel() == n && master->scalar_type() == at::kFloat && master->is_cuda() &&
+                    master->is_contiguous(), "adafactor: master must be a contiguous fp32 GPU tensor [n]");
+    check_aligned(*master, 16, "adafactor master");
+  }
+  for (auto* t : {&rv, &cst, &scal, &colpart, &rowpart, &tpart}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(),
+                "adafactor: state / scratch must be contiguous fp32 GPU tensors");
+    check_aligned(*t, 16, "adafactor state");
+  }
+  TORCH_CHECK(coef.scalar_type() == at::kFloat && coef.is_cuda(), "adafactor: coef fp32 device scalar");
+  const bool has_hyper = hyper.has_value() && hyper->defined();
+  if (has_hyper)
+    TORCH_CHECK(hyper->is_cuda() && hyper->scalar_type() == at::kFloat && hyper->numel() >= 2 && hyper->is_contiguous(),
+                "adafactor: hyper must be a contiguous fp32 device tensor [rel, beta2t]");
+  TORCH_CHECK(!tab_host.is_cuda() && tab_host.scalar_type() == at::kLong && tab_host.dim() == 2 &&
+                  tab_host.size(1) == AF_FIELDS && tab_host.size(0) >= 2 && tab_host.is_contiguous(),
+              "adafactor: host table must be a CPU int64 [U + 1, fields]");
+  TORCH_CHECK(tab_dev.is_cuda() && tab_dev.scalar_type() == at::kLong && tab_dev.sizes() == tab_host.sizes() &&
+                  tab_dev.is_contiguous(), "adafactor: device table must be the host table's copy");
+  // every range a kernel will touch, checked on the host copy of the table before anything is launched
+  const int64_t U = tab_host.size(0) - 1;
+  const int64_t* t = tab_host.data_ptr<int64_t>();
+  int64_t tiles = 0;
+  for (int64_t i = 0; i < U; ++i) {
+    const int64_t* r = t + i * AF_FIELDS;
+    const int64_t rows = r[AF_ROWS], cols = r[AF_COLS], c = r[AF_C];
+    TORCH_CHECK(rows >= 1 && cols >= 1 && cols <= n && rows <= n / cols && r[AF_OFF] >= 0 &&
+                    r[AF_OFF] <= n - rows * cols,
+                "adafactor: unit ", i, " lies outside the flat buffer");
+    const int64_t nchunk = (cols + AF_CC - 1) / AF_CC, nrb = (rows + AF_RB - 1) / AF_RB;
+    TORCH_CHECK(r[AF_TILE0] == tiles && r[AF_NCHUNK] == nchunk && r[AF_SCAL] >= 0 && r[AF_SCAL] < U,
+                "adafactor: unit ", i, " has an inconsistent tile layout");
+    TORCH_CHECK(r[AF_RV] >= 0 && r[AF_RV] + (c < 0 ? cols : rows) <= rv.numel() && (c >= 0 || rows == 1) &&
+                    (c < 0 || c + cols <= cst.numel()), "adafactor: unit ", i, " state lies outside its buffer");
+    if (c >= 0)
+      TORCH_CHECK(r[AF_COLPART] >= 0 && r[AF_COLPART] + nrb * cols <= colpart.numel() && r[AF_ROWPART] >= 0 &&
+                      r[AF_ROWPART] + rows * nchunk <= rowpart.numel(), "adafactor: unit ", i, " scratch out of range");
+    if (r[AF_VEC])
+      TORCH_CHECK(cols % 4 == 0 && r[AF_OFF] % 4 == 0 && r[AF_RV] % 4 == 0 && (c < 0 || (c % 4 == 0 &&
+                      r[AF_COLPART] % 4 == 0)), "adafactor: unit ", i, " is not aligned for 16-byte access");
+    tiles += nrb * nchunk;
+  }
+  TORCH_CHECK(t[U * AF_FIELDS + AF_TILE0] == tiles && tpart.numel() >= 2 * tiles && scal.numel() >= 4 * U &&
+                  U <= INT_MAX, "adafactor: tile scratch / scalar array too small");
+  check_rc(dllm_adafactor_step(param.data_ptr(), has_master ? master->data_ptr<float>() : nullptr,
+                               grad.data_ptr<float>(), rv.data_ptr<float>(), cst.data_ptr<float>(),
+                               reinterpret_cast<const long*>(tab_dev.data_ptr<int64_t>()), (int)U, (long)tiles,
+                               scal.data_ptr<float>(), colpart.data_ptr<float>(), rowpart.data_ptr<float>(),
+                               tpart.data_ptr<float>(), coef.data_ptr<float>(), (float)rel, (float)b2t, (float)eps1,
+                               (float)eps2, (float)clip_thr, (float)wd, scale_param ? 1 : 0, bf16 ? 1 : 0,
+                               has_hyper ? hyper->data_ptr<float>() : nullptr, stream()),
+           "adafactor");
 }
 
 // ------------------------------------------------------------------------------------------- attention
@@ -1556,6 +1665,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_step", &adamw_step, py::arg("param"), py::arg("master"), py::arg("grad"), py::arg("m"), py::arg("v"),
         py::arg("wd_mask"), py::arg("coef"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
         py::arg("bc1"), py::arg("bc2"), py::arg("hyper") = py::none());
+  m.def("adafactor_plan", &adafactor_plan, "unit table, tile count and scratch sizes of csrc/adafactor.hip");
+  m.def("adafactor_geometry", &adafactor_geometry, "[rows per tile, cols per wave, cols per tile, grid cap, ...]");
+  m.def("adafactor_step", &adafactor_step, py::arg("param"), py::arg("master"), py::arg("grad"), py::arg("rv"),
+        py::arg("c"), py::arg("table"), py::arg("table_host"), py::arg("scal"), py::arg("colpart"), py::arg("rowpart"),
+        py::arg("tpart"), py::arg("coef"), py::arg("rel"), py::arg("beta2t"), py::arg("eps1"), py::arg("eps2"),
+        py::arg("clip_threshold"), py::arg("weight_decay"), py::arg("scale_parameter"), py::arg("hyper") = py::none());
   m.def("set_seed_step", &set_seed_step, "device step counter mixed into every dropout site seed (None: off)");
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
         py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("sat_lo") = -1,

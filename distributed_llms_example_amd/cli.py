@@ -50,6 +50,9 @@ def base_parser(description: str, defaults: dict | None = None) -> argparse.Argu
                    help="run gradient-accumulation micro-batches as fewer larger passes: 'auto' (as many as the "
                         "first step's measured activation memory allows in 60%% of HBM), N (max samples per pass), 0 off")
     g.add_argument("--learning-rate", type=float, default=5e-5)
+    g.add_argument("--optim", choices=["adamw", "adafactor"], default="adamw",
+                   help="optimizer: fused AdamW, or Adafactor as the HF Trainer builds it (scale_parameter=False, "
+                        "relative_step=False, the learning rate from --learning-rate and the usual schedule)")
     g.add_argument("--max-steps", type=int, default=-1)
     g.add_argument("--bucket-mb", type=bucket_mb_arg, default="auto",
                    help="gradient all-reduce bucket size in MiB, or 'auto' (default: probe RCCL's bus bandwidth over "

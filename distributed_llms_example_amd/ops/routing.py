@@ -73,6 +73,9 @@ low-rank adapters (LoRA)       csrc/lora.hip (``lora`` = fused): mask regenerate
                                once, split reductions summed in order into the flat
                                gradient; ``lib``: the composite on torch matmuls (2-9x
                                slower per adapted projection, 3.3-3.6x per step)
+Adafactor                      csrc/adafactor.hip (``adafactor`` = fused): five launches per   adafactor_step.txt
+                               step over a device unit table, three gradient reads, fixed-
+                               order partial sums; ``composite``: the per-unit torch ops
 gradient reducer               native C++ engine (``reducer`` = native | python), buckets     r5_gloo2_gpu.txt
                                re-laid in gradient-ready order (``rebuild_buckets``)
 HIP-graph DP schedule          overlap: backward segments cut at bucket readiness            r5_gloo2_gpu_final.txt
@@ -112,6 +115,8 @@ DEFAULTS: dict = {
     "lmhead_chunk_mb": 128.0,
     # low-rank adapters (ops/lora.py): csrc/lora.hip, or the composite on torch matmuls
     "lora": "fused",              # fused | lib
+    # Adafactor (ops/optim.py FusedAdafactor): csrc/adafactor.hip, or the per-unit torch composite
+    "adafactor": "fused",         # fused | composite
     # attention (ops/attention.py, parallel/context.py)
     "attn_f32": 1,
     "attn_hd": 1,                 # bf16 head dims 32 .. 128 other than 64 on csrc/attn_hd.hip (0: composite)

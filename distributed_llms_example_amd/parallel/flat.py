@@ -84,6 +84,7 @@ class FlatParams:
         self.numel = off
         self._companions: list[tuple[object, str]] = []  # flat-indexed tensors kept in step with relayout()
         self.canonical = [s.name for s in self.segments]  # construction order (optimizer state is saved in it)
+        self.layout_version = 0  # bumped by relayout(): whoever caches segment offsets (ops/optim.py unit table) compares it
         self.param_buf = torch.zeros(off, dtype=self.dtype, device=self.device)
         self.grad_buf = torch.zeros(off, dtype=self.grad_dtype, device=self.device)
         # autograd insists p.grad has p's dtype: with fp32 gradients for bf16 weights the flat slices are handed
@@ -184,6 +185,7 @@ class FlatParams:
         segs = [Segment(self.segments[i].name, dst[i], self.segments[i].numel, self.segments[i].shape) for i in order]
         params = [self.params[i] for i in order]
         self.segments, self.params, self.numel = segs, params, n
+        self.layout_version += 1
         for i, (seg, p) in enumerate(zip(self.segments, self.params)):
             p.data = self.param_buf[seg.offset:seg.offset + seg.numel].view(seg.shape)
             p._dllm_gbuf = self.grad_view(i)

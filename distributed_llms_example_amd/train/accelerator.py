@@ -6,6 +6,7 @@ process).  ``prepare(model, optimizer, train_dl, eval_dl)`` (accelerate/accelera
 * model → :class:`PreparedModel`: weights moved to the device in the compute dtype, parameters
   flattened, the bucketed RCCL reducer attached and parameters broadcast from rank 0 (what DDP's
   constructor does); calling it runs the fused-kernel model;
+* a ``transformers.optimization.Adafactor`` → :class:`~..ops.optim.FusedAdafactor` with its group options;
 * a ``torch.optim.AdamW`` built on the raw model → :class:`~..ops.optim.FusedAdamW` over the flat
   buffers with the same lr / betas / eps and per-group weight decay (drop-in);
 * a ``DataLoader`` → :class:`DeviceDataLoader` sharded like Accelerate's BatchSamplerShard
@@ -24,7 +25,7 @@ import contextlib
 
 import torch
 
-from ..ops.optim import FusedAdamW
+from ..ops.optim import FusedAdafactor, FusedAdamW
 from ..parallel import collectives
 from ..parallel.env import init_distributed
 from ..parallel.flat import FlatParams
@@ -80,9 +81,9 @@ class DeviceDataLoader:
 
 
 class PreparedOptimizer:
-    """Wraps FusedAdamW so it quacks like the torch optimizer the user built."""
+    """Wraps FusedAdamW / FusedAdafactor so it quacks like the torch optimizer the user built."""
 
-    def __init__(self, opt: FusedAdamW, accelerator):
+    def __init__(self, opt: FusedAdamW | FusedAdafactor, accelerator):
         self.opt = opt
         self.acc = accelerator
         self._clip = None
@@ -211,8 +212,18 @@ class Accelerator:
         wds = {decay_of.get(id(p), 0.0) for p in flat.params}
         wd = max(wds) if wds else 0.0
         no_decay_names = {names[id(p)] for p in flat.params if decay_of.get(id(p), 0.0) == 0.0}
-        fused = FusedAdamW(flat, lr=g0["lr"], betas=g0.get("betas", (0.9, 0.999)), eps=g0.get("eps", 1e-8),
-                           weight_decay=wd, no_decay=(lambda n: n in no_decay_names) if wd else None)
+        no_decay = (lambda n: n in no_decay_names) if wd else None
+        if type(opt).__name__ == "Adafactor" and "clip_threshold" in g0:  # transformers.optimization.Adafactor
+            from ..models.hf_io import hf_param_names
+            cfg = getattr(self._model.module, "config", None)
+            fused = FusedAdafactor(flat, lr=g0["lr"], eps=g0["eps"], clip_threshold=g0["clip_threshold"],
+                                   decay_rate=g0["decay_rate"], beta1=g0["beta1"], weight_decay=wd,
+                                   scale_parameter=g0["scale_parameter"], relative_step=g0["relative_step"],
+                                   warmup_init=g0["warmup_init"], no_decay=no_decay,
+                                   parts=(lambda n: len(hf_param_names(cfg, n))) if cfg is not None else None)
+        else:
+            fused = FusedAdamW(flat, lr=g0["lr"], betas=g0.get("betas", (0.9, 0.999)), eps=g0.get("eps", 1e-8),
+                               weight_decay=wd, no_decay=no_decay)
         po = PreparedOptimizer(fused, self)
         self._prepared_opts.append(po)
         return po

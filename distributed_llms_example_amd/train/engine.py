@@ -16,7 +16,7 @@ from ..data.packing import PACKED_KEYS
 from ..ops import gemm
 from ..ops import rng as rng_mod
 from ..ops import streams
-from ..ops.optim import FusedAdamW
+from ..ops.optim import FusedAdafactor, FusedAdamW
 from ..utils import profiling
 from ..parallel.env import DistEnv
 from ..parallel.flat import FlatParams
@@ -48,10 +48,12 @@ class TrainEngine:
                  betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float | None = 1.0,
                  dtype: torch.dtype = torch.bfloat16, bucket_mb: float | str = DEFAULT_BUCKET_MB, overlap: bool = True,
                  no_decay=default_no_decay, label_smoothing: float = 0.0, grad_dtype: torch.dtype | None = None,
-                 force_reducer: bool = False, grad_reduce_dtype: str | None = None):
+                 force_reducer: bool = False, grad_reduce_dtype: str | None = None, optim: str = "adamw"):
         """``bucket_mb``: MiB per all-reduce bucket, or "auto" (parallel/reducer.py choose_bucket_mb: probed on the
         job's process group, recorded in ``reducer.bucket_choice``).  ``grad_reduce_dtype``: "bf16" compresses each bucket
-        for the wire only (fp32 accumulation kept), None / "fp32" reduces the gradient buffer as it is."""
+        for the wire only (fp32 accumulation kept), None / "fp32" reduces the gradient buffer as it is.  ``optim``:
+        "adamw", or "adafactor" as the HF Trainer builds it (scale_parameter=False, relative_step=False, the learning
+        rate from ``lr``; ``betas`` / ``eps`` are AdamW's and unused)."""
         self.env = env
         self.model = model.to(device=env.device, dtype=dtype)
         self.dtype = dtype
@@ -63,8 +65,17 @@ class TrainEngine:
                         if env.world_size > 1 or force_reducer else None)
         if self.reducer is not None:
             self.reducer.broadcast_params(self.model)
-        self.optimizer = FusedAdamW(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                    no_decay=no_decay)
+        if optim == "adamw":
+            self.optimizer = FusedAdamW(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                        no_decay=no_decay)
+        elif optim == "adafactor":
+            from ..models.hf_io import hf_param_names
+            cfg = getattr(self.model, "config", None)
+            self.optimizer = FusedAdafactor(self.flat, lr=lr, weight_decay=weight_decay, scale_parameter=False,
+                                            relative_step=False, no_decay=no_decay,
+                                            parts=(lambda n: len(hf_param_names(cfg, n))) if cfg is not None else None)
+        else:
+            raise ValueError(f"optim must be 'adamw' or 'adafactor', got {optim!r}")
         self.max_grad_norm = max_grad_norm
         self.label_smoothing = label_smoothing
         self.step_seed: rng_mod.StepSeed | None = None
@@ -215,7 +226,8 @@ class TrainEngine:
             self.wgrad_defer.flush()
         self.wgrad_defer.active = True
         self._ga_k = 0
-        with profiling.range("optimizer(clip+adamw)"):
+        with profiling.range("optimizer(clip+adamw)" if isinstance(self.optimizer, FusedAdamW) else
+                             "optimizer(clip+adafactor)"):
             norm = self.optimizer.step(self.max_grad_norm, hyper=hyper)
             self.optimizer.zero_grad()
         return norm

@@ -54,6 +54,7 @@ class TrainingArguments:
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
     adam_epsilon: float = 1e-8
+    optim: str = "adamw_torch"  # any of HF's AdamW names (one fused AdamW here), or "adafactor"
     max_grad_norm: float = 1.0
     lr_scheduler_type: str = "linear"
     warmup_steps: int = 0
@@ -93,6 +94,8 @@ class TrainingArguments:
             self.eval_strategy = self.evaluation_strategy
         if self.eval_strategy == "steps" and not self.eval_steps:
             self.eval_steps = self.logging_steps
+        if self.optim != "adafactor" and not str(self.optim).startswith("adamw"):
+            raise ValueError(f"optim={self.optim!r}: 'adafactor' or one of the 'adamw*' names are supported")
 
     def to_dict(self):
         return dataclasses.asdict(self)
@@ -131,7 +134,8 @@ class Trainer:
                                   max_grad_norm=args.max_grad_norm, dtype=self.dtype,
                                   bucket_mb=args.ddp_bucket_cap_mb or "auto", overlap=args.overlap_comm,
                                   grad_reduce_dtype=args.grad_reduce_dtype,
-                                  no_decay=default_no_decay, label_smoothing=args.label_smoothing_factor)
+                                  no_decay=default_no_decay, label_smoothing=args.label_smoothing_factor,
+                                  optim="adafactor" if args.optim == "adafactor" else "adamw")
         self.model = self.engine.model
         self.train_dataset = train_dataset
         self.eval_dataset = eval_dataset

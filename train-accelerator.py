@@ -75,7 +75,11 @@ class ModelTrainer:
             {"params": [p for n, p in self.model.named_parameters() if any(nd in n for nd in no_decay)],
              "weight_decay": 0.0},
         ]
-        optimizer = torch.optim.AdamW(groups, lr=a.learning_rate)
+        if a.optim == "adafactor":  # as the HF Trainer builds it (transformers trainer.py: optim="adafactor")
+            from transformers.optimization import Adafactor
+            optimizer = Adafactor(groups, lr=a.learning_rate, scale_parameter=False, relative_step=False)
+        else:
+            optimizer = torch.optim.AdamW(groups, lr=a.learning_rate)
         model, optimizer, train_dl, eval_dl = acc.prepare(self.model, optimizer, train_dl, eval_dl)
         max_train_steps = a.num_epochs * len(train_dl)
         if a.max_steps > 0:

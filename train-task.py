@@ -84,7 +84,7 @@ def run(env, args):
         else torch.float32
     eng = TrainEngine(model, env, lr=args.learning_rate, weight_decay=0.0, max_grad_norm=None, dtype=dtype,
                       bucket_mb=args.bucket_mb or "auto", overlap=not args.no_overlap, no_decay=None,
-                      grad_reduce_dtype=args.grad_reduce_dtype)
+                      grad_reduce_dtype=args.grad_reduce_dtype, optim=args.optim)
     collator = DataCollatorForSeq2Seq.for_model(cfg, pad_to_multiple_of=8)
     # partition_dataset (ref/train-task.py:176-191)
     world = env.world_size

@@ -60,6 +60,7 @@ def run(args):
         weight_decay=0.01, logging_steps=10, evaluation_strategy="steps", eval_steps=args.evaluation_steps,
         save_steps=args.save_steps or 1e6, gradient_accumulation_steps=args.grad_accum or 16, ddp_find_unused_parameters=False,
         learning_rate=args.learning_rate, max_steps=args.max_steps, seed=args.seed,
+        optim="adafactor" if args.optim == "adafactor" else "adamw_torch",
         bf16=None if args.precision is None else args.precision == "bf16",
         ddp_bucket_cap_mb=args.bucket_mb, overlap_comm=not args.no_overlap, grad_reduce_dtype=args.grad_reduce_dtype,
         context_parallel_size=args.context_parallel,
