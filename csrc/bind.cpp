@@ -57,6 +57,14 @@ int dllm_ce_chunk_fwd(const void*, long, const int64_t*, const float*, float*, f
                       long, int, int, int, hipStream_t);
 int dllm_ce_chunk_bwd(const float*, void*, long, const int64_t*, const float*, const float*, long, int, int, int, float,
                       long, int, hipStream_t);
+int dllm_kd_fwd(const void*, const void*, const int64_t*, const float*, const float*, float*, float*, float*, long, int,
+                float, long, float, int, hipStream_t);
+int dllm_kd_bwd(const float*, const float*, const void*, const void*, const int64_t*, const float*, const float*,
+                const float*, void*, long, int, float, long, float, int, hipStream_t);
+int dllm_kd_chunk_fwd(const void*, long, const void*, long, const int64_t*, const float*, const float*, float*, float*,
+                      float*, float*, long, int, int, int, float, long, float, int, int, int, hipStream_t);
+int dllm_kd_chunk_bwd(const float*, const float*, void*, long, const void*, long, const int64_t*, const float*,
+                      const float*, const float*, long, int, int, int, float, long, float, int, hipStream_t);
 int dllm_embed_bwd(const int64_t*, const int64_t*, const void*, long, long, int, float*, void*, long, long, int,
                    hipStream_t);
 int dllm_colsum_acc(const void*, long, long, int, float*, void*, int, hipStream_t);
@@ -324,6 +332,140 @@ void ce_chunk_bwd(const Tensor& scale, Tensor& logits, const Tensor& labels, con
                              lse.data_ptr<float>(), bp, N, (int)Vc, (int)c0, (int)V, (float)eps, ignore, (int)skip,
                              stream()),
            "ce_chunk_bwd");
+}
+
+// ------------------------------------------------------------------------------------------- distillation loss
+// csrc/kd.hip: label-smoothed CE + temperature-scaled KL to a teacher's logits, one pass over both [N, V] tensors.
+namespace {
+// fp32 [V] GPU bias (or none) of one side; the returned tensor keeps the converted copy alive
+Tensor kd_bias(const optional<Tensor>& bias, int64_t V, const char* name) {
+  Tensor bf;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->is_cuda(), "kd: ", name, " must be a GPU tensor");
+    bf = bias->to(at::kFloat).contiguous();
+    TORCH_CHECK(bf.numel() == V, "kd: ", name, " must have V entries");
+  }
+  return bf;
+}
+void kd_check_pair(const Tensor& student, const Tensor& teacher, const Tensor& labels, double T) {
+  TORCH_CHECK(student.is_cuda(), "kd: student must be a GPU tensor");
+  TORCH_CHECK(teacher.is_cuda(), "kd: teacher must be a GPU tensor");
+  TORCH_CHECK(student.dim() == 2 && student.is_contiguous(), "kd: student must be contiguous [N, V]");
+  TORCH_CHECK(teacher.dim() == 2 && teacher.is_contiguous(), "kd: teacher must be contiguous [N, V]");
+  TORCH_CHECK(student.scalar_type() == at::kBFloat16 || student.scalar_type() == at::kFloat,
+              "kd: student must be bf16 or fp32");
+  TORCH_CHECK(teacher.scalar_type() == student.scalar_type(), "kd: teacher must have the student's dtype");
+  TORCH_CHECK(teacher.size(0) == student.size(0) && teacher.size(1) == student.size(1),
+              "kd: teacher must have the student's shape [N, V]");
+  TORCH_CHECK(student.size(1) > 0 && student.size(1) <= INT_MAX, "kd: student V out of range");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == student.size(0) &&
+                  labels.is_contiguous(), "kd: labels must be int64 [N] on the GPU");
+  TORCH_CHECK(T > 0.0, "kd: temperature must be > 0");
+}
+}  // namespace
+
+std::vector<Tensor> kd_fwd(const Tensor& student, const Tensor& teacher, const Tensor& labels,
+                           const optional<Tensor>& bias_s, const optional<Tensor>& bias_t, double eps, int64_t ignore,
+                           double T) {
+  kd_check_pair(student, teacher, labels, T);
+  const long N = student.size(0);
+  const int V = student.size(1);
+  Tensor bs = kd_bias(bias_s, V, "bias_s"), bt = kd_bias(bias_t, V, "bias_t");
+  auto f32 = student.options().dtype(at::kFloat);
+  auto ce = at::empty({N}, f32), kl = at::empty({N}, f32), stats = at::empty({N, 3}, f32);
+  if (N > 0)
+    check_rc(dllm_kd_fwd(student.data_ptr(), teacher.data_ptr(), labels.data_ptr<int64_t>(),
+                         bs.defined() ? bs.data_ptr<float>() : nullptr, bt.defined() ? bt.data_ptr<float>() : nullptr,
+                         ce.data_ptr<float>(), kl.data_ptr<float>(), stats.data_ptr<float>(), N, V, (float)eps, ignore,
+                         (float)T, is_bf16(student), stream()),
+             "kd_fwd");
+  return {ce, kl, stats};
+}
+
+Tensor kd_bwd(const Tensor& w_ce, const Tensor& w_kl, Tensor student, const Tensor& teacher, const Tensor& labels,
+              const Tensor& stats, const optional<Tensor>& bias_s, const optional<Tensor>& bias_t, double eps,
+              int64_t ignore, double T, bool inplace) {
+  kd_check_pair(student, teacher, labels, T);
+  const long N = student.size(0);
+  const int V = student.size(1);
+  TORCH_CHECK(w_ce.is_cuda() && w_ce.scalar_type() == at::kFloat && w_ce.numel() >= 1, "kd: w_ce must be a fp32 GPU scalar");
+  TORCH_CHECK(w_kl.is_cuda() && w_kl.scalar_type() == at::kFloat && w_kl.numel() >= 1, "kd: w_kl must be a fp32 GPU scalar");
+  TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kFloat && stats.numel() == 3 * N && stats.is_contiguous(),
+              "kd: stats must be fp32 [N, 3]");
+  Tensor bs = kd_bias(bias_s, V, "bias_s"), bt = kd_bias(bias_t, V, "bias_t");
+  Tensor out = inplace ? student : at::empty_like(student);
+  if (N > 0)
+    check_rc(dllm_kd_bwd(w_ce.data_ptr<float>(), w_kl.data_ptr<float>(), student.data_ptr(), teacher.data_ptr(),
+                         labels.data_ptr<int64_t>(), stats.data_ptr<float>(),
+                         bs.defined() ? bs.data_ptr<float>() : nullptr, bt.defined() ? bt.data_ptr<float>() : nullptr,
+                         out.data_ptr(), N, V, (float)eps, ignore, (float)T, is_bf16(student), stream()),
+             "kd_bwd");
+  return out;
+}
+
+namespace {
+// the [N, Vc] bf16 chunk pair of the vocabulary-chunked form: same conventions as ce_chunk_*
+void kd_check_chunks(const Tensor& student, const Tensor& teacher, const Tensor& labels, const Tensor& stats,
+                     const optional<Tensor>& bias_s, const optional<Tensor>& bias_t, int64_t c0, int64_t V, double T,
+                     int64_t skip) {
+  TORCH_CHECK(student.is_cuda(), "kd_chunk: student must be a GPU tensor");
+  TORCH_CHECK(teacher.is_cuda(), "kd_chunk: teacher must be a GPU tensor");
+  TORCH_CHECK(student.dim() == 2 && student.scalar_type() == at::kBFloat16 && student.stride(1) == 1 &&
+                  student.stride(0) % 4 == 0 && student.size(1) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(student.data_ptr()) % 8 == 0,
+              "kd_chunk: student must be bf16 [N, Vc] with Vc % 4 == 0 and 8-B aligned rows");
+  TORCH_CHECK(teacher.dim() == 2 && teacher.scalar_type() == at::kBFloat16 && teacher.stride(1) == 1 &&
+                  teacher.stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(teacher.data_ptr()) % 8 == 0,
+              "kd_chunk: teacher must be bf16 [N, Vc] with 8-B aligned rows");
+  TORCH_CHECK(teacher.size(0) == student.size(0) && teacher.size(1) == student.size(1),
+              "kd_chunk: teacher must have the student's shape [N, Vc]");
+  const int64_t N = student.size(0), Vc = student.size(1);
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == N && labels.is_contiguous(),
+              "kd_chunk: labels must be int64 [N] on the GPU");
+  TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kFloat && stats.numel() == 3 * N && stats.is_contiguous(),
+              "kd_chunk: stats must be fp32 [N, 3]");
+  TORCH_CHECK(V > 0 && V <= INT_MAX && c0 >= 0 && c0 + Vc <= V, "kd_chunk: chunk outside the vocabulary");
+  TORCH_CHECK(skip >= 0 && skip < std::max<int64_t>(Vc, 1), "kd_chunk: skip out of range");
+  TORCH_CHECK(T > 0.0, "kd_chunk: temperature must be > 0");
+  for (const auto* b : {&bias_s, &bias_t})
+    if (b->has_value() && (*b)->defined())
+      TORCH_CHECK((*b)->is_cuda() && (*b)->scalar_type() == at::kFloat && (*b)->numel() == V && (*b)->is_contiguous(),
+                  "kd_chunk: bias_s / bias_t must be fp32 [V] on the GPU");
+}
+}  // namespace
+
+void kd_chunk_fwd(const Tensor& student, const Tensor& teacher, const Tensor& labels, const optional<Tensor>& bias_s,
+                  const optional<Tensor>& bias_t, Tensor& state, Tensor& ce, Tensor& kl, Tensor& stats, int64_t c0,
+                  int64_t V, double eps, int64_t ignore, double T, bool first, bool last, int64_t skip) {
+  kd_check_chunks(student, teacher, labels, stats, bias_s, bias_t, c0, V, T, skip);
+  const int64_t N = student.size(0), Vc = student.size(1);
+  TORCH_CHECK(state.is_cuda() && state.scalar_type() == at::kFloat && state.numel() == 8 * N && state.is_contiguous(),
+              "kd_chunk: state must be fp32 [N, 8]");
+  TORCH_CHECK(ce.is_cuda() && kl.is_cuda() && ce.numel() == N && kl.numel() == N && ce.scalar_type() == at::kFloat &&
+                  kl.scalar_type() == at::kFloat && ce.is_contiguous() && kl.is_contiguous(),
+              "kd_chunk: ce / kl must be fp32 [N]");
+  if (N == 0) return;
+  check_rc(dllm_kd_chunk_fwd(student.data_ptr(), student.stride(0), teacher.data_ptr(), teacher.stride(0),
+                             labels.data_ptr<int64_t>(), (const float*)opt_ptr(bias_s), (const float*)opt_ptr(bias_t),
+                             state.data_ptr<float>(), ce.data_ptr<float>(), kl.data_ptr<float>(),
+                             stats.data_ptr<float>(), N, (int)Vc, (int)c0, (int)V, (float)eps, ignore, (float)T, first,
+                             last, (int)skip, stream()),
+           "kd_chunk_fwd");
+}
+
+void kd_chunk_bwd(const Tensor& w_ce, const Tensor& w_kl, Tensor& student, const Tensor& teacher, const Tensor& labels,
+                  const Tensor& stats, const optional<Tensor>& bias_s, const optional<Tensor>& bias_t, int64_t c0,
+                  int64_t V, double eps, int64_t ignore, double T, int64_t skip) {
+  kd_check_chunks(student, teacher, labels, stats, bias_s, bias_t, c0, V, T, skip);
+  const int64_t N = student.size(0), Vc = student.size(1);
+  TORCH_CHECK(w_ce.is_cuda() && w_ce.scalar_type() == at::kFloat && w_ce.numel() >= 1, "kd_chunk: w_ce must be a fp32 GPU scalar");
+  TORCH_CHECK(w_kl.is_cuda() && w_kl.scalar_type() == at::kFloat && w_kl.numel() >= 1, "kd_chunk: w_kl must be a fp32 GPU scalar");
+  if (N == 0) return;
+  check_rc(dllm_kd_chunk_bwd(w_ce.data_ptr<float>(), w_kl.data_ptr<float>(), student.data_ptr(), student.stride(0),
+                             teacher.data_ptr(), teacher.stride(0), labels.data_ptr<int64_t>(), stats.data_ptr<float>(),
+                             (const float*)opt_ptr(bias_s), (const float*)opt_ptr(bias_t), N, (int)Vc, (int)c0, (int)V,
+                             (float)eps, ignore, (float)T, (int)skip, stream()),
+           "kd_chunk_bwd");
 }
 
 // ------------------------------------------------------------------------------------------- optimizer
@@ -1662,6 +1804,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embed_bwd", &embed_bwd);
   m.def("ce_chunk_fwd", &ce_chunk_fwd);
   m.def("ce_chunk_bwd", &ce_chunk_bwd);
+  m.def("kd_fwd", &kd_fwd, "distillation loss forward (CE + KL to the teacher): (ce_rows, kl_rows, stats [N, 3])");
+  m.def("kd_bwd", &kd_bwd, "student-logits gradient of the distillation loss, optionally in place");
+  m.def("kd_chunk_fwd", &kd_chunk_fwd);
+  m.def("kd_chunk_bwd", &kd_chunk_bwd);
   m.def("adamw_step", &adamw_step, py::arg("param"), py::arg("master"), py::arg("grad"), py::arg("m"), py::arg("v"),
         py::arg("wd_mask"), py::arg("coef"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
         py::arg("bc1"), py::arg("bc2"), py::arg("hyper") = py::none());

@@ -5,46 +5,11 @@
 // bwd: dx_v = g * (exp(x_v - lse) - eps/V - (1-eps)*[v==y]) with g = *scale (device scalar, no host
 //      sync), written as bf16 — optionally in place over the logits (the only consumer).
 #include "common.h"
+#include "row_walk.h"
 
 using namespace dllm;
 
 namespace {
-
-// Rows of any length V: row r starts at logits + r * V, 16-B aligned only when V is a multiple of 16 / sizeof(T)
-// (BART's V = 50265 is odd).  Each row is walked as a scalar head up to the first 16-B boundary, 16-B vectors (8 bf16
-// or 4 fp32 per thread and step: one global_load_dwordx4), and a scalar tail — every row at the vector rate whatever
-// its alignment (an odd V with element-wise loads ran at 1.5-2.3 TB/s on bart-large 1024/1024, r5 profile).
-template <typename T>
-DLLM_DEVICE int row_head(const T* p, int V) {
-  const int mis = (int)(reinterpret_cast<uintptr_t>(p) & 15);
-  return min(V, ((16 - mis) & 15) / (int)sizeof(T));
-}
-
-template <typename T>
-struct Vec16 {
-  static constexpr int N = 16 / (int)sizeof(T);
-  DLLM_DEVICE static void load(const T* p, float (&v)[16 / sizeof(T)]) {
-    if constexpr (sizeof(T) == 2) {
-      const u16x8 u = *reinterpret_cast<const u16x8*>(p);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = bf2f(u[k]);
-    } else {
-      const f32x4 u = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = u[k];
-    }
-  }
-  DLLM_DEVICE static void store(T* p, const float (&v)[16 / sizeof(T)]) {
-    if constexpr (sizeof(T) == 2) {
-      u16x8 u;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) u[k] = f2bf(v[k]);
-      *reinterpret_cast<u16x8*>(p) = u;
-    } else {
-      *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-    }
-  }
-};
 
 template <typename T>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
@@ -146,13 +111,6 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ s
     Vec16<T>::store(dx + c, v);
   }
   for (int c = body_end + (int)threadIdx.x; c < V; c += 256) one(c);
-}
-
-// bias[c0 + c .. + 3]: one 16-B load when that address is 16-B aligned, else four scalar loads (the ragged vocab tail
-// chunk starts at c0 = V - Vc, odd for BART's V = 50265)
-DLLM_DEVICE f32x4 bias4(const float* __restrict__ bias, int i) {
-  if ((i & 3) == 0) return *reinterpret_cast<const f32x4*>(bias + i);
-  return f32x4{bias[i], bias[i + 1], bias[i + 2], bias[i + 3]};
 }
 
 // ---- vocab-chunked LM head + CE (ops/lm_head.py): the logits exist one [N, Vc] chunk at a time

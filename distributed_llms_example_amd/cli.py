@@ -27,7 +27,8 @@ def base_parser(description: str, defaults: dict | None = None) -> argparse.Argu
     d = {"batch_size": 1, "num_epochs": 1, "warmup_steps": 500, "evaluation_steps": 500}
     d.update(defaults or {})
     ap = argparse.ArgumentParser(description=description)
-    ap.add_argument("--model-ckpt", type=str, default="facebook/bart-large-cnn", help="Pretrained model checkpoint")
+    ap.add_argument("--model-ckpt", type=str, default="facebook/bart-large-cnn", action=_StoreGiven,
+                    help="Pretrained model checkpoint")
     ap.add_argument("--output-dir", type=str, default="bart-large-cnn", help="Output directory for the trained model")
     ap.add_argument("--batch-size", type=int, default=d["batch_size"], help="Batch size")
     ap.add_argument("--num-epochs", type=int, default=d["num_epochs"], help="Number of training epochs")
@@ -76,7 +77,8 @@ def base_parser(description: str, defaults: dict | None = None) -> argparse.Argu
     g.add_argument("--context-parallel", type=int, default=1,
                    help="shard the encoder sequence over groups of N ranks (ring attention; T5 family)")
     g.add_argument("--model-overrides", type=str, default=None,
-                   help="comma list key=value applied to the model config (e.g. num_layers=2)")
+                   help="comma list key=value applied to the --model-ckpt model's config (e.g. num_layers=2); a "
+                        "--teacher-ckpt model keeps its own")
     g.add_argument("--lora-r", type=int, default=0,
                    help="LoRA rank (1 .. 64): freeze the model and train low-rank adapters only; 0 (default) = full "
                         "fine-tuning")
@@ -84,7 +86,89 @@ def base_parser(description: str, defaults: dict | None = None) -> argparse.Argu
     g.add_argument("--lora-dropout", type=float, default=0.0, help="dropout on the adapter branch's input")
     g.add_argument("--lora-targets", type=str, default="q,v",
                    help="comma list of adapted projections out of q,k,v,o,wi,wo")
+    g.add_argument("--teacher-ckpt", type=str, default=None,
+                   help="distil from this frozen teacher (anything --model-ckpt takes): the training loss becomes "
+                        "(1 - kd-alpha) CE + kd-alpha T^2 KL(teacher || student); evaluation and the saved model are "
+                        "the student's alone")
+    g.add_argument("--kd-alpha", type=float, default=0.5, help="weight of the KL term, in [0, 1]")
+    g.add_argument("--kd-temperature", type=float, default=2.0, help="softmax temperature T > 0 of the KL term")
+    g.add_argument("--student-layers", type=str, default=None, metavar="E,D",
+                   help="build the student from the teacher with E encoder and D decoder layers (evenly spaced teacher "
+                        "layers, layer 0 kept) instead of loading --model-ckpt; not with --model-overrides")
     return ap
+
+
+class _StoreGiven(argparse.Action):
+    """``store`` that also records, as ``<dest>_given``, that the flag was on the command line (any spelling argparse
+    accepts, whatever list was parsed): a default cannot tell."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "_given", True)
+
+
+def resolve_distill(args):
+    """Validate the distillation flags (loud ``ValueError``s) and, with ``--student-layers``, make the teacher's
+    checkpoint the source of the student's config and tokenizer.  Returns ``args``; a no-op without the flags, and on
+    ``args`` it has already resolved."""
+    from .ops.distill import check_weights
+    layers = getattr(args, "student_layers", None)
+    teacher = getattr(args, "teacher_ckpt", None)
+    if layers and not teacher:
+        raise ValueError("--student-layers needs --teacher-ckpt (the student is built from the teacher)")
+    if not teacher:
+        return args
+    check_weights(args.kd_alpha, args.kd_temperature)
+    if getattr(args, "context_parallel", 1) > 1:
+        raise NotImplementedError("--context-parallel with --teacher-ckpt is not implemented (the teacher's encoder is "
+                                  "not sharded)")
+    if layers:
+        if getattr(args, "model_ckpt_given", False):
+            raise ValueError("--student-layers builds the student from --teacher-ckpt: give it or --model-ckpt, not "
+                             "both")
+        if getattr(args, "model_overrides", None):
+            raise ValueError("--student-layers takes the teacher's config with the two layer counts replaced: "
+                             "--model-overrides does not apply to it (it is for a --model-ckpt student)")
+        if isinstance(layers, str):
+            try:
+                e, d = (int(x) for x in layers.split(","))
+            except ValueError:
+                raise ValueError(f"--student-layers takes E,D (two integers), got {layers!r}") from None
+            args.student_layers = (e, d)
+        args.model_ckpt = teacher
+    return args
+
+
+def _load(ckpt: str, cfg=None):
+    from .models import build_model, from_pretrained
+    return from_pretrained(ckpt) if os.path.isdir(ckpt or "") else build_model(cfg or resolve_config(ckpt))
+
+
+def build_models(args, cfg):
+    """``(model, teacher)``: the model the entry points train — ``--model-ckpt``, or with ``--student-layers`` a
+    shallower copy of the teacher (models/distill.py make_student) — and the ``--teacher-ckpt`` model or None.  On
+    ``--resume-from`` the teacher is rebuilt from ``--teacher-ckpt`` the same way: checkpoints hold the student only."""
+    teacher_ckpt = getattr(args, "teacher_ckpt", None)
+    if not teacher_ckpt:
+        return _load(args.model_ckpt, cfg), None
+    from .models.distill import make_student
+    layers = getattr(resolve_distill(args), "student_layers", None)
+    teacher = _load(teacher_ckpt)
+    if layers:
+        model = make_student(teacher, *layers)
+    else:
+        model = _load(args.model_ckpt, cfg)
+    if model.config.vocab_size != teacher.config.vocab_size:
+        raise ValueError(f"teacher vocab_size {teacher.config.vocab_size} and student vocab_size "
+                         f"{model.config.vocab_size} differ (teachers with another vocabulary are not supported)")
+    return model, teacher
+
+
+def kd_logs(engine) -> dict:
+    """``{"ce_loss", "kd_loss"}`` of the engine's last micro-batch when it distils, else ``{}``."""
+    if getattr(engine, "teacher", None) is None or engine.last_ce_loss is None:
+        return {}
+    return {"ce_loss": round(float(engine.last_ce_loss), 4), "kd_loss": round(float(engine.last_kd_loss), 4)}
 
 
 def maybe_apply_lora(model, args, log_fn=None):
@@ -163,7 +247,11 @@ def build_data(args, cfg):
 
 
 def model_config(args):
+    resolve_distill(args)
     cfg = apply_overrides(resolve_config(args.model_ckpt), args.model_overrides)
+    if isinstance(getattr(args, "student_layers", None), tuple):
+        from .models.distill import student_config
+        cfg = student_config(cfg, *args.student_layers)
     if getattr(args, "gradient_checkpointing", False):
         cfg = cfg.replace(gradient_checkpointing=True)
     return cfg

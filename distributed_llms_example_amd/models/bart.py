@@ -54,6 +54,7 @@ from ..ops.lm_head import lm_head_loss, wants_lm_head_loss
 from ..ops.rng import default_rng
 from .blocks import run_block
 from .config import Seq2SeqConfig
+from .distill import lm_output as distill_lm_output
 from .output import Seq2SeqLMOutput
 
 
@@ -548,7 +549,30 @@ class BartForConditionalGeneration(nn.Module):
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, labels=None,
                 label_smoothing: float = 0.0, return_logits: bool = False, encoder_outputs=None, segment_ids=None,
                 decoder_segment_ids=None, position_ids=None, decoder_position_ids=None, global_attention_mask=None,
-                global_index=None):
+                global_index=None, distill=None):
+        # distill: the teacher's LM-head operands and the loss weights (models/distill.py Distill); None: plain CE
+        dec, enc = self._decoder_hidden(input_ids, attention_mask, decoder_input_ids, labels, encoder_outputs,
+                                        segment_ids, decoder_segment_ids, position_ids, decoder_position_ids,
+                                        global_attention_mask, global_index)
+        if distill is not None:
+            return distill_lm_output(dec, self.output_embedding(), labels, distill, enc=enc, bias=self.logits_bias(),
+                                     label_smoothing=label_smoothing, return_logits=return_logits)
+        return self._lm_output(dec, enc, labels, label_smoothing, return_logits)
+
+    def lm_head_operands(self, input_ids=None, attention_mask=None, decoder_input_ids=None, labels=None,
+                         encoder_outputs=None, segment_ids=None, decoder_segment_ids=None, position_ids=None,
+                         decoder_position_ids=None, global_attention_mask=None, global_index=None):
+        """``(decoder hidden states, output embedding weight, final_logits_bias or None)`` of a batch ``forward`` would
+        take, without forming logits — what a student's ``forward(distill=...)`` needs of this model as the teacher
+        (models/distill.py)."""
+        dec, _ = self._decoder_hidden(input_ids, attention_mask, decoder_input_ids, labels, encoder_outputs,
+                                      segment_ids, decoder_segment_ids, position_ids, decoder_position_ids,
+                                      global_attention_mask, global_index)
+        return dec, self.output_embedding(), self.logits_bias()
+
+    def _decoder_hidden(self, input_ids, attention_mask, decoder_input_ids, labels, encoder_outputs, segment_ids,
+                        decoder_segment_ids, position_ids, decoder_position_ids, global_attention_mask, global_index):
+        """(decoder output, encoder output) of ``forward``'s batch, before the LM head."""
         packed = [segment_ids, decoder_segment_ids, position_ids, decoder_position_ids]
         if any(t is not None for t in packed) and self.config.model_type == "led":
             raise NotImplementedError("LED: packed inputs (--pack-sequences, segment ids) are not implemented")
@@ -570,6 +594,9 @@ class BartForConditionalGeneration(nn.Module):
             if decoder_input_ids is None:
                 decoder_input_ids = self.shift_right(labels)
             dec = self.decode(decoder_input_ids, enc, attention_mask)
+        return dec, enc
+
+    def _lm_output(self, dec, enc, labels, label_smoothing, return_logits):
         loss = None
         if labels is not None and not return_logits and wants_lm_head_loss(dec, labels.numel(), self.config.vocab_size):
             # LM head + CE with final_logits_bias, no materialised logits (ops/lm_head.py)

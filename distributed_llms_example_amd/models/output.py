@@ -11,6 +11,9 @@ class Seq2SeqLMOutput:
     loss: torch.Tensor | None = None
     logits: torch.Tensor | None = None
     encoder_last_hidden_state: torch.Tensor | None = None
+    # distillation (forward(distill=...), models/distill.py): the detached CE and KL means of the combined loss
+    ce_loss: torch.Tensor | None = None
+    kd_loss: torch.Tensor | None = None
 
     def __getitem__(self, i):
         return (self.loss, self.logits)[i]

@@ -39,6 +39,7 @@ from ..ops.lm_head import lm_head_loss, wants_lm_head_loss
 from ..ops.rng import default_rng
 from .blocks import run_block
 from .config import Seq2SeqConfig
+from .distill import lm_output as distill_lm_output
 from .output import Seq2SeqLMOutput
 
 
@@ -390,24 +391,43 @@ class T5ForConditionalGeneration(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, labels=None,
                 label_smoothing: float = 0.0, return_logits: bool = False, encoder_outputs=None, segment_ids=None,
-                decoder_segment_ids=None, position_ids=None, decoder_position_ids=None):
+                decoder_segment_ids=None, position_ids=None, decoder_position_ids=None, distill=None):
         # (position ids of a packed batch: the relative bias needs none, j - i inside an example is what it was)
+        # distill: the teacher's LM-head operands and the loss weights (models/distill.py Distill); None: plain CE
+        dec, enc = self._decoder_hidden(input_ids, attention_mask, decoder_input_ids, labels, encoder_outputs,
+                                        segment_ids, decoder_segment_ids)
+        return self._lm_output(dec, enc, labels, label_smoothing, return_logits, distill)
+
+    def _decoder_hidden(self, input_ids, attention_mask, decoder_input_ids, labels, encoder_outputs, segment_ids,
+                        decoder_segment_ids):
+        """(decoder output, encoder output) of ``forward``'s batch, before the LM head."""
         cp = getattr(self.encoder, "_cp_group", False)
         if segment_ids is not None or decoder_segment_ids is not None:
-            return self._forward_packed(input_ids, attention_mask, decoder_input_ids, labels, label_smoothing,
-                                        return_logits, encoder_outputs, segment_ids, decoder_segment_ids)
+            return self._hidden_packed(input_ids, attention_mask, decoder_input_ids, encoder_outputs, segment_ids,
+                                       decoder_segment_ids)
         if cp is not False and encoder_outputs is None:
             enc, attention_mask = context_parallel_encode(self.encode, input_ids, attention_mask, cp)
         else:
             enc = encoder_outputs if encoder_outputs is not None else self.encode(input_ids, attention_mask)
         if decoder_input_ids is None:
             decoder_input_ids = self.shift_right(labels)
-        dec = self.decode(decoder_input_ids, enc, attention_mask)
-        return self._lm_output(dec, enc, labels, label_smoothing, return_logits)
+        return self.decode(decoder_input_ids, enc, attention_mask), enc
 
-    def _forward_packed(self, input_ids, attention_mask, decoder_input_ids, labels, label_smoothing, return_logits,
-                        encoder_outputs, segment_ids, decoder_segment_ids):
-        """``forward`` on packed rows: several examples per row, told apart by ``segment_ids`` [B, S] and
+    def lm_head_operands(self, input_ids=None, attention_mask=None, decoder_input_ids=None, labels=None,
+                         encoder_outputs=None, segment_ids=None, decoder_segment_ids=None, position_ids=None,
+                         decoder_position_ids=None):
+        """``(decoder hidden states with the output scale applied, output embedding weight, logits bias = None)`` of
+        a batch ``forward`` would take, without forming logits — what a student's ``forward(distill=...)`` needs of
+        this model as the teacher (models/distill.py)."""
+        dec, _ = self._decoder_hidden(input_ids, attention_mask, decoder_input_ids, labels, encoder_outputs,
+                                      segment_ids, decoder_segment_ids)
+        if self.config.scale_decoder_outputs:
+            dec = dec * (self.config.d_model ** -0.5)
+        return dec, self.output_embedding(), self.logits_bias()
+
+    def _hidden_packed(self, input_ids, attention_mask, decoder_input_ids, encoder_outputs, segment_ids,
+                       decoder_segment_ids):
+        """``_decoder_hidden`` on packed rows: several examples per row, told apart by ``segment_ids`` [B, S] and
         ``decoder_segment_ids`` [B, T] (ids 0, 1, 2, ... in order, -1 on the padded tail; data/packing.py).  The
         per-64-block tables are built here, once per batch, and shared by every layer."""
         if segment_ids is None or decoder_segment_ids is None:
@@ -424,10 +444,13 @@ class T5ForConditionalGeneration(nn.Module):
         if attention_mask is None:
             attention_mask = segment_ids >= 0
         enc = encoder_outputs if encoder_outputs is not None else self.encode(input_ids, attention_mask, seg=(es, es))
-        dec = self.decode(decoder_input_ids, enc, attention_mask, seg=(ds, ds), cross_seg=(ds, es))
-        return self._lm_output(dec, enc, labels, label_smoothing, return_logits)
+        return self.decode(decoder_input_ids, enc, attention_mask, seg=(ds, ds), cross_seg=(ds, es)), enc
 
-    def _lm_output(self, dec, enc, labels, label_smoothing, return_logits):
+    def _lm_output(self, dec, enc, labels, label_smoothing, return_logits, distill=None):
+        if distill is not None:
+            scale = self.config.d_model ** -0.5 if self.config.scale_decoder_outputs else None
+            return distill_lm_output(dec, self.output_embedding(), labels, distill, enc=enc, scale=scale,
+                                     label_smoothing=label_smoothing, return_logits=return_logits)
         if labels is not None and not return_logits and wants_lm_head_loss(dec, labels.numel(), self.config.vocab_size):
             # LM head + CE without materialised logits: GEMM-epilogue CE or vocabulary chunks (ops/lm_head.py)
             scale = self.config.d_model ** -0.5 if self.config.scale_decoder_outputs else None

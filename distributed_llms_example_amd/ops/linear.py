@@ -215,14 +215,18 @@ class Linear(nn.Linear):
 
 def _adjacent(ts):
     """[t0; t1; ...] as ONE view when the tensors sit back-to-back in memory (same trailing shape),
-    else None.  FlatParams lays out grouped parameters this way (``_dllm_param_groups``)."""
+    else None.  FlatParams lays out grouped parameters this way (``_dllm_param_groups``).  Back-to-back addresses are
+    not enough: parameters of a model outside FlatParams each own a storage, and the allocator may well place two of
+    them next to each other — a view of the first cannot reach into the second's storage."""
     t0 = ts[0]
     if t0 is None or not t0.is_contiguous():
         return None
     tail = tuple(t0.shape[1:])
+    store = t0.untyped_storage().data_ptr()
     rows = 0
     for t in ts:
         if (t is None or not t.is_contiguous() or tuple(t.shape[1:]) != tail or t.dtype != t0.dtype
+                or t.untyped_storage().data_ptr() != store
                 or t.data_ptr() != t0.data_ptr() + rows * (t0.numel() // t0.shape[0]) * t0.element_size()):
             return None
         rows += t.shape[0]

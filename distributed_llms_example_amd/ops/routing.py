@@ -33,6 +33,11 @@ LM head + cross-entropy        full logits while they fit ``lmhead_full_mb`` (16
                                else vocabulary chunks of ``lmhead_chunk_mb``; the fused       r4_lmhead_fused_ab.txt,
                                GEMM+CE (w4 CEF / CEB epilogues) when ``lmhead`` = fused or    r5_bart_lmhead_fused_ab.txt
                                (auto) when the logits would exceed the budget
+distillation loss              csrc/kd.hip (``kd`` = fused): CE + KL to a teacher's logits    kd_step.txt
+(CE + KL to a teacher)         in one pass over both [N, V] tensors, gradient in place;
+                               both logits tensors count against ``lmhead_full_mb``, above
+                               it vocabulary chunks (``kd_chunk_*``); ``composite``: the
+                               torch ops.  The GEMM-epilogue CE does not serve this loss
 attention                      csrc/attn.hip bf16 flash kernels; fp32 inputs on the fp32      r4_t5base_fp32_b16_summary.txt
                                MFMA kernels of csrc/attn_f32.hip (``attn_f32`` = 1)
 cross-attention backward       one pass: dQ folded into the short-query dK/dV kernel (one    attn_sq_onepass_ab.txt
@@ -113,6 +118,8 @@ DEFAULTS: dict = {
     "lmhead": "auto",             # auto | fused | logits
     "lmhead_full_mb": 16384.0,
     "lmhead_chunk_mb": 128.0,
+    # distillation loss (ops/distill.py): csrc/kd.hip, or the torch composite
+    "kd": "fused",                # fused | composite
     # low-rank adapters (ops/lora.py): csrc/lora.hip, or the composite on torch matmuls
     "lora": "fused",              # fused | lib
     # Adafactor (ops/optim.py FusedAdafactor): csrc/adafactor.hip, or the per-unit torch composite
@@ -205,7 +212,7 @@ def attention_route(head_dim: int, bf16: bool = True, window: int | None = None,
 
 
 def plan(model: str, tokens_enc: int, tokens_dec: int, d_model: int, d_ff: int, act: str, vocab: int, *,
-         head_dim: int = 64, window: int | None = None) -> dict:
+         head_dim: int = 64, window: int | None = None, teacher: bool = False) -> dict:
     """What the table routes for one training step of an encoder-decoder model with these shapes (per micro-batch
     token rows): a dict op -> kernel family, as the tests and docs/ARCHITECTURE.md read it.  ``head_dim``: the
     model's attention head dim (bf16 step); ``window``: the encoder self-attention's sliding window (LongT5-local),
@@ -238,6 +245,13 @@ def plan(model: str, tokens_enc: int, tokens_dec: int, d_model: int, d_ff: int, 
     lm = get("lmhead")
     out["lm_head"] = ("w4-fused-ce" if lm == "fused" or (lm == "auto" and logits_mb > get("lmhead_full_mb"))
                       else "hipblaslt+ce")
+    if teacher:  # the distillation loss replaces the LM head's CE (ops/distill.py); no GEMM-epilogue form
+        if get("kd") != "fused":
+            out["lm_head"] = "hipblaslt+composite-kd"
+        elif get("lmhead_full_mb") >= 0 and 2 * logits_mb > get("lmhead_full_mb"):
+            out["lm_head"] = "hipblaslt+kd-chunk"
+        else:
+            out["lm_head"] = "hipblaslt+kd"
     out["attention"] = attention_route(head_dim)
     if window is not None:
         out["attention.window"] = int(window)

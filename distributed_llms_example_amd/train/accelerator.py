@@ -258,21 +258,25 @@ class Accelerator:
         m = model if isinstance(model, PreparedModel) else self._model
         return m.no_sync() if m is not None else contextlib.nullcontext()
 
-    def make_train_step(self, model, optimizer, graph: bool | None = None):
+    def make_train_step(self, model, optimizer, graph: bool | None = None, teacher=None, kd_alpha: float = 0.5,
+                        kd_temperature: float = 2.0):
         """The reference loop's per-batch body — ``outputs = model(**batch); accelerator.backward(outputs.loss);
         optimizer.step(); optimizer.zero_grad()`` (ref/train-accelerator.py:219-228) — as one callable
         ``step(batch) -> loss``, run by train/graph.py's StepRunner: replayed from a HIP graph once the batch shape
         repeats (GPU, unless ``graph=False`` / ``DLLM_GRAPH=0``), eager otherwise.  Gradient accumulation keeps the
         explicit loop (``accumulate`` / ``backward``).  ``clip_grad_norm_`` keeps its eager meaning: it applies to the
         next step only (call it every iteration to clip every step); a captured graph holds the clip it was captured
-        with, so a step whose clip differs drops the graph and the runner captures again (StepRunner.invalidate)."""
+        with, so a step whose clip differs drops the graph and the runner captures again (StepRunner.invalidate).
+        ``teacher``: a frozen model to distil from (train/engine.py ``set_teacher``); ``step.engine`` then carries the
+        last micro-batch's ``last_ce_loss`` / ``last_kd_loss`` for logging."""
         from .engine import TrainEngine
         from .graph import StepRunner
         m = model if isinstance(model, PreparedModel) else self._model
         po = optimizer if isinstance(optimizer, PreparedOptimizer) else self._prepared_opts[-1]
         if self.gradient_accumulation_steps != 1:
             raise ValueError("make_train_step: one micro-batch per optimizer step (use accumulate() for GA)")
-        eng = TrainEngine.from_parts(m.module, self.env, m.flat, m.reducer, po.opt, max_grad_norm=None)
+        eng = TrainEngine.from_parts(m.module, self.env, m.flat, m.reducer, po.opt, max_grad_norm=None,
+                                     teacher=teacher, kd_alpha=kd_alpha, kd_temperature=kd_temperature)
         runner = StepRunner(eng, enabled=graph)
 
         def step(batch: dict) -> torch.Tensor:
@@ -286,6 +290,7 @@ class Accelerator:
             return losses[0]
 
         step.runner = runner
+        step.engine = eng
         return step
 
     def clip_grad_norm_(self, parameters=None, max_norm: float = 1.0):

@@ -13,9 +13,11 @@ import os
 import torch
 
 from ..data.packing import PACKED_KEYS
+from ..models.distill import Distill
 from ..ops import gemm
 from ..ops import rng as rng_mod
 from ..ops import streams
+from ..ops.distill import check_weights
 from ..ops.optim import FusedAdafactor, FusedAdamW
 from ..utils import profiling
 from ..parallel.env import DistEnv
@@ -48,12 +50,15 @@ class TrainEngine:
                  betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float | None = 1.0,
                  dtype: torch.dtype = torch.bfloat16, bucket_mb: float | str = DEFAULT_BUCKET_MB, overlap: bool = True,
                  no_decay=default_no_decay, label_smoothing: float = 0.0, grad_dtype: torch.dtype | None = None,
-                 force_reducer: bool = False, grad_reduce_dtype: str | None = None, optim: str = "adamw"):
+                 force_reducer: bool = False, grad_reduce_dtype: str | None = None, optim: str = "adamw",
+                 teacher: torch.nn.Module | None = None, kd_alpha: float = 0.5, kd_temperature: float = 2.0):
         """``bucket_mb``: MiB per all-reduce bucket, or "auto" (parallel/reducer.py choose_bucket_mb: probed on the
         job's process group, recorded in ``reducer.bucket_choice``).  ``grad_reduce_dtype``: "bf16" compresses each bucket
         for the wire only (fp32 accumulation kept), None / "fp32" reduces the gradient buffer as it is.  ``optim``:
         "adamw", or "adafactor" as the HF Trainer builds it (scale_parameter=False, relative_step=False, the learning
-        rate from ``lr``; ``betas`` / ``eps`` are AdamW's and unused)."""
+        rate from ``lr``; ``betas`` / ``eps`` are AdamW's and unused).  ``teacher``: a frozen model to distil from
+        (``set_teacher``): training steps then minimise (1 - kd_alpha) CE + kd_alpha T^2 KL(teacher || student) at
+        temperature ``kd_temperature`` (ops/distill.py)."""
         self.env = env
         self.model = model.to(device=env.device, dtype=dtype)
         self.dtype = dtype
@@ -80,6 +85,32 @@ class TrainEngine:
         self.label_smoothing = label_smoothing
         self.step_seed: rng_mod.StepSeed | None = None
         self._init_defer()
+        self.set_teacher(teacher, kd_alpha, kd_temperature)
+
+    def set_teacher(self, teacher: torch.nn.Module | None, alpha: float = 0.5, temperature: float = 2.0) -> None:
+        """Distil from ``teacher`` (None: plain CE).  The teacher is cast to the compute dtype, put in ``eval()`` and
+        frozen; it lives outside the flat parameters, the reducer, the optimizer and the checkpoints.  It runs in
+        ``eval()`` under a seed scope of its own (``forward``), so it draws nothing from the dropout seed stream and the
+        student's masks are those of a run without it."""
+        self.teacher, self.kd_alpha, self.kd_temperature = None, float(alpha), float(temperature)
+        self.last_ce_loss = self.last_kd_loss = None
+        if teacher is None:
+            return
+        check_weights(alpha, temperature)
+        tv, sv = teacher.config.vocab_size, self.model.config.vocab_size
+        if tv != sv:
+            raise ValueError(f"teacher vocab_size {tv} and student vocab_size {sv} differ (teachers with another "
+                             "vocabulary are not supported)")
+        if teacher is self.model:
+            raise ValueError("the teacher must be a model of its own, not the student")
+        self._check_teacher_cp()
+        self.teacher = teacher.to(device=self.env.device, dtype=self.dtype).eval().requires_grad_(False)
+
+    def _check_teacher_cp(self) -> None:
+        enc = getattr(self.model, "encoder", None)
+        if getattr(enc, "_cp_group", False) is not False:
+            raise NotImplementedError("--context-parallel with a teacher (--teacher-ckpt) is not implemented: the "
+                                      "teacher's encoder is not sharded")
 
     # micro-batches of at most this many input tokens defer their weight gradients to the window's last one
     DEFER_MAX_TOKENS = 16384
@@ -109,7 +140,8 @@ class TrainEngine:
 
     @classmethod
     def from_parts(cls, model: torch.nn.Module, env: DistEnv, flat: FlatParams, reducer: GradReducer | None,
-                   optimizer: FusedAdamW, max_grad_norm: float | None = None, label_smoothing: float = 0.0):
+                   optimizer: FusedAdamW, max_grad_norm: float | None = None, label_smoothing: float = 0.0,
+                   teacher: torch.nn.Module | None = None, kd_alpha: float = 0.5, kd_temperature: float = 2.0):
         """An engine over state another front end already built (train/accelerator.py: the prepared model's flat
         buffers and reducer, the prepared optimizer), so its loop can run the same step — and the same HIP-graph
         step runner (train/graph.py) — as the Trainer."""
@@ -119,6 +151,7 @@ class TrainEngine:
         eng.max_grad_norm, eng.label_smoothing = max_grad_norm, label_smoothing
         eng.step_seed = None
         eng._init_defer()
+        eng.set_teacher(teacher, kd_alpha, kd_temperature)
         return eng
 
     def enable_step_seeds(self, start: int | None = None) -> rng_mod.StepSeed:
@@ -143,12 +176,23 @@ class TrainEngine:
     def no_sync(self):
         return self.reducer.no_sync() if self.reducer is not None else contextlib.nullcontext()
 
-    def forward(self, batch: dict):
+    def forward(self, batch: dict, distill: bool = True):
+        """The model's forward on ``batch``.  With a teacher (``set_teacher``) the teacher runs first, under ``no_grad``,
+        and the loss is the distillation loss; ``distill=False`` (evaluation) keeps plain CE on the student alone."""
         self.flat.reset_pending()
         # packed rows (data/packing.py) carry their segment and position ids; other batches none of these keys
         packed = {k: batch[k] for k in PACKED_KEYS if k in batch}
         # LED batches (data/collator.py) carry their global tokens, as a mask and as an index of fixed shape
         packed.update({k: batch[k] for k in ("global_attention_mask", "global_index") if k in batch})
+        if self.teacher is not None and distill:
+            self._check_teacher_cp()
+            # a stream of its own: every block draws a scope seed even at p = 0 (models/blocks.py), and the student's
+            # stream must be the one of a run without a teacher
+            with torch.no_grad(), rng_mod.rng_scope(0):
+                th, tw, tb = self.teacher.lm_head_operands(
+                    input_ids=batch["input_ids"], attention_mask=batch.get("attention_mask"),
+                    decoder_input_ids=batch.get("decoder_input_ids"), labels=batch["labels"], **packed)
+            packed["distill"] = Distill(th, tw, tb, self.kd_alpha, self.kd_temperature)
         return self.model(input_ids=batch["input_ids"], attention_mask=batch.get("attention_mask"),
                           decoder_input_ids=batch.get("decoder_input_ids"), labels=batch["labels"],
                           label_smoothing=self.label_smoothing, **packed)
@@ -197,6 +241,8 @@ class TrainEngine:
             with profiling.range("forward"):
                 out = self.forward(batch)
                 loss = out.loss
+                # the distillation loss's components of this micro-batch (None without a teacher), for logging
+                self.last_ce_loss, self.last_kd_loss = getattr(out, "ce_loss", None), getattr(out, "kd_loss", None)
             with profiling.range("backward" if sync else "backward(no_sync)"):
                 if num_items is not None:
                     w = dp_ranks if dp_ranks is not None else (self.reducer.world if self.reducer is not None else 1)

@@ -78,6 +78,8 @@ class TrainingArguments:
     grad_reduce_dtype: str = "fp32"  # "bf16": compress each gradient bucket for the wire (fp32 accumulation kept)
     context_parallel_size: int = 1  # shard the encoder sequence over groups of this many consecutive ranks
     resume_from_checkpoint: str | None = None
+    kd_alpha: float = 0.5  # distillation (Trainer(teacher=...)): weight of the KL term, and its temperature
+    kd_temperature: float = 2.0
     nan_guard: bool = True  # raise when the (logged, already synchronised) mean loss is NaN/Inf
     # Run an optimizer step's gradient-accumulation micro-batches as fewer, larger forward/backward passes (same
     # samples, same token-count normalisation, same single optimizer step).  The reference accumulates 16 micro-batches
@@ -110,7 +112,7 @@ class TrainOutput:
 
 class Trainer:
     def __init__(self, model, args: TrainingArguments, train_dataset=None, eval_dataset=None, data_collator=None,
-                 callbacks=None, tokenizer=None, processing_class=None, compute_metrics=None, env=None):
+                 callbacks=None, tokenizer=None, processing_class=None, compute_metrics=None, env=None, teacher=None):
         self.args = args
         self.env = env or init_distributed(timeout_s=args.ddp_timeout)
         self.tokenizer = processing_class if processing_class is not None else tokenizer
@@ -135,7 +137,8 @@ class Trainer:
                                   bucket_mb=args.ddp_bucket_cap_mb or "auto", overlap=args.overlap_comm,
                                   grad_reduce_dtype=args.grad_reduce_dtype,
                                   no_decay=default_no_decay, label_smoothing=args.label_smoothing_factor,
-                                  optim="adafactor" if args.optim == "adafactor" else "adamw")
+                                  optim="adafactor" if args.optim == "adafactor" else "adamw",
+                                  teacher=teacher, kd_alpha=args.kd_alpha, kd_temperature=args.kd_temperature)
         self.model = self.engine.model
         self.train_dataset = train_dataset
         self.eval_dataset = eval_dataset
@@ -378,7 +381,13 @@ class Trainer:
                     tr_loss_n.zero_()
                     if args.nan_guard and not math.isfinite(mean):  # NaN/Inf guard on loss
                         raise FloatingPointError(f"non-finite training loss {mean} at step {self.state.global_step}")
-                    self.log({"loss": round(mean, 4), "grad_norm": float(last_norm) if last_norm is not None else None,
+                    kd = {}
+                    if eng.teacher is not None and eng.last_ce_loss is not None:  # the last micro-batch's components
+                        kd = collectives.mean_across_processes(
+                            {"ce_loss": float(eng.last_ce_loss), "kd_loss": float(eng.last_kd_loss)}, env.device)
+                        kd = {k: round(v, 4) for k, v in kd.items()}
+                    self.log({"loss": round(mean, 4), **kd,
+                              "grad_norm": float(last_norm) if last_norm is not None else None,
                               "learning_rate": self.scheduler.get_last_lr()[0], "epoch": round(self.state.epoch, 4)})
                 if self.control.should_evaluate and self.eval_dataset is not None:
                     self.evaluate()
@@ -446,7 +455,7 @@ class Trainer:
             self.model.enable_context_parallel(enable=False)
         try:
             for batch in loader:
-                out = self.engine.forward(self._to_device(batch))
+                out = self.engine.forward(self._to_device(batch), distill=False)  # plain CE on the student alone
                 tot += out.loss.double()
                 n += 1
         finally:

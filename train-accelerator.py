@@ -24,10 +24,10 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from torch.utils.data import DataLoader  # noqa: E402
 
-from distributed_llms_example_amd.cli import (base_parser, build_data, eval_batch_size, maybe_apply_lora,  # noqa: E402
+from distributed_llms_example_amd.cli import (base_parser, build_data, build_models, eval_batch_size,  # noqa: E402
+                                              kd_logs, maybe_apply_lora,
                                               model_config)
 from distributed_llms_example_amd.data.collator import DataCollatorForSeq2Seq  # noqa: E402
-from distributed_llms_example_amd.models import build_model, from_pretrained  # noqa: E402
 from distributed_llms_example_amd.utils import faults  # noqa: E402
 from distributed_llms_example_amd.ops.rng import manual_seed  # noqa: E402
 from distributed_llms_example_amd.platform import valohai  # noqa: E402
@@ -53,8 +53,7 @@ class ModelTrainer:
         torch.manual_seed(args.seed)
         manual_seed(args.seed + 7919 * self.accelerator.process_index)
         self.cfg = model_config(args)
-        self.model = from_pretrained(args.model_ckpt) if os.path.isdir(args.model_ckpt or "") else \
-            build_model(self.cfg)
+        self.model, self.teacher = build_models(args, self.cfg)
         if self.cfg.gradient_checkpointing:
             self.model.gradient_checkpointing_enable()
         maybe_apply_lora(self.model, args, print if self.accelerator.is_main_process else None)
@@ -86,7 +85,8 @@ class ModelTrainer:
             max_train_steps = min(max_train_steps, a.max_steps)
         lr_scheduler = get_scheduler("linear", optimizer, num_warmup_steps=1, num_training_steps=max_train_steps)
         metric = rouge.load("rouge")
-        train_step = acc.make_train_step(model, optimizer)
+        train_step = acc.make_train_step(model, optimizer, teacher=self.teacher, kd_alpha=a.kd_alpha,
+                                         kd_temperature=a.kd_temperature)
         self.dump({"comm": train_step.runner.comm_report()})  # bucket choice and step schedules of this run
         self.logger.info(f"***** Running training ***** examples={len(train_ds)} epochs={a.num_epochs}")
         completed = 0
@@ -110,7 +110,7 @@ class ModelTrainer:
                     t_warm = time.perf_counter()
                 faults.maybe_inject(completed, acc.process_index)
                 if completed % 300 == 0:
-                    self.dump({"loss": loss.item(), "step": completed})
+                    self.dump({"loss": loss.item(), **kd_logs(train_step.engine), "step": completed})
                 if completed >= max_train_steps:
                     break
             torch.cuda.synchronize() if acc.device.type == "cuda" else None

@@ -50,9 +50,8 @@ def run(env, args):
     import numpy as np
     from torch.utils.data import DataLoader
 
-    from distributed_llms_example_amd.cli import build_data, maybe_apply_lora, model_config
+    from distributed_llms_example_amd.cli import build_data, build_models, kd_logs, maybe_apply_lora, model_config
     from distributed_llms_example_amd.data.collator import DataCollatorForSeq2Seq
-    from distributed_llms_example_amd.models import build_model, from_pretrained
     from distributed_llms_example_amd.ops.rng import manual_seed
     from distributed_llms_example_amd.parallel import collectives
     from distributed_llms_example_amd.parallel.sampler import DataPartitioner, ShardedBatchSampler
@@ -76,7 +75,7 @@ def run(env, args):
     if env.is_main_process:
         print(f"Train dataset size: {len(train_ds)}")
         print(f"Test dataset size: {len(eval_ds)}")
-    model = from_pretrained(args.model_ckpt) if os.path.isdir(args.model_ckpt or "") else build_model(cfg)
+    model, teacher = build_models(args, cfg)
     if cfg.gradient_checkpointing:
         model.gradient_checkpointing_enable()
     maybe_apply_lora(model, args, print if env.is_main_process else None)
@@ -84,7 +83,8 @@ def run(env, args):
         else torch.float32
     eng = TrainEngine(model, env, lr=args.learning_rate, weight_decay=0.0, max_grad_norm=None, dtype=dtype,
                       bucket_mb=args.bucket_mb or "auto", overlap=not args.no_overlap, no_decay=None,
-                      grad_reduce_dtype=args.grad_reduce_dtype, optim=args.optim)
+                      grad_reduce_dtype=args.grad_reduce_dtype, optim=args.optim, teacher=teacher,
+                      kd_alpha=args.kd_alpha, kd_temperature=args.kd_temperature)
     collator = DataCollatorForSeq2Seq.for_model(cfg, pad_to_multiple_of=8)
     # partition_dataset (ref/train-task.py:176-191)
     world = env.world_size
@@ -118,7 +118,7 @@ def run(env, args):
             completed += 1
             faults.maybe_inject(completed, env.rank)
             if completed % 100 == 0:
-                dump_metrics({"loss": float(loss), "step": completed}, env.is_main_process)
+                dump_metrics({"loss": float(loss), **kd_logs(eng), "step": completed}, env.is_main_process)
             if completed >= max_steps:
                 break
         eng.train(False)

@@ -20,10 +20,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("TRANSFORMERS_NO_ADVISORY_WARNINGS", "true")
 
-from distributed_llms_example_amd.cli import (base_parser, build_data, eval_batch_size, maybe_apply_lora,  # noqa: E402
-                                              model_config)
+from distributed_llms_example_amd.cli import (base_parser, build_data, build_models, eval_batch_size,  # noqa: E402
+                                              maybe_apply_lora, model_config)
 from distributed_llms_example_amd.data.collator import DataCollatorForSeq2Seq  # noqa: E402
-from distributed_llms_example_amd.models import build_model, from_pretrained  # noqa: E402
 from distributed_llms_example_amd.parallel.env import init_distributed  # noqa: E402
 from distributed_llms_example_amd.platform import valohai  # noqa: E402
 from distributed_llms_example_amd.train.callbacks import PrinterCallback  # noqa: E402
@@ -50,7 +49,7 @@ def run(args):
         print(f"Train dataset size: {len(train_ds)}")
         print(f"Test dataset size: {len(eval_ds)}")
     torch.manual_seed(args.seed)  # random-init runs (no pretrained weights offline) start identically
-    model = from_pretrained(args.model_ckpt) if os.path.isdir(args.model_ckpt or "") else build_model(cfg)
+    model, teacher = build_models(args, cfg)
     if cfg.gradient_checkpointing:
         model.gradient_checkpointing_enable()
     maybe_apply_lora(model, args, print if env.is_main_process else None)
@@ -63,10 +62,11 @@ def run(args):
         optim="adafactor" if args.optim == "adafactor" else "adamw_torch",
         bf16=None if args.precision is None else args.precision == "bf16",
         ddp_bucket_cap_mb=args.bucket_mb, overlap_comm=not args.no_overlap, grad_reduce_dtype=args.grad_reduce_dtype,
-        context_parallel_size=args.context_parallel,
+        context_parallel_size=args.context_parallel, kd_alpha=args.kd_alpha, kd_temperature=args.kd_temperature,
         coalesce_grad_accum=getattr(args, "coalesce_grad_accum", "auto"))
     trainer = Trainer(model=model, args=targs, tokenizer=tok, data_collator=DataCollatorForSeq2Seq.for_model(cfg),
-                      train_dataset=train_ds, eval_dataset=eval_ds, callbacks=[PrinterCallback], env=env)
+                      train_dataset=train_ds, eval_dataset=eval_ds, callbacks=[PrinterCallback], env=env,
+                      teacher=teacher)
     resume = True if args.resume_from == "latest" else args.resume_from
     trainer.train(resume_from_checkpoint=resume)
     trainer.save_model(output_dir)
