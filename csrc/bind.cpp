@@ -322,11 +322,22 @@ void ce_chunk_bwd(const Tensor& scale, Tensor& logits, const Tensor& labels, con
                   const optional<Tensor>& bias, int64_t c0, int64_t V, double eps, int64_t ignore, int64_t skip) {
   check_gpu(logits, "logits");
   TORCH_CHECK(logits.dim() == 2 && logits.scalar_type() == at::kBFloat16 && logits.stride(1) == 1 &&
-                  logits.stride(0) % 4 == 0 && logits.size(1) % 4 == 0, "ce_chunk_bwd: logits");
+                  logits.stride(0) % 4 == 0 && logits.size(1) % 4 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 8 == 0,
+              "ce_chunk_bwd: logits must be bf16 [N, Vc] with Vc % 4 == 0 and 8-B aligned rows");
   const int64_t N = logits.size(0), Vc = logits.size(1);
-  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_cuda() && labels.numel() == N && lse.numel() == N,
-              "ce_chunk_bwd: args");
-  const float* bp = (bias.has_value() && bias->defined()) ? bias->data_ptr<float>() : nullptr;
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_cuda() && scale.numel() >= 1, "ce_chunk_bwd: scale");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.numel() == N && labels.is_contiguous(),
+              "ce_chunk_bwd: labels");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.numel() == N && lse.is_contiguous(),
+              "ce_chunk_bwd: lse");
+  TORCH_CHECK(c0 >= 0 && c0 + Vc <= V, "ce_chunk_bwd: chunk outside the vocabulary");
+  TORCH_CHECK(skip >= 0 && skip < Vc, "ce_chunk_bwd: skip outside [0, Vc)");
+  const float* bp = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->numel() == V && bias->is_contiguous(),
+                "ce_chunk_bwd: bias fp32 [V]");
+    bp = bias->data_ptr<float>();
+  }
   if (N == 0) return;
   check_rc(dllm_ce_chunk_bwd(scale.data_ptr<float>(), logits.data_ptr(), logits.stride(0), labels.data_ptr<int64_t>(),
                              lse.data_ptr<float>(), bp, N, (int)Vc, (int)c0, (int)V, (float)eps, ignore, (int)skip,

@@ -11,6 +11,10 @@ using namespace dllm;
 
 namespace {
 
+// eps * mean_v(x_v).  Without smoothing the term is left out, not multiplied by 0: a banned token's -inf logit (BART
+// final_logits_bias) makes the row's sum of logits -inf, and 0 * -inf would turn a finite loss into NaN.
+DLLM_DEVICE float smooth_term(float eps, float sum_x, int V) { return eps != 0.f ? eps * sum_x / (float)V : 0.f; }
+
 template <typename T>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
                                                      const float* __restrict__ bias, float* __restrict__ loss_out,
@@ -66,7 +70,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
     if (y != ignore && y >= 0 && y < V) {
       float xy = Elem<T>::load(x + y);
       if (bias != nullptr) xy += bias[y];
-      loss = lse - (1.f - eps) * xy - eps * SX / (float)V;
+      loss = lse - (1.f - eps) * xy - smooth_term(eps, SX, V);
     }
     loss_out[row] = loss;
     lse_out[row] = lse;
@@ -162,7 +166,7 @@ __global__ __launch_bounds__(256) void ce_chunk_fwd_kernel(const uint16_t* __res
     if (last) {
       const float lse = cur.x + __logf(cur.y);
       const bool valid = y != ignore && y >= 0 && y < V;
-      loss_out[row] = valid ? lse - (1.f - eps) * cur.w - eps * cur.z / (float)V : 0.f;
+      loss_out[row] = valid ? lse - (1.f - eps) * cur.w - smooth_term(eps, cur.z, V) : 0.f;
       lse_out[row] = lse;
     }
   }
@@ -221,7 +225,7 @@ __global__ __launch_bounds__(256) void ce_merge_kernel(const f32x4* __restrict__
     const long y = labels[row];
     const bool valid = y != ignore && y >= 0 && y < V;
     const float lse = M + __logf(S);
-    loss_out[row] = valid ? lse - (1.f - eps) * xlab[row] - eps * SX / (float)V : 0.f;
+    loss_out[row] = valid ? lse - (1.f - eps) * xlab[row] - smooth_term(eps, SX, V) : 0.f;
     lse_out[row] = lse;
   }
 }

@@ -49,7 +49,7 @@ def _chunk_cols(N: int, V: int) -> int:
     c = int(mb * 2**20 / (2 * max(N, 1))) // 256 * 256
     c = max(256, min(c, (V + 255) // 256 * 256))
     if V % 8 and c >= V:  # a ragged vocabulary needs >= 2 chunks (the tail chunk re-covers aligned columns)
-        c = max(8, (V // 2 + 255) // 256 * 256)
+        c = max(8, min((V // 2 + 255) // 256 * 256, V // 8 * 8))  # V < 256: whole 8-groups, then the re-covering tail
     return c
 
 

@@ -36,7 +36,7 @@ Compiled instantiation -> test that runs it
         test_wgrad[*], test_wgrad_sched[*], test_wgrad_segs[*]
   colsum kernels
         test_colsum_acc[*], test_colsum_partials_acc[*]
-The CE epilogues (8 / 9) have per-row checks in tests/test_grads_gpu.py.
+The CE epilogues (8 / 9): tests/test_loss_kernels_gpu.py (per row / per element, persistent arm included).
 """
 import functools
 
