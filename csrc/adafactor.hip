@@ -324,7 +324,7 @@ __global__ __launch_bounds__(256) void af_fin_clip(const long* __restrict__ tab,
 }  // namespace
 
 // One Adafactor step over every unit of `tab` ([U + 1, AF_FIELDS] int64 on the device, planned and bounds-checked by
-// csrc/bind.cpp).  `tpart` holds 2 * n_tiles floats, `scal` 4 * U.  is_bf16: bf16 parameters with an fp32 master; else
+// csrc/bind_optim.cpp).  `tpart` holds 2 * n_tiles floats, `scal` 4 * U.  is_bf16: bf16 parameters with an fp32 master; else
 // fp32 parameters updated in place (master == nullptr).
 extern "C" int dllm_adafactor_step(void* param, float* master, const float* grad, float* rv, float* cst,
                                    const long* tab, int U, long n_tiles, float* scal, float* colpart, float* rowpart,

@@ -1,5 +1,5 @@
 // Geometry and unit-table layout of the Adafactor kernels (csrc/adafactor.hip), shared with the host code that plans
-// the table (csrc/bind.cpp adafactor_plan) so that both sides enumerate the same tiles and scratch offsets.
+// the table (csrc/bind_optim.cpp adafactor_plan) so that both sides enumerate the same tiles and scratch offsets.
 #pragma once
 
 // A unit (one transformers parameter: a whole flat segment, or one dim-0 slice of a fused one) is cut into tiles of

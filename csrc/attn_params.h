@@ -1,5 +1,5 @@
 // The attention contract: one parameter block for the three kernel families, filled by the host binding
-// (csrc/bind.cpp fill_common / fill_bwd) and passed by value to every kernel.
+// (csrc/bind_attn.cpp fill_common / fill_bwd) and passed by value to every kernel.
 //
 //   AttnParamsT<float>     AttnF32Params   csrc/attn_f32.hip   fp32, head dim 64
 //   AttnParamsT<uint16_t>  AttnHdParams    csrc/attn_hd.hip    bf16, head dims 32 .. 128 other than 64

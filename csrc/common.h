@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launchers.h"  // every launcher a translation unit defines is checked against its one declaration
+
 #define DLLM_HOST_DEVICE __host__ __device__ __forceinline__
 #define DLLM_DEVICE __device__ __forceinline__
 

@@ -46,8 +46,10 @@ namespace {
 
 constexpr int BM = 256, BN = 256, NT = 512;
 
-enum Epi { EPI_NONE = 0, EPI_RELU = 1, EPI_GELU = 2, EPI_DRELU = 3, EPI_DGELU = 4, EPI_GELU_TANH = 5,
-           EPI_DGELU_TANH = 6, EPI_DRELU_M = 7, EPI_GEGLU = 8, EPI_DGEGLU = 9 };
+enum Epi { EPI_NONE = GEMM_FUSED_EPI_NONE, EPI_RELU = GEMM_FUSED_EPI_RELU, EPI_GELU = GEMM_FUSED_EPI_GELU,
+           EPI_DRELU = GEMM_FUSED_EPI_DRELU, EPI_DGELU = GEMM_FUSED_EPI_DGELU, EPI_GELU_TANH = GEMM_FUSED_EPI_GELU_TANH,
+           EPI_DGELU_TANH = GEMM_FUSED_EPI_DGELU_TANH, EPI_DRELU_M = GEMM_FUSED_EPI_DRELU_M,
+           EPI_GEGLU = GEMM_FUSED_EPI_GEGLU, EPI_DGEGLU = GEMM_FUSED_EPI_DGEGLU };  // csrc/gemm_params.h
 
 DLLM_DEVICE int xcd_remap(int bid, int nblk) {
   const int q = nblk / 8, r = nblk % 8, x = bid % 8;

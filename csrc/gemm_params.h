@@ -1,6 +1,19 @@
-// Parameter block shared by csrc/gemm.hip and the host binding (csrc/bind.cpp).
+// Parameter blocks, epilogue and variant numbers shared by csrc/gemm.hip, csrc/gemm_fused.hip, csrc/gemm_w4.hip and
+// the host binding (csrc/bind_gemm.cpp).  The numbers are the Python-facing `epi` / `variant` integers.
 #pragma once
 #include <stdint.h>
+
+// csrc/gemm_w4.hip epilogues (dllm_gemm_w4's epi)
+enum { W4_EPI_NONE = 0, W4_EPI_RELU = 1, W4_EPI_DRELU_M = 7, W4_EPI_CEF = 8, W4_EPI_CEB = 9, W4_EPI_WG = 10,
+       W4_EPI_GELU = 11, W4_EPI_DGELU = 12 };
+
+// csrc/gemm_fused.hip epilogues (GemmFusedParams::epi; its enum Epi takes these values)
+enum { GEMM_FUSED_EPI_NONE = 0, GEMM_FUSED_EPI_RELU = 1, GEMM_FUSED_EPI_GELU = 2, GEMM_FUSED_EPI_DRELU = 3,
+       GEMM_FUSED_EPI_DGELU = 4, GEMM_FUSED_EPI_GELU_TANH = 5, GEMM_FUSED_EPI_DGELU_TANH = 6,
+       GEMM_FUSED_EPI_DRELU_M = 7, GEMM_FUSED_EPI_GEGLU = 8, GEMM_FUSED_EPI_DGEGLU = 9 };
+// csrc/gemm_fused.hip kernels (dllm_gemm_fused's variant): the staged BK = 32 kernel (any K % 32 == 0), the ping-pong
+// kernel (K % 64 == 0) and its persistent form
+enum { GEMM_FUSED_V_STAGED = 1, GEMM_FUSED_V_PP = 8, GEMM_FUSED_V_PP_PERSIST = 9 };
 
 struct GemmWgradParams {
   const uint16_t* A;  // [K][lda]

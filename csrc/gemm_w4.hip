@@ -53,9 +53,6 @@ namespace {
 // csrc/gemm.hip's split-K pass), or — one split — accumulates straight into the fp32 / bf16 C.
 // GELU (erf) FFN: forward NT + bias writing h and its dropout-scaled derivative (two outputs, as csrc/gemm_fused.hip's
 // epilogue 2), backward NN multiplying by that derivative and summing dU per 128 rows (csrc/gemm_fused.hip epilogue 4)
-enum { W4_EPI_NONE = 0, W4_EPI_RELU = 1, W4_EPI_DRELU_M = 7, W4_EPI_CEF = 8, W4_EPI_CEB = 9, W4_EPI_WG = 10,
-       W4_EPI_GELU = 11, W4_EPI_DGELU = 12 };
-
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8v;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;

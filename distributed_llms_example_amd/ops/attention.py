@@ -270,12 +270,12 @@ def _tuned(q, window=None, seg=None) -> bool:
 
 
 def _seg_args(q_seg, k_seg) -> tuple:
-    """The trailing segment arguments of attn_hd_* / attn_f32_* (csrc/bind.cpp): ids and block tables, or nothing."""
+    """The trailing segment arguments of attn_hd_* / attn_f32_* (csrc/bind_attn.cpp): ids and block tables, or nothing."""
     return () if q_seg is None else (q_seg.ids, k_seg.ids, q_seg.blk, k_seg.blk)
 
 
 def _glob_args(gk) -> dict:
-    """The global-key keyword arguments of attn_hd_* / attn_f32_* (csrc/bind.cpp): flags and block list, or nothing."""
+    """The global-key keyword arguments of attn_hd_* / attn_f32_* (csrc/bind_attn.cpp): flags and block list, or nothing."""
     return {} if gk is None else {"k_glob": gk.flags, "k_gblk": gk.blk}
 
 

@@ -121,7 +121,7 @@ class WgradDefer:
     @staticmethod
     def run(out, parts, beta):
         """``out (+)= Σ dY_iᵀ X_i`` over the window: the w4 weight-gradient kernel reading every kept segment in place
-        (csrc/bind.cpp gemm_wgrad_segs; equal-shaped segments, 32 per launch), else one GEMM over the concatenated
+        (csrc/bind_gemm.cpp gemm_wgrad_segs; equal-shaped segments, 32 per launch), else one GEMM over the concatenated
         operands.  A kept dY changed in place since it was kept (its version moved) fails loudly."""
         for dy2, _, v in parts:
             if dy2._version != v:

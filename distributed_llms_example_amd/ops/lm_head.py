@@ -221,7 +221,7 @@ def use_fused() -> bool:
 
 
 def fused_ok(h: torch.Tensor, w: torch.Tensor) -> bool:
-    """Shapes the GEMM-epilogue CE handles (csrc/bind.cpp check_lmhead_operands): bf16, d % 64 == 0, 16-B rows."""
+    """Shapes the GEMM-epilogue CE handles (csrc/bind_gemm.cpp lmhead_params): bf16, d % 64 == 0, 16-B rows."""
     return (use_fused() and h.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and h.shape[-1] % 64 == 0
             and w.stride(-1) == 1 and w.stride(0) % 8 == 0 and w.data_ptr() % 16 == 0 and h.data_ptr() % 16 == 0
             and _ext.use_native(h))

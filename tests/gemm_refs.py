@@ -298,7 +298,7 @@ def w4_persistent(epi, tiles, K, persist, cus):
 
 
 def wgrad_splits(tiles, K, cus):
-    """csrc/bind.cpp wgrad_splits (``cus``: the device's raw multi-processor count there)."""
+    """csrc/bind_gemm.cpp wgrad_splits (``cus``: the device's raw multi-processor count there)."""
     smax = max(1, min(K // 256, 64))
     best, bestc = 1, 1e30
     for s in range(1, smax + 1):
@@ -310,7 +310,7 @@ def wgrad_splits(tiles, K, cus):
 
 
 def wgrad_split_plan(K, M, N, lda, ldb, cus, splits_req=0):
-    """(splits, kchunk) of csrc/bind.cpp gemm_wgrad for A = [K, M] (row stride lda), B = [K, N] (ldb)."""
+    """(splits, kchunk) of csrc/bind_gemm.cpp gemm_wgrad for A = [K, M] (row stride lda), B = [K, N] (ldb)."""
     tiles = ((M + 255) // 256) * (N // 256)
     splits = splits_req if splits_req > 0 else wgrad_splits(tiles, K, cus)
     splits = max(1, min(splits, K // 256))
@@ -323,7 +323,7 @@ def wgrad_split_plan(K, M, N, lda, ldb, cus, splits_req=0):
 
 
 def wgrad_segs_plan(nseg, rows, M, N, lda, ldb, cus):
-    """(splits, kchunk, chunks per segment) of csrc/bind.cpp gemm_wgrad_segs."""
+    """(splits, kchunk, chunks per segment) of csrc/bind_gemm.cpp gemm_wgrad_segs."""
     tiles = ((M + 255) // 256) * (N // 256)
     want = wgrad_splits(tiles, rows * nseg, cus)
     chunks = max(1, min((want + nseg // 2) // nseg, rows // 64))

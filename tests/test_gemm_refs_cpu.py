@@ -5,7 +5,7 @@
 * ``dyadic`` operands meet the exactness precondition at every reduction length the GPU tests use, and an fp32 matmul of
   them, summed in another order, equals the fp64 one bit for bit;
 * the mask decoders invert scalar encoders written from the layout comments of csrc/gemm_params.h;
-* the launch-predicate mirrors reproduce the split counts documented above csrc/bind.cpp ``wgrad_splits``;
+* the launch-predicate mirrors reproduce the split counts documented above csrc/bind_gemm.cpp ``wgrad_splits``;
 * SENSITIVITY: the smallest plausible kernel faults, injected into a correct synthetic output at the persistent
   ping-pong shape (8448 x 4096), are rejected by the new checks — and, as a record of the gap they close, accepted by
   the whole-tensor numbers the GEMM tests used so far (``_rel < 8e-3``, ``_close(2e-2, 2e-2)`` at a 0.1 % share).
@@ -222,7 +222,7 @@ def test_mask_decoders_invert_the_documented_layouts():
 
 # ------------------------------------------------------------------------------------------------ predicate mirrors
 def test_wgrad_split_counts_documented_in_bind():
-    """The comment above csrc/bind.cpp wgrad_splits, on 256 CUs: 378 tiles -> 2, 216 -> 13, 9 / 36 at 512K tokens ->
+    """The comment above csrc/bind_gemm.cpp wgrad_splits, on 256 CUs: 378 tiles -> 2, 216 -> 13, 9 / 36 at 512K tokens ->
     28 / 7, 27 -> 28."""
     K = 512 * 1024
     assert R.wgrad_splits(378, 8192, 256) == 2 and R.wgrad_splits(378, K, 256) == 2

@@ -424,7 +424,7 @@ def test_bart_attention_bias_colsum_matches_column_reduction(sq_force, monkeypat
 
 def test_gemm_wgrad_w4_wide_leading_dim():
     """A [K, M] view of a 40000-column buffer with one split requested: its k-rows span > 4 GB, past one buffer
-    descriptor's 32-bit range — the binding raises the split count until each split's span fits (csrc/bind.cpp)."""
+    descriptor's 32-bit range — the binding raises the split count until each split's span fits (csrc/bind_gemm.cpp)."""
     torch.manual_seed(3)
     K, M, N, LD = 65536, 256, 256, 40000
     af = torch.empty(K, LD, device=DEV, dtype=torch.bfloat16)
@@ -466,7 +466,7 @@ def test_deferred_weight_gradients_gpu(model, monkeypatch):
 
 @pytest.mark.parametrize("nseg,rows,M,N", [(5, 1024, 520, 512), (16, 192, 768, 768), (32, 64, 256, 256)])
 def test_gemm_wgrad_segs_matches_fp64(nseg, rows, M, N):
-    """The w4 weight-gradient mode over deferred micro-batch segments read in place (csrc/bind.cpp gemm_wgrad_segs):
+    """The w4 weight-gradient mode over deferred micro-batch segments read in place (csrc/bind_gemm.cpp gemm_wgrad_segs):
     Σ_i a_iᵀ b_i + C for fp32 / bf16 C, ragged M, strided segments."""
     torch.manual_seed(4)
     af = torch.randn(nseg, rows, M + 8, device=DEV, dtype=torch.bfloat16)

@@ -301,7 +301,7 @@ def test_gemm_wgrad_explicit_splits_match():
 
 def test_gemm_wgrad_auto_splits_fill_the_last_round():
     """378 output tiles (a t5 LM-head weight gradient: ragged vocab rows x 768) on 256 CUs: one tile per workgroup would
-    leave the second round half empty; the auto split count (csrc/bind.cpp wgrad_splits) takes 2 (3 full rounds)."""
+    leave the second round half empty; the auto split count (csrc/bind_gemm.cpp wgrad_splits) takes 2 (3 full rounds)."""
     torch.manual_seed(2)
     K, M, N = 8192, 32128, 768
     a = torch.randn(K, M, device=DEV, dtype=torch.bfloat16)

@@ -466,3 +466,27 @@ def test_ce_chunk_bindings_reject_before_launch():
     with pytest.raises(RuntimeError, match="vocabulary"):
         C.ce_chunk_bwd(sc, lg, labels, lse, bias, V - 8, V, 0.1, IGN, 0)
     torch.cuda.synchronize()
+
+
+def test_ce_bindings_reject_cpu_operands():
+    """ce_fwd (labels, bias) and ce_chunk_fwd (labels, state, bias) hand these pointers to their kernels: a tensor
+    that is not on the GPU must raise.  Zero-row inputs: the bindings check everything and return before launching, so
+    a missing check shows as "did not raise" and never as a kernel reading a host pointer."""
+    C = _C()
+    V = 8
+    labels, rows = torch.zeros(0, dtype=torch.long, device=DEV), torch.zeros(0, device=DEV)
+    bias = torch.zeros(V, device=DEV)
+    cases = [
+        (C.ce_fwd, (torch.zeros(0, V, device=DEV), labels, bias, 0.1, IGN), (1, 2)),
+        (C.ce_chunk_fwd, (torch.zeros(0, V, device=DEV, dtype=BF16), labels, bias, torch.zeros(0, 4, device=DEV), rows,
+                          rows.clone(), 0, V, 0.1, IGN, True, True, 0), (1, 2, 3)),
+    ]
+    for call, args, slots in cases:
+        call(*args)  # well-formed: passes
+        for i in slots:
+            bad = list(args)
+            bad[i] = args[i].cpu()
+            with pytest.raises(RuntimeError):
+                call(*bad)
+                pytest.fail(f"{call.__name__} accepted a CPU tensor as argument {i}")
+    torch.cuda.synchronize()

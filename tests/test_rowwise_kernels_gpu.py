@@ -448,6 +448,33 @@ def test_backward_bindings_reject_what_the_kernels_cannot_address():
     torch.cuda.synchronize()
 
 
+def _rejects_cpu_operands(call, args, slots):
+    """The well-formed call passes; with any one of `slots` replaced by its CPU copy it raises.  Zero-row inputs: the
+    bindings check everything and return before launching, so a missing check shows as "did not raise" and never as a
+    kernel reading a host pointer."""
+    call(*args)
+    for i in slots:
+        bad = list(args)
+        bad[i] = args[i].cpu()
+        with pytest.raises(RuntimeError):
+            call(*bad)
+            pytest.fail(f"{call.__name__} accepted a CPU tensor as argument {i}")
+
+
+def test_rowwise_bindings_reject_cpu_operands():
+    """norm_fwd (w, resid, b), norm_bwd (dout, dw_acc) and act_bwd (dy) hand these pointers to their kernels: a tensor
+    that is not on the GPU must raise."""
+    C = _ext.native()
+    d = 8
+    x = torch.zeros(0, d, device=DEV)
+    w, b, stat = torch.ones(d, device=DEV), torch.zeros(d, device=DEV), torch.zeros(0, device=DEV)
+    _rejects_cpu_operands(C.norm_fwd, (x, x.clone(), w, b, 1e-6, 0.0, 0, 1, True), slots=(1, 2, 3))
+    _rejects_cpu_operands(C.norm_bwd, (x.clone(), None, x, w, b, stat, stat.clone(), 0.0, 0, 1, False,
+                                       torch.zeros(d, device=DEV), torch.zeros(d, device=DEV)), slots=(0, 11))
+    _rejects_cpu_operands(C.act_bwd, (x.clone(), x, 0, False, 0.0, 0), slots=(0,))
+    torch.cuda.synchronize()
+
+
 # --------------------------------------------------------------------------------------------------------- sq_norm
 @pytest.mark.parametrize("dt", ["bf16", "fp32"])
 @pytest.mark.parametrize("n", [4, 1048580, 3000004])  # 1024 x 256 x 4 = 1,048,576: the next 4 start the second trip

@@ -1,8 +1,8 @@
 """Build the in-tree native extension ``distributed_llms_example_amd/_C*.so`` for gfx950.
 
 No hipify, no CUDA compatibility layer: every ``csrc/*.hip`` file is plain HIP compiled by
-``hipcc --offload-arch=gfx950`` into an object with C-ABI launchers; ``csrc/bind.cpp`` (torch +
-pybind11 glue, host-only) is compiled by the host C++ compiler with torch's headers; both are linked
+``hipcc --offload-arch=gfx950`` into an object with C-ABI launchers; ``csrc/bind*.cpp`` (torch +
+pybind11 glue, host-only) are compiled by the host C++ compiler with torch's headers; both are linked
 into one shared object next to the Python package so it travels with the repo snapshot.
 Incremental by content: an object is rebuilt when the hash of its source, the headers or its command line changed
 (``<obj>.sha256`` sidecars).  Every link writes the provenance record ``distributed_llms_example_amd/_C.build.json``
@@ -111,7 +111,7 @@ def build(force: bool = False, jobs: int = 8, verbose: bool = True) -> str:
         obj = os.path.join(BUILD, os.path.basename(src) + ".o")
         objs.append(obj)
         cmd = ([HIPCC, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast",
-                "-munsafe-fp-atomics"] + EXTRA_FLAGS.get(os.path.basename(src), [])
+                "-munsafe-fp-atomics", "-Werror=missing-prototypes"] + EXTRA_FLAGS.get(os.path.basename(src), [])
                + (_ENV_FLAGS if _ENV_FLAGS_SRC in ("", os.path.basename(src)) else [])
                + ["-I", CSRC, "-c", src, "-o", obj])
         key = _key(src, headers, cmd)
