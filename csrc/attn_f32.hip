@@ -11,6 +11,9 @@
 // Global keys (AttnParamsT::k_glob / k_gblk, only with a window): as in csrc/attn_hd.hip, forward and dQ walk the band
 // merged with the listed blocks that hold a global key (BlockWalk), dK / dV every query block from a key block with
 // one.
+// Block lists (AttnParamsT::kl_ptr / kl_idx / ql_ptr / ql_idx): as in csrc/attn_hd.hip, forward and dQ follow the query
+// block's list of key blocks and dK / dV the key block's list of query blocks, repeats included (list_range), in
+// instantiations of their own (template parameter LISTS): the kernels of every other call are the code they were.
 //
 // Layout trick (no transposes through LDS for P or dS): the 16x16x4 f32 MFMA's C/D map puts rows 4g .. 4g+3
 // (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction index k = g from
@@ -82,7 +85,7 @@ DLLM_DEVICE f32x4 rd_col4(const float* tr, int col, int r4) {
 // the segment hooks (3, 2, 2): with it the unsegmented fp32 step measures as before, at fewer registers
 // (profiles/packing_regression_gate.txt; without it 0.7 % slower).
 // ================================================================================================ forward
-template <bool DROP>
+template <bool DROP, bool LISTS = false>
 __global__ __launch_bounds__(NT, 3) void attn_f32_fwd_kernel(AttnF32Params P) {
   __shared__ __attribute__((aligned(16))) float Ks[BKY * D];
   __shared__ __attribute__((aligned(16))) float Vt[D * BKY];
@@ -189,7 +192,15 @@ __global__ __launch_bounds__(NT, 3) void attn_f32_fwd_kernel(AttnF32Params P) {
       }
     }
   };
-  if (P.k_glob == nullptr) {  // the walk as it was before the global keys: the band (or everything), segment skips
+  if constexpr (LISTS) {
+    // follow the query block's list of key blocks, repeats included (no causal, window, segments or global keys here)
+    int li, le;
+    list_range(P, P.kl_ptr, h, (P.Sq + 63) / 64, (int)blockIdx.x, li, le);
+    for (; li < le; ++li) {
+      const int k0 = list_block(P.kl_idx, li, (P.Sk + 63) / 64);
+      if (k0 >= 0) block(k0);
+    }
+  } else if (P.k_glob == nullptr) {  // the walk as it was before the global keys: the band (or everything), segment skips
     for (int k0 = kstart; k0 < kend; k0 += BKY) {
       if (seg_apart(P, b, q0, k0)) continue;
       block(k0);
@@ -228,7 +239,7 @@ __global__ __launch_bounds__(NT) void attn_f32_delta_kernel(AttnF32Params P) {
   if (r < rows && j == 0) P.delta[r] = s;
 }
 
-template <bool DROP>
+template <bool DROP, bool LISTS = false>
 __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
   __shared__ __attribute__((aligned(16))) float Ks[BKY * D];
   __shared__ __attribute__((aligned(16))) float Kt[D * BKY];
@@ -336,7 +347,15 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
       dlut_add_diagonals(P, h, q0, k0, Ds, tid);
     }
   };
-  if (P.k_glob == nullptr) {  // the walk as it was before the global keys: the band (or everything), segment skips
+  if constexpr (LISTS) {
+    // follow the query block's list of key blocks, repeats included (no causal, window, segments or global keys here)
+    int li, le;
+    list_range(P, P.kl_ptr, h, (P.Sq + 63) / 64, (int)blockIdx.x, li, le);
+    for (; li < le; ++li) {
+      const int k0 = list_block(P.kl_idx, li, (P.Sk + 63) / 64);
+      if (k0 >= 0) block(k0);
+    }
+  } else if (P.k_glob == nullptr) {  // the walk as it was before the global keys: the band (or everything), segment skips
     for (int k0 = kstart; k0 < kend; k0 += BKY) {
       if (seg_apart(P, b, q0, k0)) continue;
       block(k0);
@@ -351,7 +370,7 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
   }
 }
 
-template <bool DROP>
+template <bool DROP, bool LISTS = false>
 __global__ __launch_bounds__(NT, 2) void attn_f32_dkdv_kernel(AttnF32Params P) {
   __shared__ __attribute__((aligned(16))) float Qs[BQ * D];
   __shared__ __attribute__((aligned(16))) float Qt[D * BQ];
@@ -396,69 +415,19 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dkdv_kernel(AttnF32Params P) {
   bool glob_blk;  // the block holds a valid global key: every query block sees it
   const int kwin = key_window(P, b, k0, key, kok, glob_blk);
   if (!glob_blk) band_range(P, k0, qstart, qend);
-  for (int q0 = qstart; q0 < qend; q0 += BQ) {
-    if (seg_apart(P, b, q0, k0)) continue;
-    __syncthreads();
-    stage<true, true>(qb, P.q_ss, q0, P.Sq, Qs, Qt, tid);
-    stage<true, true>(ob, P.do_ss, q0, P.Sq, Os, Ot, tid);
-    stage_bias(P, h, q0, k0, Ls, tid, 1.f);
-    if (tid < BQ) {
-      const int r = q0 + tid;
-      const bool ok = r < P.Sq;
-      Rl[tid] = ok ? P.lse[(long)bh * P.Sq + r] : INFINITY;
-      Rd[tid] = ok ? P.delta[(long)bh * P.Sq + r] : 0.f;
-      if (DROP) Rh[tid] = mix32(seed, (uint32_t)((long)bh * P.Sq + min(r, P.Sq - 1)));
-      if (P.q_seg) Rs[tid] = seg_at(P.q_seg, b, P.Sq, r);
+  if constexpr (LISTS) {
+    // follow the key block's list of query blocks — the transpose of the key lists, repeats included
+    int li, le;
+    list_range(P, P.ql_ptr, h, (P.Sk + 63) / 64, (int)blockIdx.x, li, le);
+    for (; li < le; ++li) {
+      const int q0 = list_block(P.ql_idx, li, (P.Sq + 63) / 64);
+      if (q0 < 0) continue;
+#include "attn_f32_dkdv_block.h"
     }
-    __syncthreads();
-    const uint32_t vis = kok ? seg_bits(P, Rs, ksg, g) : 0u;  // key valid and of the rows' segments
-    f32x4 sc[4], dp[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      float qf[16], of[16];
-      rd_row16(Qs, 16 * t + c, g, qf);
-      rd_row16(Os, 16 * t + c, g, of);
-      sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        sc[t] = mma(qf[s], kf[s], sc[t]);
-        dp[t] = mma(of[s], vf[s], dp[t]);
-      }
-    }
-    // sc[t][i] = S[row = q0 + 16 t + 4 g + i][key]; pd = kept P, sc <- dS
-    f32x4 pd[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int rl = 16 * t + 4 * g + i, row = q0 + rl;
-        float x = sc[t][i] * P.scale;
-        if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) ||
-                         (P.window >= 0 && off_band_w(kwin, row, key));
-        const float pr = msk ? 0.f : __expf(x - Rl[rl]);
-        const bool kp = DROP ? keep_key(Rh[rl], key, P.thr) : true;
-        const float dpk = kp ? dp[t][i] * dscale : 0.f;
-        pd[t][i] = kp ? pr * dscale : 0.f;
-        sc[t][i] = pr * (dpk - Rd[rl]);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const f32x4 oa = rd_col4(Ot, 16 * dt + c, 16 * t + 4 * g);
-        const f32x4 qa = rd_col4(Qt, 16 * dt + c, 16 * t + 4 * g);
-        dv[dt] = mma(pd[t][0], oa.x, dv[dt]);
-        dv[dt] = mma(pd[t][1], oa.y, dv[dt]);
-        dv[dt] = mma(pd[t][2], oa.z, dv[dt]);
-        dv[dt] = mma(pd[t][3], oa.w, dv[dt]);
-        dk[dt] = mma(sc[t][0], qa.x, dk[dt]);
-        dk[dt] = mma(sc[t][1], qa.y, dk[dt]);
-        dk[dt] = mma(sc[t][2], qa.z, dk[dt]);
-        dk[dt] = mma(sc[t][3], qa.w, dk[dt]);
-      }
+  } else {
+    for (int q0 = qstart; q0 < qend; q0 += BQ) {
+      if (seg_apart(P, b, q0, k0)) continue;
+#include "attn_f32_dkdv_block.h"
     }
   }
   // dk[dt][i] = dK[key = k0 + 16 w + 4 g + i][d = 16 dt + c]
@@ -481,7 +450,10 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dkdv_kernel(AttnF32Params P) {
 extern "C" int dllm_attn_f32_fwd(AttnF32Params* pp, hipStream_t st) {
   const AttnF32Params& P = *pp;
   dim3 grid((P.Sq + BQ - 1) / BQ, P.B * P.H);
-  if (P.p_drop > 0.f) hipLaunchKernelGGL(attn_f32_fwd_kernel<true>, grid, dim3(NT), 0, st, P);
+  if (P.kl_ptr != nullptr) {  // the instantiations that follow block lists
+    if (P.p_drop > 0.f) hipLaunchKernelGGL((attn_f32_fwd_kernel<true, true>), grid, dim3(NT), 0, st, P);
+    else hipLaunchKernelGGL((attn_f32_fwd_kernel<false, true>), grid, dim3(NT), 0, st, P);
+  } else if (P.p_drop > 0.f) hipLaunchKernelGGL(attn_f32_fwd_kernel<true>, grid, dim3(NT), 0, st, P);
   else hipLaunchKernelGGL(attn_f32_fwd_kernel<false>, grid, dim3(NT), 0, st, P);
   DLLM_CHECK_LAUNCH();
   return 0;
@@ -493,7 +465,15 @@ extern "C" int dllm_attn_f32_bwd(AttnF32Params* pp, hipStream_t st) {
   hipLaunchKernelGGL(attn_f32_delta_kernel, dim3((unsigned)((rows + NT / 16 - 1) / (NT / 16))), dim3(NT), 0, st, P);
   DLLM_CHECK_LAUNCH();
   dim3 gq((P.Sq + BQ - 1) / BQ, P.B * P.H), gk((P.Sk + BKY - 1) / BKY, P.B * P.H);
-  if (P.p_drop > 0.f) {
+  if (P.kl_ptr != nullptr) {  // the instantiations that follow block lists
+    if (P.p_drop > 0.f) {
+      hipLaunchKernelGGL((attn_f32_dq_kernel<true, true>), gq, dim3(NT), 0, st, P);
+      hipLaunchKernelGGL((attn_f32_dkdv_kernel<true, true>), gk, dim3(NT), 0, st, P);
+    } else {
+      hipLaunchKernelGGL((attn_f32_dq_kernel<false, true>), gq, dim3(NT), 0, st, P);
+      hipLaunchKernelGGL((attn_f32_dkdv_kernel<false, true>), gk, dim3(NT), 0, st, P);
+    }
+  } else if (P.p_drop > 0.f) {
     hipLaunchKernelGGL(attn_f32_dq_kernel<true>, gq, dim3(NT), 0, st, P);
     hipLaunchKernelGGL(attn_f32_dkdv_kernel<true>, gk, dim3(NT), 0, st, P);
   } else {

@@ -7,8 +7,8 @@
 // (its output row is 0) — parallel/context.py _merge combines blocks by it.
 //
 // The real head dim D (D % 8 == 0, 32 <= D <= DP) is a runtime field: columns D .. DP-1 are staged as zeros and never
-// stored.  bias / kpm / causal / window are runtime flags; only DP and DROP are template parameters (24 kernel
-// instantiations).
+// stored.  bias / kpm / causal / window are runtime flags; only DP, DROP and LISTS are template parameters (24 kernel
+// instantiations, and 18 that follow block lists).
 //
 // Sliding window (AttnParamsT::window >= 0, LongT5-local; Sq == Sk, not causal): forward and dQ walk only the key
 // blocks that intersect [q0 - w, q0 + 63 + w], dK / dV only the query blocks that intersect [k0 - w, k0 + 63 + w]
@@ -27,6 +27,15 @@
 // for bit); dK / dV walk every query block from a key block with a valid global key (key_window: a vote over the
 // block's flags) and the band from the others.  Blocks neither in the band nor listed are never loaded.  A runtime
 // flag like the window.
+//
+// Block lists (AttnParamsT::kl_ptr / kl_idx / ql_ptr / ql_idx, block-sparse attention such as BigBird's): forward and
+// dQ follow the query block's list of 64-key blocks, dK / dV the key block's list of 64-query blocks (attn_small.h
+// list_range / list_block) — a third loop over the same block body.  A block listed n times is walked n times and so
+// counts n times (attn_params.h says why that is the contract); unlisted blocks are never loaded.  The third loop
+// lives in instantiations of its own (template parameter LISTS, head dims other than 32): in the kernels that serve
+// every other call it cost scalar spills (dQ) or occupancy, so those are the code they were
+// (profiles/attn_block_lists.txt).  No causal, window, segments or global keys with lists, and none at head dim 32
+// (the launchers refuse, the op takes the composite).
 //
 // Layout trick of csrc/attn_f32.hip, carried over to the 16x16x32 bf16 MFMA: its C/D map puts rows 4g .. 4g+3
 // (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction indices k = 8g + j
@@ -142,7 +151,7 @@ constexpr int occ_dq(int DP, bool DROP) {
 constexpr int occ_dkdv(int DP) { return DP == 32 ? 3 : DP == 64 ? 3 : 2; }
 
 // ================================================================================================ forward
-template <int DP, bool DROP>
+template <int DP, bool DROP, bool LISTS = false>
 __global__ __launch_bounds__(NT, occ_fwd(DP, DROP)) void attn_hd_fwd_kernel(AttnHdParams P) {
   constexpr int KS = DP / 32, DT = DP / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[Img<DP>::SIZE];
@@ -171,7 +180,16 @@ __global__ __launch_bounds__(NT, occ_fwd(DP, DROP)) void attn_hd_fwd_kernel(Attn
   if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
   int kstart = 0;
   band_range(P, q0, kstart, kend);
-  if constexpr (DP == 32) {
+  if constexpr (LISTS) {
+    // follow the query block's list of key blocks, repeats included (no causal, window, segments or global keys here)
+    int li, le;
+    list_range(P, P.kl_ptr, h, (P.Sq + 63) / 64, (int)blockIdx.x, li, le);
+    for (; li < le; ++li) {
+      const int k0 = list_block(P.kl_idx, li, (P.Sk + 63) / 64);
+      if (k0 < 0) continue;
+#include "attn_hd_fwd_block.h"
+    }
+  } else if constexpr (DP == 32) {
     // Head dim 32 has no global keys (above): the loop and the block body as they were, in place.  (Through the lambda
     // below its dropout instantiation no longer fits the 80 registers of its 6 waves, with or without a second loop.)
     for (int k0 = kstart; k0 < kend; k0 += BKY) {
@@ -228,7 +246,7 @@ __global__ __launch_bounds__(NT) void attn_hd_delta_kernel(AttnHdParams P) {
   if (r < rows && j == 0) P.delta[r] = s;
 }
 
-template <int DP, bool DROP>
+template <int DP, bool DROP, bool LISTS = false>
 __global__ __launch_bounds__(NT, occ_dq(DP, DROP)) void attn_hd_dq_kernel(AttnHdParams P) {
   constexpr int KS = DP / 32, DT = DP / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[Img<DP>::SIZE];
@@ -266,7 +284,16 @@ __global__ __launch_bounds__(NT, occ_dq(DP, DROP)) void attn_hd_dq_kernel(AttnHd
   if (P.causal) kend = min(P.Sk, max(0, q0 + BQ + P.causal_off));
   int kstart = 0;
   band_range(P, q0, kstart, kend);
-  if constexpr (DP == 32) {
+  if constexpr (LISTS) {
+    // follow the query block's list of key blocks, repeats included, as the forward
+    int li, le;
+    list_range(P, P.kl_ptr, h, (P.Sq + 63) / 64, (int)blockIdx.x, li, le);
+    for (; li < le; ++li) {
+      const int k0 = list_block(P.kl_idx, li, (P.Sk + 63) / 64);
+      if (k0 < 0) continue;
+#include "attn_hd_dq_block.h"
+    }
+  } else if constexpr (DP == 32) {
     // Head dim 32 has no global keys: the loop and the block body of before, in place, as in the forward
     for (int k0 = kstart; k0 < kend; k0 += BKY) {
       if (seg_apart(P, b, q0, k0)) continue;
@@ -297,7 +324,7 @@ __global__ __launch_bounds__(NT, occ_dq(DP, DROP)) void attn_hd_dq_kernel(AttnHd
   }
 }
 
-template <int DP, bool DROP>
+template <int DP, bool DROP, bool LISTS = false>
 __global__ __launch_bounds__(NT, occ_dkdv(DP)) void attn_hd_dkdv_kernel(AttnHdParams P) {
   constexpr int KS = DP / 32, DT = DP / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Qs[Img<DP>::SIZE];
@@ -334,60 +361,19 @@ __global__ __launch_bounds__(NT, occ_dkdv(DP)) void attn_hd_dkdv_kernel(AttnHdPa
   int kwin = P.window;
   if constexpr (DP != 32) kwin = key_window(P, b, k0, key, kok, glob_blk);  // no global keys at head dim 32
   if (!glob_blk) band_range(P, k0, qstart, qend);
-  for (int q0 = qstart; q0 < qend; q0 += BQ) {
-    if (seg_apart(P, b, q0, k0)) continue;
-    __syncthreads();
-    stage<DP>(qb, P.q_ss, q0, P.Sq, P.D, Qs, tid);
-    stage<DP>(ob, P.do_ss, q0, P.Sq, P.D, Os, tid);
-    stage_bias(P, h, q0, k0, Ls, tid, LOG2E);
-    if (tid < BQ) {
-      const int r = q0 + tid;
-      const bool ok = r < P.Sq;
-      Rl[tid] = ok ? P.lse[(long)bh * P.Sq + r] : INFINITY;
-      Rd[tid] = ok ? P.delta[(long)bh * P.Sq + r] : 0.f;
-      if (DROP) Rh[tid] = mix32(seed, (uint32_t)((long)bh * P.Sq + min(r, P.Sq - 1)));
-      if (P.q_seg) Rs[tid] = seg_at(P.q_seg, b, P.Sq, r);
+  if constexpr (LISTS) {
+    // follow the key block's list of query blocks — the transpose of the key lists, repeats included
+    int li, le;
+    list_range(P, P.ql_ptr, h, (P.Sk + 63) / 64, (int)blockIdx.x, li, le);
+    for (; li < le; ++li) {
+      const int q0 = list_block(P.ql_idx, li, (P.Sq + 63) / 64);
+      if (q0 < 0) continue;
+#include "attn_hd_dkdv_block.h"
     }
-    __syncthreads();
-    const uint32_t vis = kok ? seg_bits(P, Rs, ksg, g) : 0u;  // key valid and of the rows' segments
-    f32x4 sc[4], dp[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        sc[t] = mma(ld_row<DP>(Qs, 16 * t + c, ks, g), kf[ks], sc[t]);
-        dp[t] = mma(ld_row<DP>(Os, 16 * t + c, ks, g), vf[ks], dp[t]);
-      }
-    }
-    // sc[t][i] = S[row = q0 + 16 t + 4 g + i][key]; pd = kept P, sc <- dS
-    f32x4 pd[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int rl = 16 * t + 4 * g + i, row = q0 + rl;
-        float x = sc[t][i] * scale2;
-        if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
-        const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) ||
-                         (DP == 32 ? off_band(P, row, key) : (P.window >= 0 && off_band_w(kwin, row, key)));
-        const float pr = msk ? 0.f : ex2(x - Rl[rl]);
-        const bool kp = DROP ? keep_key(Rh[rl], key, P.thr) : true;
-        const float dpk = kp ? dp[t][i] * dscale : 0.f;
-        pd[t][i] = kp ? pr * dscale : 0.f;
-        sc[t][i] = pr * (dpk - Rd[rl]);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const bf16x8v pb = pack8(pd[2 * u], pd[2 * u + 1]);
-      const bf16x8v sb = pack8(sc[2 * u], sc[2 * u + 1]);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        dv[dt] = mma(ld_tr2<DP>(Os, 32 * u, 16 * dt, c, g), pb, dv[dt]);
-        dk[dt] = mma(ld_tr2<DP>(Qs, 32 * u, 16 * dt, c, g), sb, dk[dt]);
-      }
+  } else {
+    for (int q0 = qstart; q0 < qend; q0 += BQ) {
+      if (seg_apart(P, b, q0, k0)) continue;
+#include "attn_hd_dkdv_block.h"
     }
   }
   // dk[dt][i] = dK[key][d = 16 dt + 4 g + i] / scale
@@ -407,6 +393,14 @@ __global__ __launch_bounds__(NT, occ_dkdv(DP)) void attn_hd_dkdv_kernel(AttnHdPa
 template <int DP>
 int launch_fwd(const AttnHdParams& P, hipStream_t st) {
   dim3 grid((P.Sq + BQ - 1) / BQ, P.B * P.H);
+  if constexpr (DP != 32) {  // the instantiations that follow block lists (none at head dim 32: refused before)
+    if (P.kl_ptr != nullptr) {
+      if (P.p_drop > 0.f) hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, true, true>), grid, dim3(NT), 0, st, P);
+      else hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, false, true>), grid, dim3(NT), 0, st, P);
+      DLLM_CHECK_LAUNCH();
+      return 0;
+    }
+  }
   if (P.p_drop > 0.f) hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, true>), grid, dim3(NT), 0, st, P);
   else hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, false>), grid, dim3(NT), 0, st, P);
   DLLM_CHECK_LAUNCH();
@@ -416,6 +410,19 @@ int launch_fwd(const AttnHdParams& P, hipStream_t st) {
 template <int DP>
 int launch_bwd(const AttnHdParams& P, hipStream_t st) {
   dim3 gq((P.Sq + BQ - 1) / BQ, P.B * P.H), gk((P.Sk + BKY - 1) / BKY, P.B * P.H);
+  if constexpr (DP != 32) {  // the instantiations that follow block lists, as in launch_fwd
+    if (P.kl_ptr != nullptr) {
+      if (P.p_drop > 0.f) {
+        hipLaunchKernelGGL((attn_hd_dq_kernel<DP, true, true>), gq, dim3(NT), 0, st, P);
+        hipLaunchKernelGGL((attn_hd_dkdv_kernel<DP, true, true>), gk, dim3(NT), 0, st, P);
+      } else {
+        hipLaunchKernelGGL((attn_hd_dq_kernel<DP, false, true>), gq, dim3(NT), 0, st, P);
+        hipLaunchKernelGGL((attn_hd_dkdv_kernel<DP, false, true>), gk, dim3(NT), 0, st, P);
+      }
+      DLLM_CHECK_LAUNCH();
+      return 0;
+    }
+  }
   if (P.p_drop > 0.f) {
     hipLaunchKernelGGL((attn_hd_dq_kernel<DP, true>), gq, dim3(NT), 0, st, P);
     hipLaunchKernelGGL((attn_hd_dkdv_kernel<DP, true>), gk, dim3(NT), 0, st, P);
@@ -433,7 +440,7 @@ int launch_bwd(const AttnHdParams& P, hipStream_t st) {
 extern "C" int dllm_attn_hd_fwd(AttnHdParams* pp, hipStream_t st) {
   const AttnHdParams& P = *pp;
   if (P.D < 32 || P.D > 128 || P.D % 8) return -1;
-  if (P.D == 32 && P.k_glob != nullptr) return -2;  // the binding checks it first
+  if (P.D == 32 && (P.k_glob != nullptr || P.kl_ptr != nullptr)) return -2;  // the binding checks it first
   switch ((P.D + 31) / 32) {
     case 1: return launch_fwd<32>(P, st);
     case 2: return launch_fwd<64>(P, st);
@@ -445,7 +452,7 @@ extern "C" int dllm_attn_hd_fwd(AttnHdParams* pp, hipStream_t st) {
 extern "C" int dllm_attn_hd_bwd(AttnHdParams* pp, hipStream_t st) {
   const AttnHdParams& P = *pp;
   if (P.D < 32 || P.D > 128 || P.D % 8) return -1;
-  if (P.D == 32 && P.k_glob != nullptr) return -2;
+  if (P.D == 32 && (P.k_glob != nullptr || P.kl_ptr != nullptr)) return -2;
   const long rows = (long)P.B * P.H * P.Sq;
   hipLaunchKernelGGL(attn_hd_delta_kernel, dim3((unsigned)((rows + NT / 16 - 1) / (NT / 16))), dim3(NT), 0, st, P);
   DLLM_CHECK_LAUNCH();

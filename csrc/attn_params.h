@@ -35,6 +35,22 @@
 // compose with kpm, the bias LUT (indexed by j - i as always) and dropout (the keep hash still indexes (b, h, row,
 // key)), not with causal or segments (the binding rejects both); csrc/attn.hip has none, and csrc/attn_hd.hip none at
 // head dim 32 (the binding rejects it).
+// Block lists (block-sparse attention, BigBird): with kl_ptr / kl_idx / ql_ptr / ql_idx given (all four or none) the
+// walks follow explicit lists of 64-blocks instead of a range. nq = ceil(Sq / 64), nk = ceil(Sk / 64); kl_ptr is
+// [Hl, nq + 1] and ql_ptr [Hl, nk + 1] (CSR row starts into kl_idx / ql_idx, both [nnz]), Hl = H or 1 (one list shared
+// by all heads), the same for every batch row. For head h and query block x, forward and dQ visit the key blocks
+// kl_idx[kl_ptr[h][x] .. kl_ptr[h][x + 1]) in list order; dK / dV visit, for a key block, the query blocks of ql_idx
+// alike — the transpose of the key lists, with the same multiplicities (the host builds both, ops/attention.py
+// block_lists). Key j contributes to query i once per occurrence of block j / 64 in the list of block i / 64, if
+// key_ok: a block listed n times is visited n times, and the online softmax, dS and the bias gradient count its keys n
+// times (as a dense mask: + log n on the scores). BigBird's own plans repeat blocks, so this is the contract and not
+// an accident. An empty list gives rows without a visible key (output 0, LSE +inf); a key block in no list gets
+// dK = dV = 0; entries outside [0, nk) / [0, nq) are passed over, as BlockWalk does, and row starts are clamped to
+// [0, nnz]; blocks not listed are never loaded. A list of every block once, ascending, is the list-free call bit for
+// bit. Everything in the walk is uniform over the workgroup. Lists compose with kpm, the bias LUT (indexed by j - i)
+// and its gradient, and dropout (the keep hash indexes (b, h, row, key), so the copies of a repeated key are kept or
+// dropped together), not with causal, a window, segments or global keys (the binding rejects each); csrc/attn.hip has
+// none, and csrc/attn_hd.hip none at head dim 32 (the binding rejects it).
 // Bias: lut[h][(j - i) + Sq - 1] is added to the scaled score.
 // LSE: [B, H, Sq] fp32, forward writes and backward reads; +inf marks a row without a visible key (its output row is
 // 0).  The bf16 families store it in log2 units (scores are scaled by log2(e), softmax by exp2), fp32 in natural-log
@@ -88,6 +104,14 @@ struct AttnParamsT {
   float p_drop;
   uint32_t seed;
   uint32_t thr;    // set by the host (csrc/attn.hip: by its launchers)
+  // block lists, after everything else: the fields above keep the offsets (and the kernels the argument loads) they had
+  const int* kl_ptr;   // [Hl, ceil(Sq / 64) + 1] row starts into kl_idx; nullptr: no block lists (csrc/attn_hd.hip,
+                       // csrc/attn_f32.hip only)
+  const int* kl_idx;   // [nnz] 64-key block indices, forward and dQ; given with kl_ptr
+  const int* ql_ptr;   // [Hl, ceil(Sk / 64) + 1] row starts into ql_idx; given with kl_ptr
+  const int* ql_idx;   // [nnz] 64-query block indices, dK / dV: the transpose of kl, multiplicities kept
+  int Hl;          // heads of the block lists: H, or 1 (shared by all heads); 0 without lists
+  int l_nnz;       // length of kl_idx and of ql_idx
 };
 
 using AttnF32Params = AttnParamsT<float>;

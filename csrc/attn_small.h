@@ -96,6 +96,21 @@ struct BlockWalk {
     return nb;
   }
 };
+// Block lists (attn_params.h kl_ptr / kl_idx and ql_ptr / ql_idx, nullptr: none): the third walk, "follow a list",
+// of the kernels' LISTS instantiations.  list_range gives the entries [i, e) of the list of 64-block `x` of head `h` in
+// a CSR table whose rows are `n` blocks long, clamped to the index array; list_block the start of the block that entry
+// `i` names, or -1 for an entry outside [0, nblk) (passed over, as BlockWalk does).  A block listed twice is walked
+// twice: that is the contract.  Uniform over the workgroup, so the barriers of the walked blocks stay matched.
+template <class Params>
+DLLM_DEVICE void list_range(const Params& P, const int* ptr, int h, int n, int x, int& i, int& e) {
+  const int* lp = ptr + (long)(P.Hl > 1 ? h : 0) * (n + 1) + x;
+  i = max(lp[0], 0);
+  e = min(lp[1], P.l_nnz);
+}
+DLLM_DEVICE int list_block(const int* idx, int i, int nblk) {
+  const int e = idx[i];
+  return (unsigned)e < (unsigned)nblk ? e * 64 : -1;
+}
 // The staged key bytes of forward / dQ carry the global flag in bit 1 (bit 0: key valid).
 template <class Params>
 DLLM_DEVICE uint8_t key_byte(const Params& P, int b, int key) {

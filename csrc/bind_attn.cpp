@@ -69,6 +69,9 @@ void fill_common(P& p, const AttnFamily<P>& f, int64_t D, const Tensor& q, const
   p.q_seg = p.k_seg = p.q_blk = p.k_blk = nullptr;  // set_segments: the same two families only
   p.k_glob = nullptr;  // set_global: the same two families only
   p.k_gblk = nullptr;
+  p.kl_ptr = p.kl_idx = p.ql_ptr = p.ql_idx = nullptr;  // set_lists: the same two families only
+  p.Hl = 0;
+  p.l_nnz = 0;
   p.p_drop = (float)drop;
   p.seed = (uint32_t)seed;
   p.thr = drop > 0.0 ? (uint32_t)std::min(65535.0, drop * 65536.0) : 0u;  // ops/rng.py threshold16
@@ -183,18 +186,54 @@ void set_global(P& p, const Tensor& q, const optional<Tensor>& k_glob, const opt
   p.k_gblk = flat_ptr<const int>(*k_gblk, q, at::kInt, at_least(0), "k_gblk");
 }
 
+// the block lists of csrc/attn_params.h: the CSR table of key blocks per (head, query block) and its transpose, all
+// four or none, with nothing else that shapes the walk
+template <class P>
+void set_lists(P& p, const Tensor& q, const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
+               const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
+  const int n = has(kl_ptr) + has(kl_idx) + has(ql_ptr) + has(ql_idx);
+  if (n == 0) return;
+  TORCH_CHECK(n == 4, "attention: kl_ptr, kl_idx, ql_ptr and ql_idx are given together or not at all");
+  TORCH_CHECK(!p.causal, "attention: block lists with causal are unsupported");
+  TORCH_CHECK(p.k_glob == nullptr, "attention: block lists with global keys are unsupported");  // (they bring a window)
+  TORCH_CHECK(p.window < 0, "attention: block lists with a window are unsupported");
+  TORCH_CHECK(p.q_seg == nullptr, "attention: block lists with segments are unsupported");
+  TORCH_CHECK(!(std::is_same<P, AttnHdParams>::value && p.D == 32),
+              "attn_hd: block lists at head dim 32 are not served (csrc/attn_hd.hip)");
+  const int64_t nq = (p.Sq + 63) / 64, nk = (p.Sk + 63) / 64;
+  TORCH_CHECK(kl_ptr->dim() == 2 && (kl_ptr->size(0) == p.H || kl_ptr->size(0) == 1) && kl_ptr->size(1) == nq + 1,
+              "kl_ptr: expected [H or 1, ", nq + 1, "], got ", kl_ptr->sizes());
+  TORCH_CHECK(ql_ptr->dim() == 2 && ql_ptr->size(0) == kl_ptr->size(0) && ql_ptr->size(1) == nk + 1,
+              "ql_ptr: expected [", kl_ptr->size(0), ", ", nk + 1, "], got ", ql_ptr->sizes());
+  TORCH_CHECK(kl_idx->dim() == 1 && ql_idx->dim() == 1 && kl_idx->numel() == ql_idx->numel() &&
+                  kl_idx->numel() < INT_MAX,
+              "kl_idx / ql_idx: expected two [nnz] tensors of one length, got ", kl_idx->sizes(), " and ",
+              ql_idx->sizes());
+  p.Hl = (int)kl_ptr->size(0);
+  p.l_nnz = (int)kl_idx->numel();
+  p.kl_ptr = flat_ptr<const int>(*kl_ptr, q, at::kInt, at_least(0), "kl_ptr");
+  p.ql_ptr = flat_ptr<const int>(*ql_ptr, q, at::kInt, at_least(0), "ql_ptr");
+  // an empty index tensor may have no storage: the kernels never read it (row ends are clamped to nnz), any non-null
+  // pointer of the device will do
+  p.kl_idx = p.l_nnz ? flat_ptr<const int>(*kl_idx, q, at::kInt, at_least(0), "kl_idx") : p.kl_ptr;
+  p.ql_idx = p.l_nnz ? flat_ptr<const int>(*ql_idx, q, at::kInt, at_least(0), "ql_idx") : p.ql_ptr;
+}
+
 template <class P>
 std::vector<Tensor> attn_small_fwd(const AttnFamily<P>& f, int64_t D, const Tensor& q, const Tensor& k,
                                    const Tensor& v, const optional<Tensor>& kpm, const optional<Tensor>& lut,
                                    double scale, bool causal, double p, int64_t seed, int64_t window,
                                    const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
                                    const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
-                                   const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
+                                   const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
+                                   const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
+                                   const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
   P prm{};
   fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
   set_window(prm, window);
   set_segments(prm, q, q_seg, k_seg, q_blk, k_blk);
   set_global(prm, q, k_glob, k_gblk);
+  set_lists(prm, q, kl_ptr, kl_idx, ql_ptr, ql_idx);
   check_limits_small(prm);
   auto out = fill_fwd(prm, q);
   check_rc(f.fwd(&prm, stream()), f.fwd_name);
@@ -209,12 +248,15 @@ std::vector<Tensor> attn_small_bwd(const AttnFamily<P>& f, int64_t D, const Tens
                                    const optional<Tensor>& dk_out, const optional<Tensor>& dv_out, int64_t window,
                                    const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
                                    const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
-                                   const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
+                                   const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
+                                   const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
+                                   const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
   P prm{};
   fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
   set_window(prm, window);
   set_segments(prm, q, q_seg, k_seg, q_blk, k_blk);
   set_global(prm, q, k_glob, k_gblk);
+  set_lists(prm, q, kl_ptr, kl_idx, ql_ptr, ql_idx);
   check_limits_small(prm);
   auto r = fill_bwd(prm, f, q, o, dout, lse, dq_out, dk_out, dv_out, need_dlut);
   check_rc(f.bwd(&prm, stream()), f.bwd_name);
@@ -226,9 +268,12 @@ std::vector<Tensor> attn_f32_fwd(const Tensor& q, const Tensor& k, const Tensor&
                                  int64_t window,
                                  const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
                                  const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
-                                 const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
+                                 const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
+                                 const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
+                                 const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
   return attn_small_fwd(kAttnF32, 64, q, k, v, kpm, lut, scale, causal, p, seed, window, q_seg, k_seg, q_blk,
-                        k_blk, k_glob, k_gblk);
+                        k_blk, k_glob, k_gblk, kl_ptr, kl_idx,
+                        ql_ptr, ql_idx);
 }
 
 std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
@@ -238,9 +283,12 @@ std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tens
                                  const optional<Tensor>& dv_out, int64_t window,
                                  const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
                                  const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
-                                 const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
+                                 const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
+                                 const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
+                                 const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
   return attn_small_bwd(kAttnF32, 64, dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed, need_dlut, dq_out,
-                        dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk, k_glob, k_gblk);
+                        dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk, k_glob, k_gblk, kl_ptr, kl_idx,
+                        ql_ptr, ql_idx);
 }
 
 // the head dim of an attn_hd call: what csrc/attn_hd.hip is instantiated for (padded to 32, 16-B rows)
@@ -256,9 +304,12 @@ std::vector<Tensor> attn_hd_fwd(const Tensor& q, const Tensor& k, const Tensor& 
                                 int64_t window,
                                 const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
                                 const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
-                                const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
+                                const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
+                                const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
+                                const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
   return attn_small_fwd(kAttnHd, attn_hd_dim(q, k), q, k, v, kpm, lut, scale, causal, p, seed, window, q_seg, k_seg,
-                        q_blk, k_blk, k_glob, k_gblk);
+                        q_blk, k_blk, k_glob, k_gblk, kl_ptr, kl_idx,
+                        ql_ptr, ql_idx);
 }
 
 std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
@@ -268,9 +319,12 @@ std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tenso
                                 const optional<Tensor>& dv_out, int64_t window,
                                 const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
                                 const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
-                                const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk) {
+                                const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
+                                const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
+                                const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
   return attn_small_bwd(kAttnHd, attn_hd_dim(q, k), dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed,
-                        need_dlut, dq_out, dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk, k_glob, k_gblk);
+                        need_dlut, dq_out, dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk, k_glob, k_gblk, kl_ptr, kl_idx,
+                        ql_ptr, ql_idx);
 }
 
 // ---- csrc/attn.hip: the same helpers, plus its extras (dropout bit planes, saturated-bias ranges, rowrec, column sums)
@@ -384,23 +438,27 @@ void bind_attn(pybind11::module& m) {
   m.def("attn_f32_fwd", &attn_f32_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
         py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1,
         py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
-        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none());
+        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
+        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none());
   m.def("attn_f32_bwd", &attn_f32_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
         py::arg("dv_out") = py::none(), py::arg("window") = -1, py::arg("q_seg") = py::none(),
         py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
-        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none());
+        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
+        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none());
   m.def("attn_hd_fwd", &attn_hd_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
         py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1,
         py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
-        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none());
+        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
+        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none());
   m.def("attn_hd_bwd", &attn_hd_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
         py::arg("dv_out") = py::none(), py::arg("window") = -1, py::arg("q_seg") = py::none(),
         py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
-        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none());
+        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
+        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none());
 }
 
 }  // namespace dllm

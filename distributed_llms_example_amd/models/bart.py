@@ -36,6 +36,16 @@ finite: nothing reads them.  ``forward`` / ``encode`` / ``generate`` take ``glob
 global; None: no global token) and / or ``global_index`` ``[B, n]`` int64 (-1 = none), the same information in a shape
 that does not depend on the data: given both (data/collator.py emits both), the step has no host sync and replays
 from a HIP graph.  Packed inputs and context parallelism are not implemented for LED.
+
+BigBird-Pegasus (``model_type: "bigbird_pegasus"``, transformers modeling_bigbird_pegasus.py): pre-LN layers with a final
+LayerNorm per stack (transformers calls it ``layernorm_embedding``; models/hf_io.py maps the name), learned positions
+without offset, ``gelu_new`` FFN, attention projections without bias when ``use_bias`` is false.  With ``attention_type
+== "block_sparse"`` and an input longer than ``(5 + 2 num_random_blocks) block_size`` tokens the ENCODER self-attention
+of layer ``l`` is one block-list call (ops/attention.py ``block_lists``) on the pattern of models/bigbird.py drawn with
+seed ``l``, at the real length — no padding to a block multiple: the tail block is partial and the key-padding mask and
+the sequence end do the rest — and without dropout on the probabilities (transformers has none there); otherwise it is
+ordinary full attention.  The decision is made per call: transformers' switch to ``original_full`` on a short input is
+sticky on the module, ours is not.  Packed inputs and context parallelism are not implemented for BigBird-Pegasus.
 """
 from __future__ import annotations
 
@@ -52,6 +62,7 @@ from ..ops.embedding import embedding
 from ..ops.linear import Linear, linear, linear_res, stacked_linear
 from ..ops.lm_head import lm_head_loss, wants_lm_head_loss
 from ..ops.rng import default_rng
+from . import bigbird
 from .blocks import run_block
 from .config import Seq2SeqConfig
 from .distill import lm_output as distill_lm_output
@@ -68,20 +79,23 @@ class BartAttention(nn.Module):
         self.n_heads = cfg.num_heads
         self.head_dim = d // cfg.num_heads
         self.scaling = self.head_dim ** -0.5
+        bias = cfg.use_bias if cfg.model_type == "bigbird_pegasus" else True  # every other family's carry one
         if cross:
-            self.q_proj = Linear(d, d)
-            self.kv_proj = Linear(d, 2 * d)
+            self.q_proj = Linear(d, d, bias=bias)
+            self.kv_proj = Linear(d, 2 * d, bias=bias)
         else:
-            self.qkv_proj = Linear(d, 3 * d)
-        self.out_proj = Linear(d, d)
+            self.qkv_proj = Linear(d, 3 * d, bias=bias)
+        self.out_proj = Linear(d, d, bias=bias)
 
     def project_kv(self, kv_in):
         B, S, _ = kv_in.shape
         return self.kv_proj(kv_in).view(B, S, 2, self.n_heads, self.head_dim)
 
-    def forward(self, x, kv_in=None, mask=None, causal=False, p=0.0, cache=None, kv=None, residual=False, seg=None):
+    def forward(self, x, kv_in=None, mask=None, causal=False, p=0.0, cache=None, kv=None, residual=False, seg=None,
+                lists=None):
         """Attention block output; with ``residual`` also ``x`` for the post-LN residual, its gradient accumulated by
-        the input projection's dgrad GEMM (ops/linear.py linear_res)."""
+        the input projection's dgrad GEMM (ops/linear.py linear_res).  ``lists``: the ops/attention.py BlockLists of a
+        block-sparse self-attention (BigBird-Pegasus encoder)."""
         B, S, _ = x.shape
         res = x
         H, D = self.n_heads, self.head_dim
@@ -91,6 +105,8 @@ class BartAttention(nn.Module):
             if cache is not None:
                 raise NotImplementedError("packed inputs (segment ids) are not implemented with a generation cache")
             kw["q_segments"], kw["k_segments"] = seg
+        if lists is not None:
+            kw["block_lists"] = lists
         if self.cross:
             if residual:
                 q, res = linear_res(x, self.q_proj)
@@ -210,7 +226,7 @@ class BartLayer(nn.Module):
                                             rng.next_seed() if p > 0 else 0, xb)
 
     def forward_pre(self, normed, h, next_norm, mask=None, enc_out=None, enc_mask=None, cache=None, cross_kv=None,
-                    seg=None, cross_seg=None):
+                    seg=None, cross_seg=None, lists=None):
         """Pre-LN layer (mBART / Pegasus) on (LN_self_attn(h), h) -> (next_norm(h'), h'): every residual update is
         fused with the LayerNorm that follows it (the next sub-layer's, or ``next_norm``: the next layer's first
         LayerNorm or the stack's final one)."""
@@ -222,8 +238,9 @@ class BartLayer(nn.Module):
         eps = cfg.layer_norm_epsilon
         rng = default_rng()
         xb = _NORM_BIAS_COLSUM
-        a = self.self_attn(normed, mask=None if self.is_decoder else mask, causal=self.is_decoder, p=pa, cache=cache,
-                           seg=seg)
+        # BigBird's block-sparse call (``lists``) has no dropout on the probabilities
+        a = self.self_attn(normed, mask=None if self.is_decoder else mask, causal=self.is_decoder,
+                           p=0.0 if lists is not None else pa, cache=cache, seg=seg, lists=lists)
         if self.is_decoder:
             normed, h = norms.add_dropout_layer_norm_pre(h, a, self.encoder_attn_layer_norm.weight,
                                                          self.encoder_attn_layer_norm.bias, eps, p,
@@ -336,6 +353,10 @@ class BartStack(nn.Module):
             if not self.is_decoder and S > cfg.max_encoder_position_embeddings:
                 raise ValueError(f"LED: input of {S} tokens is longer than max_encoder_position_embeddings = "
                                  f"{cfg.max_encoder_position_embeddings}")
+        if cfg.model_type == "bigbird_pegasus" and (seg is not None or cross_seg is not None
+                                                     or position_ids is not None):
+            raise NotImplementedError("BigBird-Pegasus: packed inputs (--pack-sequences, segment ids) are not "
+                                      "implemented")
         if (seg is not None or position_ids is not None) and caches is not None:
             raise NotImplementedError("packed inputs (segment / position ids) are not implemented with a generation "
                                       "cache")
@@ -377,16 +398,21 @@ class BartStack(nn.Module):
         """Pre-LN stack: (LN_0(h), h) with h = dropout(embeddings), layer by layer, ending in (layer_norm(h), h)."""
         cfg = self.cfg
         layers = list(self.layers)
+        sparse = (cfg.model_type == "bigbird_pegasus" and not self.is_decoder and cfg.attention_type == "block_sparse"
+                  and not bigbird.full_attention_rule(x.shape[1], cfg.block_size, cfg.num_random_blocks))
         normed, h = norms.dropout_layer_norm_pre(x, layers[0].self_attn_layer_norm.weight,
                                                  layers[0].self_attn_layer_norm.bias, cfg.layer_norm_epsilon, p, seed)
         for i, layer in enumerate(layers):
             nxt = layers[i + 1].self_attn_layer_norm if i + 1 < len(layers) else self.layer_norm
             cache = caches[i] if caches is not None else None
             ckv = cross_kv[i] if cross_kv is not None else None
+            # BigBird's pattern of this layer (seed = its index) at this length and mode: kept, with its device tables
+            bl = bigbird.cached_lists(x.shape[1], cfg.block_size, cfg.num_random_blocks, cfg.num_heads, i,
+                                      self.training, cfg.max_position_embeddings, x.device) if sparse else None
 
-            def run(normed, h, layer=layer, nxt=nxt, cache=cache, ckv=ckv):
+            def run(normed, h, layer=layer, nxt=nxt, cache=cache, ckv=ckv, bl=bl):
                 return layer.forward_pre(normed, h, nxt, mask=attention_mask, enc_out=enc_out, enc_mask=enc_mask,
-                                         cache=cache, cross_kv=ckv, seg=seg, cross_seg=cross_seg)
+                                         cache=cache, cross_kv=ckv, seg=seg, cross_seg=cross_seg, lists=bl)
 
             normed, h = run_block(run, normed, h, checkpoint=cfg.gradient_checkpointing and self.training and
                                   caches is None)
@@ -522,7 +548,7 @@ class BartForConditionalGeneration(nn.Module):
 
     def _dllm_param_groups(self):
         lin = self.model.decoder.cross_kv_linears()
-        return [[m.weight for m in lin], [m.bias for m in lin]]
+        return [g for g in ([m.weight for m in lin], [m.bias for m in lin]) if g[0] is not None]
 
     def generate(self, input_ids, attention_mask=None, **kw):
         from .generation import generate
@@ -534,6 +560,9 @@ class BartForConditionalGeneration(nn.Module):
         if enable and self.config.model_type == "led":
             raise NotImplementedError("LED: context parallelism is not implemented (its windowed encoder with global "
                                       "tokens is not sharded); it is implemented for T5 / FLAN-T5 encoders only")
+        if enable and self.config.model_type == "bigbird_pegasus":
+            raise NotImplementedError("BigBird-Pegasus: context parallelism is not implemented (its block-sparse "
+                                      "encoder is not sharded); it is implemented for T5 / FLAN-T5 encoders only")
         if enable:
             raise NotImplementedError("context parallelism is implemented for T5 / FLAN-T5 encoders only")
         return self
@@ -576,6 +605,9 @@ class BartForConditionalGeneration(nn.Module):
         packed = [segment_ids, decoder_segment_ids, position_ids, decoder_position_ids]
         if any(t is not None for t in packed) and self.config.model_type == "led":
             raise NotImplementedError("LED: packed inputs (--pack-sequences, segment ids) are not implemented")
+        if any(t is not None for t in packed) and self.config.model_type == "bigbird_pegasus":
+            raise NotImplementedError("BigBird-Pegasus: packed inputs (--pack-sequences, segment ids) are not "
+                                      "implemented")
         if any(t is not None for t in packed):
             # packed rows (data/packing.py): several examples per row; the block tables are built once per batch
             if any(t is None for t in packed) or decoder_input_ids is None:

@@ -19,7 +19,8 @@ from dataclasses import dataclass, field
 
 @dataclass
 class Seq2SeqConfig:
-    # "t5" | BART family: "bart" | "mbart" | "pegasus" | "marian" | "m2m_100" | "plbart" | "blenderbot" | "led"
+    # "t5" | BART family: "bart" | "mbart" | "pegasus" | "marian" | "m2m_100" | "plbart" | "blenderbot" | "led" |
+    # "bigbird_pegasus"
     model_type: str = "t5"
     # T5 implementation variants: "t5" / "mt5" (same layers), "umt5" (every self-attention layer owns its
     # relative-position bias table: modeling_umt5.py UMT5LayerSelfAttention, has_relative_attention_bias=True),
@@ -71,6 +72,15 @@ class Seq2SeqConfig:
     # own size, and max_position_embeddings stays the decoder's (config.json: max_decoder_position_embeddings)
     attention_window: list | int | None = None
     max_encoder_position_embeddings: int | None = None
+    # BigBird-Pegasus (model_type="bigbird_pegasus", modeling_bigbird_pegasus.py): Pegasus-like pre-LN layers whose
+    # ENCODER self-attention is BigBird's block-sparse pattern (models/bigbird.py) when attention_type is
+    # "block_sparse" and the input is longer than (5 + 2 num_random_blocks) block_size tokens, full attention
+    # otherwise ("original_full": always); use_bias: the attention projections carry a bias (false in the public
+    # checkpoints)
+    attention_type: str = "block_sparse"
+    block_size: int = 64
+    num_random_blocks: int = 3
+    use_bias: bool = True
     # special tokens
     pad_token_id: int = 0
     eos_token_id: int = 1
@@ -94,6 +104,13 @@ class Seq2SeqConfig:
             self.attention_window = w
             if self.max_encoder_position_embeddings is None:
                 self.max_encoder_position_embeddings = 16384
+        if self.model_type == "bigbird_pegasus":
+            if self.attention_type not in ("block_sparse", "original_full"):
+                raise ValueError(f"BigBird-Pegasus: attention_type must be 'block_sparse' or 'original_full', got "
+                                 f"{self.attention_type!r}")
+            if self.block_size < 1 or self.num_random_blocks < 0:
+                raise ValueError(f"BigBird-Pegasus: block_size must be >= 1 and num_random_blocks >= 0, got "
+                                 f"{self.block_size} and {self.num_random_blocks}")
 
     @property
     def inner_dim(self) -> int:
@@ -167,7 +184,8 @@ class Seq2SeqConfig:
                     "pegasus": "PegasusForConditionalGeneration", "marian": "MarianMTModel",
                     "m2m_100": "M2M100ForConditionalGeneration", "plbart": "PLBartForConditionalGeneration",
                     "blenderbot": "BlenderbotForConditionalGeneration",
-                    "led": "LEDForConditionalGeneration"}[self.model_type]
+                    "led": "LEDForConditionalGeneration",
+                    "bigbird_pegasus": "BigBirdPegasusForConditionalGeneration"}[self.model_type]
             d = {
                 "architectures": [arch],
                 "model_type": self.model_type,
@@ -205,6 +223,9 @@ class Seq2SeqConfig:
                 d.update(attention_window=list(self.attention_window),
                          max_encoder_position_embeddings=self.max_encoder_position_embeddings,
                          max_decoder_position_embeddings=self.max_position_embeddings)
+            if self.model_type == "bigbird_pegasus":
+                d.update(attention_type=self.attention_type, block_size=self.block_size,
+                         num_random_blocks=self.num_random_blocks, use_bias=self.use_bias)
         d["torch_dtype"] = "float32"
         return d
 
@@ -243,6 +264,12 @@ class Seq2SeqConfig:
                 fam.update(attention_window=d.get("attention_window", 512),
                            max_encoder_position_embeddings=d.get("max_encoder_position_embeddings", 16384))
                 d = {**d, "max_position_embeddings": d.get("max_decoder_position_embeddings", 1024)}
+            if mt == "bigbird_pegasus":  # BigBirdPegasusConfig's defaults where the file is silent
+                fam.update(attention_type=d.get("attention_type", "block_sparse"), block_size=d.get("block_size", 64),
+                           num_random_blocks=d.get("num_random_blocks", 3), use_bias=d.get("use_bias", False))
+                d = {"vocab_size": 96103, "encoder_layers": 16, "decoder_layers": 16, "activation_function": "gelu_new",
+                     "max_position_embeddings": 4096, "scale_embedding": True, "pad_token_id": 0, "eos_token_id": 1,
+                     "bos_token_id": 2, "decoder_start_token_id": 2, "forced_eos_token_id": None, **d}
             return cls(
                 model_type=mt, vocab_size=d.get("vocab_size", 50265), d_model=d.get("d_model", 1024),
                 d_kv=d.get("d_model", 1024) // d.get("encoder_attention_heads", 16),
@@ -304,6 +331,10 @@ _FAMILY = {
                        shift_mode="standard"),
     # LED: BART layers, learned positions without offset (modeling_led.py LEDLearnedPositionalEmbedding)
     "led": dict(normalize_before=False, layernorm_embedding=True, position_embedding="learned0", shift_mode="standard"),
+    # BigBird-Pegasus: pre-LN with a final LayerNorm per stack (transformers names it layernorm_embedding, models/
+    # hf_io.py), no embedding LayerNorm, learned positions without offset (modeling_bigbird_pegasus.py)
+    "bigbird_pegasus": dict(normalize_before=True, layernorm_embedding=False, position_embedding="learned0",
+                            shift_mode="standard"),
     # M2M100 / NLLB: pre-LN, padding-aware sinusoidal positions (modeling_m2m_100.py), no final_logits_bias
     "m2m_100": dict(normalize_before=True, layernorm_embedding=False, position_embedding="sinusoidal_m2m",
                     shift_mode="standard", final_logits_bias=False),
@@ -398,7 +429,19 @@ PRESETS["led-base-16384"] = _bartlike("led", "led-base-16384", 50265, 768, 6, 12
 PRESETS["led-large-16384"] = _bartlike("led", "led-large-16384", 50265, 1024, 12, 16, 4096, "gelu", 1024, False, pad=1,
                                        eos=2, bos=0, start=2, attention_window=1024,
                                        max_encoder_position_embeddings=16384)
+# BigBird-Pegasus (google/bigbird-pegasus-large-{arxiv,pubmed,bigpatent}): BigBirdPegasusConfig's defaults, which are
+# the large checkpoints' values; a checkpoint directory's own config.json overrides them
+PRESETS["bigbird-pegasus-large-arxiv"] = _bartlike(
+    "bigbird_pegasus", "bigbird-pegasus-large-arxiv", 96103, 1024, 16, 16, 4096, "gelu_new", 4096, True, pad=0, eos=1,
+    bos=2, start=2, attention_type="block_sparse", block_size=64, num_random_blocks=3, use_bias=False)
+for _n in ("pubmed", "bigpatent"):
+    PRESETS[f"bigbird-pegasus-large-{_n}"] = PRESETS["bigbird-pegasus-large-arxiv"].replace(
+        name=f"bigbird-pegasus-large-{_n}")
 # tiny configs for CPU tests
+# block 8, 2 random blocks: block-sparse above 72 tokens, full attention up to there
+PRESETS["bigbird-tiny"] = _bartlike("bigbird_pegasus", "bigbird-tiny", 512, 64, 2, 4, 128, "gelu_new", 256, True, pad=0,
+                                    eos=1, bos=2, start=2, attention_type="block_sparse", block_size=8,
+                                    num_random_blocks=2, use_bias=False)
 PRESETS["t5-tiny"] = _t5("t5-tiny", 64, 128, 2, 4, vocab=512, d_kv=16)
 PRESETS["t5-tiny-gated"] = _t5("t5-tiny-gated", 64, 96, 2, 4, ff="gated-gelu", tie=False, vocab=512, d_kv=16)
 PRESETS["umt5-tiny"] = _t5("umt5-tiny", 64, 96, 2, 4, ff="gated-gelu", tie=True, vocab=512, d_kv=16, flavor="umt5")

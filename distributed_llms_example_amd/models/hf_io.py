@@ -28,6 +28,11 @@ _FUSED_LED = {".self_attn.qkv_proj.": [_LS + "query.", _LS + "key.", _LS + "valu
               ".self_attn.kv_global.": [_LS + "key_global.", _LS + "value_global."],
               ".self_attn.q_global.": [_LS + "query_global."],
               ".self_attn.out_proj.": [".self_attn.output."]}
+# BigBird-Pegasus (modeling_bigbird_pegasus.py): the encoder's self-attention is BigBirdPegasusEncoderAttention (self.
+# {query, key, value} + output), and each stack's FINAL LayerNorm is called layernorm_embedding
+_BS = ".self_attn.self."
+_FUSED_BIGBIRD_ENC = {".self_attn.qkv_proj.": [_BS + "query.", _BS + "key.", _BS + "value."],
+                      ".self_attn.out_proj.": [".self_attn.output."]}
 
 
 def _hf_names(cfg, name):
@@ -38,6 +43,14 @@ def _hf_names(cfg, name):
             name = "led." + name[len("model."):]
         if name.startswith("led.encoder."):
             for key, parts in _FUSED_LED.items():
+                if key in name:
+                    return [name.replace(key, p) for p in parts]
+    if cfg.model_type == "bigbird_pegasus":
+        for stack in ("model.encoder.", "model.decoder."):
+            if name.startswith(stack + "layer_norm."):
+                return [name.replace(stack + "layer_norm.", stack + "layernorm_embedding.")]
+        if name.startswith("model.encoder."):
+            for key, parts in _FUSED_BIGBIRD_ENC.items():
                 if key in name:
                     return [name.replace(key, p) for p in parts]
     for key, parts in _FUSED_BART.items():

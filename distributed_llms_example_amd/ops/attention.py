@@ -41,12 +41,22 @@ a global key, O(S·(w + 64·such blocks)); they compose with the key-padding mas
 ``window`` and do not go with ``causal`` or segments; bf16 at head dim 32 takes the composite (csrc/attn_hd.hip). (The
 rows AT the global positions attend to everything through projections of their own: the model runs them as a second,
 ordinary call — models/bart.py.)
+
+Block lists (block-sparse attention, BigBird-Pegasus encoder self-attention): ``block_lists`` is a :class:`BlockLists`
+from :func:`block_lists`: per head (or one for all heads) and per query block the key blocks that block attends to.
+Key ``j`` counts for query ``i`` once per occurrence of block ``j // block`` in the list of block ``i // block``: a
+block listed ``n`` times counts ``n`` times, which as a dense mask is ``+ log n`` on the scores and ``-inf`` on what no
+list names (``_reference``).  Repeats are the contract, not an accident: BigBird's own plans have them (models/
+bigbird.py).  The same two kernel files follow the lists at 64-block granularity — a pattern whose block size is a
+multiple of 64 is expanded, any other block size takes the composite on the GPU — and never load an unlisted block.
+Lists compose with the key-padding mask, the bias and dropout, not with ``causal``, ``window``, segments or global
+keys; bf16 at head dim 32 takes the composite.
 """
 from __future__ import annotations
 
 import math
 
-
+import numpy as np
 import torch
 
 from .. import _ext
@@ -187,6 +197,151 @@ def _check_global(gk, B, Sk, window, causal, q_seg) -> None:
         raise ValueError(f"attention: global_keys must be [B, Sk] = [{B}, {Sk}], got {tuple(gk.flags.shape)}")
 
 
+class BlockLists:
+    """A block-sparse pattern as the kernels and the composite take it.  ``ptr`` int64 ``[heads, nq + 1]`` and ``idx``
+    int64 ``[nnz]`` (numpy, host): the key blocks of query block ``x`` of head ``h`` are ``idx[ptr[h, x] : ptr[h, x +
+    1]]``, in list order, repeats kept; ``heads`` is the call's head count or 1 (one pattern for all heads); ``block``
+    the block size in positions; ``nq`` / ``nk`` the numbers of query / key blocks.  :meth:`tables` gives the int32
+    device tables of csrc/attn_params.h at 64-block granularity (``kl_ptr``, ``kl_idx`` and their transpose ``ql_ptr``,
+    ``ql_idx``), built once per device and shape and kept; :meth:`log_mult` the dense definition.  Built by
+    :func:`block_lists`."""
+
+    __slots__ = ("ptr", "idx", "heads", "block", "nq", "nk", "_tables")
+
+    def __init__(self, ptr, idx, block: int, nk: int):
+        self.ptr, self.idx, self.block, self.nk = ptr, idx, int(block), int(nk)
+        self.heads, self.nq = ptr.shape[0], ptr.shape[1] - 1
+        self._tables: dict = {}
+
+    def counts(self) -> np.ndarray:
+        """The multiplicity matrix ``[heads, nq, nk]``: how often key block ``j`` stands in the list of query block
+        ``x``.  Entries outside ``[0, nk)`` are passed over, as the kernels do."""
+        m = np.zeros((self.heads, self.nq, self.nk), dtype=np.int64)
+        for h in range(self.heads):
+            rows = np.repeat(np.arange(self.nq), np.diff(self.ptr[h]))
+            cols = self.idx[self.ptr[h, 0]:self.ptr[h, -1]]
+            ok = (cols >= 0) & (cols < self.nk)
+            np.add.at(m[h], (rows[ok], cols[ok]), 1)
+        return m
+
+    def log_mult(self, Sq: int, Sk: int, device) -> tuple:
+        """``(bias, hidden)`` of the dense definition, both ``[heads, Sq, Sk]``: ``log`` of the multiplicity of (query,
+        key) where it is listed (fp32, 0 elsewhere) and where it is not (bool)."""
+        m = torch.from_numpy(self.counts()).to(device)
+        m = m.repeat_interleave(self.block, 1)[:, :Sq].repeat_interleave(self.block, 2)[:, :, :Sk]
+        return torch.log(m.clamp_min(1).to(torch.float32)), m == 0
+
+    def tables(self, device, Sq: int, Sk: int) -> dict:
+        """The keyword arguments of attn_hd_* / attn_f32_* (csrc/bind_attn.cpp) for a ``[Sq, Sk]`` call on ``device``:
+        the lists in 64-blocks (each block of a pattern with ``block`` = 64 m stands for m x m of them, in order;
+        64-blocks past the ends of the sequences are dropped) and their transpose, multiplicities kept.  Built and
+        uploaded on first use, so a step that is captured and replayed builds nothing."""
+        if self.block % 64:
+            raise ValueError(f"attention: the kernels follow lists of 64-blocks; block size {self.block} is no multiple")
+        nq, nk = (Sq + 63) // 64, (Sk + 63) // 64
+        key = (str(device), nq, nk)
+        hit = self._tables.get(key)
+        if hit is not None:
+            return hit
+        m = self.block // 64
+        kp, ki, qp, qi = [], [], [], []
+        off = 0
+        for h in range(self.heads):
+            cnt = np.diff(self.ptr[h])
+            rows = np.repeat(np.arange(self.nq), cnt)  # the query block of every entry, list order kept
+            cols = self.idx[self.ptr[h, 0]:self.ptr[h, -1]]
+            ok = (cols >= 0) & (cols < self.nk)
+            rows, cols = rows[ok], cols[ok]
+            if m > 1:  # (x, j) -> (m x + a, m j + c): per 64-row block a, the entries in list order, each m wide
+                a, c = np.arange(m), np.arange(m)
+                r64 = (rows[None, :, None] * m + a[:, None, None] + 0 * c[None, None, :])
+                c64 = (cols[None, :, None] * m + 0 * a[:, None, None] + c[None, None, :])
+                rows, cols = r64.reshape(-1), c64.reshape(-1)
+                order = np.argsort(rows, kind="stable")
+                rows, cols = rows[order], cols[order]
+            ok = (rows < nq) & (cols < nk)
+            rows, cols = rows[ok], cols[ok]
+            kp.append(off + np.concatenate(([0], np.cumsum(np.bincount(rows, minlength=nq)))))
+            ki.append(cols)
+            order = np.argsort(cols, kind="stable")  # the transpose: per key block its query blocks, ascending
+            qp.append(off + np.concatenate(([0], np.cumsum(np.bincount(cols, minlength=nk)))))
+            qi.append(rows[order])
+            off += len(cols)
+        if off >= 2**31:
+            raise ValueError("attention: block lists too long")
+
+        def dev(parts, shape):
+            return torch.from_numpy(np.concatenate(parts).astype(np.int32)).view(*shape).to(device)
+
+        hit = {"kl_ptr": dev(kp, (self.heads, nq + 1)), "kl_idx": dev(ki, (-1,)),
+               "ql_ptr": dev(qp, (self.heads, nk + 1)), "ql_idx": dev(qi, (-1,))}
+        self._tables[key] = hit
+        return hit
+
+
+def block_lists(kl, *, block: int = 64, num_key_blocks: int | None = None, device=None, seq_len=None) -> "BlockLists | None":
+    """:class:`BlockLists` of ``kl`` (None and a ``BlockLists`` pass through): per head a sequence with, per query
+    block, the sequence of key-block indices it attends to (Python lists or numpy arrays; lists may differ in length,
+    repeat an index, or be empty) — or the lists of a single head, shared by all.  ``block``: the block size in
+    positions; ``num_key_blocks``: the number of key blocks (default: that of query blocks, self-attention).  With
+    ``device`` and ``seq_len`` (``S`` or ``(Sq, Sk)``) the kernels' tables are built there at once."""
+    if kl is None or isinstance(kl, BlockLists):
+        return kl
+    if block < 1:
+        raise ValueError(f"attention: block_lists block size must be >= 1, got {block}")
+    heads = list(kl)
+    if not heads:
+        raise ValueError("attention: block_lists got no lists")
+
+    def is_list_of_ints(x):
+        return len(x) == 0 or np.ndim(x[0]) == 0
+
+    if is_list_of_ints(heads[0]) or (isinstance(kl, np.ndarray) and kl.ndim == 2):  # one head's lists
+        heads = [heads]
+    nq = len(heads[0])
+    ptr = np.zeros((len(heads), nq + 1), dtype=np.int64)
+    idx = []
+    off = 0
+    for h, lists in enumerate(heads):
+        if len(lists) != nq:
+            raise ValueError(f"attention: block_lists head {h} has {len(lists)} query blocks, head 0 has {nq}")
+        ptr[h, 0] = off
+        for x, lst in enumerate(lists):
+            a = np.asarray(lst)
+            if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+                raise ValueError(f"attention: block_lists head {h} query block {x}: expected a 1-D list of integer "
+                                 f"block indices, got {a.dtype} {a.shape}")
+            idx.append(a.astype(np.int64))
+            off += a.size
+            ptr[h, x + 1] = off
+    bl = BlockLists(ptr, np.concatenate(idx) if idx else np.zeros(0, np.int64), block,
+                    nq if num_key_blocks is None else num_key_blocks)
+    if device is not None and seq_len is not None and block % 64 == 0:
+        sq, sk = (seq_len, seq_len) if np.ndim(seq_len) == 0 else seq_len
+        bl.tables(device, int(sq), int(sk))
+    return bl
+
+
+def _check_lists(bl, H, Sq, Sk, window, causal, q_seg, gk) -> None:
+    """Block lists go with neither causal, a window, segments nor global keys, and fit the call's heads and lengths."""
+    if bl is None:
+        return
+    if causal:
+        raise ValueError("attention: block_lists with causal are unsupported")
+    if window is not None:
+        raise ValueError("attention: block_lists with a window are unsupported")
+    if q_seg is not None:
+        raise ValueError("attention: block_lists with segments are unsupported")
+    if gk is not None:
+        raise ValueError("attention: block_lists with global_keys are unsupported")
+    if bl.heads not in (1, H):
+        raise ValueError(f"attention: block_lists are for {bl.heads} heads, the call has {H} (1 or {H} expected)")
+    nq, nk = -(-Sq // bl.block), -(-Sk // bl.block)
+    if (bl.nq, bl.nk) != (nq, nk):
+        raise ValueError(f"attention: block_lists are for {bl.nq} x {bl.nk} blocks of {bl.block}, the call has "
+                         f"{nq} x {nk} (Sq = {Sq}, Sk = {Sk})")
+
+
 def _check_segments(q_seg, k_seg, B, Sq, Sk, window) -> None:
     """Segments come for both sides or neither, as ids [B, Sq] / [B, Sk], and not with a window."""
     if q_seg is None and k_seg is None:
@@ -200,7 +355,7 @@ def _check_segments(q_seg, k_seg, B, Sq, Sk, window) -> None:
             raise ValueError(f"attention: {name} must be [B, S] = [{B}, {S}], got {tuple(sg.ids.shape)}")
 
 
-def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None, q_seg=None, k_seg=None, gk=None):
+def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None, q_seg=None, k_seg=None, gk=None, bl=None):
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     gk = global_keys(gk)
@@ -232,7 +387,15 @@ def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None, q_seg=Non
         qs, ks = q_seg.ids.to(q.device), k_seg.ids.to(q.device)
         hid = (ks[:, None, :] < 0) | (qs[:, :, None] != ks[:, None, :])
         s = s.masked_fill(hid[:, None], neg)
+    bl = block_lists(bl)
+    _check_lists(bl, H, Sq, Sk, window, causal, q_seg, gk)
+    if bl is not None:  # the dense definition: + log(multiplicity) where listed, hidden where not
+        lm, hid = bl.log_mult(Sq, Sk, q.device)
+        s = s.masked_fill(hid[None], neg) + lm[None]
     pr = torch.softmax(s, dim=-1)
+    if bl is not None:  # an empty list, or only padding listed: rows without a visible key, output 0
+        see = ~hid[None] if kpm is None else ~hid[None] & kpm.bool()[:, None, None, :]
+        pr = pr * see.any(-1, keepdim=True).to(pr.dtype)
     if q_seg is not None:  # the kernels' contract for a row without a visible key (here: a padding row): output 0
         pr = pr * (qs >= 0)[:, None, :, None].to(pr.dtype)
     if p > 0.0:
@@ -263,10 +426,10 @@ def _split(mode, a, b, c):
     return a, b, c
 
 
-def _tuned(q, window=None, seg=None) -> bool:
-    """csrc/attn.hip serves the call (bf16, head dim 64, no window, no segments); else csrc/attn_f32.hip (fp32) or
-    csrc/attn_hd.hip (bf16)."""
-    return q.dtype != torch.float32 and q.shape[-1] == 64 and window is None and seg is None
+def _tuned(q, window=None, seg=None, bl=None) -> bool:
+    """csrc/attn.hip serves the call (bf16, head dim 64, no window, no segments, no block lists); else csrc/attn_f32.hip
+    (fp32) or csrc/attn_hd.hip (bf16)."""
+    return q.dtype != torch.float32 and q.shape[-1] == 64 and window is None and seg is None and bl is None
 
 
 def _seg_args(q_seg, k_seg) -> tuple:
@@ -279,35 +442,43 @@ def _glob_args(gk) -> dict:
     return {} if gk is None else {"k_glob": gk.flags, "k_gblk": gk.blk}
 
 
+def _list_args(bl, q, k) -> dict:
+    """The block-list keyword arguments of attn_hd_* / attn_f32_* (csrc/bind_attn.cpp): the four tables, or nothing."""
+    return {} if bl is None else bl.tables(q.device, q.shape[1], k.shape[1])
+
+
 class _AttnFn(torch.autograd.Function):
     """Inputs are packed the way the projections produce them (``qkv`` = one [B,S,3,H,D] tensor for
     self-attention, ``q`` + ``kv`` [B,Sk,2,H,D] for cross-attention) so backward writes ONE packed
     gradient buffer through strided views instead of three zero-padded slice gradients."""
 
     @staticmethod
-    def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed, window=None, q_seg=None, k_seg=None, gk=None):
+    def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed, window=None, q_seg=None, k_seg=None, gk=None,
+                bl=None):
         C = _ext.native()
         q, k, v = _split(mode, a, b, c)
         args = (q, k, v, kpm, lut, float(scale), bool(causal), float(p), int(seed))
         sat_lo = sat_hi = -1
         dmask = None
-        if _tuned(q, window, q_seg):
+        if _tuned(q, window, q_seg, bl):
             # saturated bias tiles add a scalar instead of reading the LUT (forward -2 %)
             sat = getattr(lut, "_dllm_sat", None) if lut is not None else None
             sat_lo, sat_hi = sat if sat is not None else (-1, -1)
             o, lse, dmask = C.attn_fwd(*args, sat_lo, sat_hi)
         else:
             o, lse = (C.attn_f32_fwd if q.dtype == torch.float32 else C.attn_hd_fwd)(
-                *args, -1 if window is None else int(window), *_seg_args(q_seg, k_seg), **_glob_args(gk))
+                *args, -1 if window is None else int(window), *_seg_args(q_seg, k_seg), **_glob_args(gk),
+                **_list_args(bl, q, k))
         ctx.save_for_backward(a, b, c, o, lse, lut, kpm, dmask)
         ctx.cfg = (mode, scale, causal, p, seed, lut is not None and lut.requires_grad, sat_lo, sat_hi, window)
         ctx.seg = (q_seg, k_seg)  # plain int tensors, no graph: kept as they are
         ctx.gk = gk
+        ctx.bl = bl
         # packed inputs straight from a biased projection (ops/linear.py marks its output): the backward kernels also
         # sum dQ / dK / dV over tokens for that projection's bias gradient (colsum_record).  csrc/attn.hip only (the
         # partials hard-code H * 64) and bias-LUT-free calls only (its column-sum variants exist for those); everything
         # else takes the separate reduction, as with BIAS_COLSUM = False
-        cs_ok = BIAS_COLSUM and lut is None and _tuned(q, window, q_seg)
+        cs_ok = BIAS_COLSUM and lut is None and _tuned(q, window, q_seg, bl)
         ctx.cs = (cs_ok and mode != "sep" and _bias_out(a), cs_ok and mode == "q_kv" and _bias_out(b))
         # ops/linear.py stacked_linear: the packed kv is a slice of a multi-layer projection and its
         # gradient has a home in the stacked gradient buffer — write dK/dV there directly
@@ -349,11 +520,12 @@ class _AttnFn(torch.autograd.Function):
                     csk, csv = pkv[:, :HD], pkv[:, HD:]
         args = (do.contiguous(), q, k, v, o, lse, kpm, lut, float(scale), bool(causal), float(p), int(seed),
                 bool(need_dlut), dq, dk, dv)
-        if _tuned(q, window, ctx.seg[0]):
+        if _tuned(q, window, ctx.seg[0], ctx.bl):
             rq, rk, rv, dlut = C.attn_bwd(*args, dmask, sat_lo, sat_hi, csq, csk, csv)
         else:
             rq, rk, rv, dlut = (C.attn_f32_bwd if q.dtype == torch.float32 else C.attn_hd_bwd)(
-                *args, -1 if window is None else int(window), *_seg_args(*ctx.seg), **_glob_args(ctx.gk))
+                *args, -1 if window is None else int(window), *_seg_args(*ctx.seg), **_glob_args(ctx.gk),
+                **_list_args(ctx.bl, q, k))
         if part is not None:  # per-block partials, reduced by the consumer into the bias gradient (ops/gemm.py)
             colsum_record(da, part)
         if pq is not None:
@@ -363,7 +535,8 @@ class _AttnFn(torch.autograd.Function):
         if mode == "sep":
             da, db, dc = rq, rk, rv
         streams.pair_join()  # side-stream weight gradients paired with these VALU-bound kernels (ops/streams.py)
-        return None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None, None, None, None, None
+        return (None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None, None, None, None, None,
+                None)
 
 
 # False: the projections' bias gradients from a separate column reduction of dQKV (tests flip the module attribute)
@@ -408,7 +581,7 @@ def _aligned(t) -> bool:
     return t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
 
 
-def _route(t, *rest, window=None, seg=False, glob=False):
+def _route(t, *rest, window=None, seg=False, glob=False, lists=None):
     """Which kernel family serves a call whose q (or packed qkv) is ``t`` — by ops/routing.py ``attention_route``:
 
     * ``"attn.hip"``: bf16, head dim 64, no ``window`` (csrc/attn.hip, the tuned kernels);
@@ -431,12 +604,21 @@ def _route(t, *rest, window=None, seg=False, glob=False):
     if glob and bf16 and D == 32:  # csrc/attn_hd.hip serves no global keys at head dim 32 (its header says why)
         _warn_composite("global keys at head dim 32", t)
         return None
-    r = routing.attention_route(D, bf16, window, segments=seg)
+    if lists is not None:
+        if not routing.get("attn_lists"):  # A/B: list calls on the composite
+            return None
+        if lists.block % 64:  # the kernels follow lists of 64-blocks
+            _warn_composite(f"block lists at block size {lists.block} (no multiple of 64)", t)
+            return None
+        if bf16 and D == 32:  # csrc/attn_hd.hip serves no block lists at head dim 32 (its header says why)
+            _warn_composite("block lists at head dim 32", t)
+            return None
+    r = routing.attention_route(D, bf16, window, segments=seg, lists=lists is not None)
     if r == "attn_hd.hip" and not all(_aligned(x) for x in (t,) + rest if x is not None):
         _warn_composite("unaligned rows", t)
         return None
     if r == "composite":
-        served = (D == 64 and window is None and not seg or bf16 and 32 <= D <= 128 and D % 8 == 0
+        served = (D == 64 and window is None and not seg and lists is None or bf16 and 32 <= D <= 128 and D % 8 == 0
                   or not bf16 and D == 64)
         if not served:  # (else: switched off by DLLM_ROUTE)
             _warn_composite("this head dim" if bf16 else "fp32 at this head dim", t)
@@ -444,8 +626,8 @@ def _route(t, *rest, window=None, seg=False, glob=False):
     return r
 
 
-def _native(t, *rest, window=None, seg=False, glob=False) -> bool:
-    return _route(t, *rest, window=window, seg=seg, glob=glob) is not None
+def _native(t, *rest, window=None, seg=False, glob=False, lists=None) -> bool:
+    return _route(t, *rest, window=window, seg=seg, glob=glob, lists=lists) is not None
 
 
 def _on(sg, t):
@@ -458,28 +640,33 @@ def _on(sg, t):
 
 
 _global_keys = global_keys  # the function, where a parameter of the same name shadows it
+_block_lists = block_lists
 
 
 def attention(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_mask=None, bias_lut=None,
               dropout_p: float = 0.0, seed: int = 0, window: int | None = None, q_segments=None, k_segments=None,
-              global_keys=None):
+              global_keys=None, block_lists=None):
     """Multi-head attention.  q ``[B,Sq,H,D]``, k/v ``[B,Sk,H,D]``; ``key_padding_mask`` bool
     ``[B,Sk]`` (True = attend); ``bias_lut`` from :func:`relative_bias_lut`; ``window``: keys with
     ``|j - i| > window`` are masked (needs ``Sq == Sk`` and ``causal=False``; None: full attention);
     ``q_segments`` / ``k_segments``: ids ``[B,Sq]`` / ``[B,Sk]`` or :class:`Segments` (both or neither, not with
     ``window``): a key is visible only to the queries of its own non-negative id; ``global_keys``: flags ``[B,Sk]``
     (nonzero = global) or :class:`GlobalKeys` (needs ``window``; not with ``causal`` or segments): such a key is
-    visible to every query, inside its window or not."""
+    visible to every query, inside its window or not; ``block_lists``: a :class:`BlockLists` (or what
+    :func:`block_lists` takes; not with ``causal``, ``window``, segments or global keys): a key counts once per
+    occurrence of its block in the list of the query's block."""
     if window is not None:
         _check_window(window, q.shape[1], k.shape[1], causal)
     qs, ks = segments(q_segments), segments(k_segments)
     _check_segments(qs, ks, q.shape[0], q.shape[1], k.shape[1], window)
     gk = _global_keys(global_keys)
     _check_global(gk, q.shape[0], k.shape[1], window, causal, qs)
-    if _native(q, k, v, window=window, seg=qs is not None, glob=gk is not None):
+    bl = _block_lists(block_lists)
+    _check_lists(bl, q.shape[2], q.shape[1], k.shape[1], window, causal, qs, gk)
+    if _native(q, k, v, window=window, seg=qs is not None, glob=gk is not None, lists=bl):
         return _AttnFn.apply("sep", q, k, v, bias_lut, _prep_kpm(key_padding_mask), scale, causal, dropout_p, seed,
-                             window, _on(qs, q), _on(ks, q), _on(gk, q))
-    return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed, window, qs, ks, gk)
+                             window, _on(qs, q), _on(ks, q), _on(gk, q), bl)
+    return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed, window, qs, ks, gk, bl)
 
 
 def attention_qkv(qkv, **kw):
@@ -494,10 +681,12 @@ def attention_qkv(qkv, **kw):
     _check_segments(qs, ks, qkv.shape[0], qkv.shape[1], qkv.shape[1], window)
     gk = kw["global_keys"] = _global_keys(kw.get("global_keys"))
     _check_global(gk, qkv.shape[0], qkv.shape[1], window, kw.get("causal", False), qs)
-    if _native(qkv, window=window, seg=qs is not None, glob=gk is not None):
+    bl = kw["block_lists"] = _block_lists(kw.get("block_lists"))
+    _check_lists(bl, qkv.shape[3], qkv.shape[1], qkv.shape[1], window, kw.get("causal", False), qs, gk)
+    if _native(qkv, window=window, seg=qs is not None, glob=gk is not None, lists=bl):
         return _AttnFn.apply("qkv", qkv, None, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
                              kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
-                             window, _on(qs, qkv), _on(ks, qkv), _on(gk, qkv))
+                             window, _on(qs, qkv), _on(ks, qkv), _on(gk, qkv), bl)
     return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], **kw)
 
 
@@ -512,8 +701,12 @@ def attention_q_kv(q, kv, **kw):
     _check_global(gk, q.shape[0], kv.shape[1], window, kw.get("causal", False), qs)
     if gk is not None:
         kw = dict(kw, global_keys=gk)
-    if _native(q, kv, window=window, seg=qs is not None, glob=gk is not None):
+    bl = _block_lists(kw.get("block_lists"))
+    _check_lists(bl, q.shape[2], q.shape[1], kv.shape[1], window, kw.get("causal", False), qs, gk)
+    if bl is not None:
+        kw = dict(kw, block_lists=bl)
+    if _native(q, kv, window=window, seg=qs is not None, glob=gk is not None, lists=bl):
         return _AttnFn.apply("q_kv", q, kv, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
                              kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
-                             window, _on(qs, q), _on(ks, q), _on(gk, q))
+                             window, _on(qs, q), _on(ks, q), _on(gk, q), bl)
     return attention(q, kv[:, :, 0], kv[:, :, 1], **kw)

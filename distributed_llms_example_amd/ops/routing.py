@@ -60,6 +60,11 @@ window + global keys           as the window (same route; bf16 head dim 32: comp
                                O(S·(w + 64·such blocks)); the rows at the global positions
                                are an ordinary short-query call (csrc/attn.hip at head dim
                                64)
+block-list attention           as the window (same route; bf16 head dim 32 and block sizes   attn_block_lists.txt
+(BigBird-Pegasus encoder)      that are no multiple of 64: composite): forward and dQ
+                               follow each query block's list of 64-key blocks, dK / dV
+                               its transpose; a block listed n times counts n times; the
+                               rest is never loaded (``attn_lists`` = 1; 0: the composite)
 segment-masked attention       as the window: bf16 (head dim 64 included) on                 attn_segments_vs_masked.txt
 (sequence packing)             csrc/attn_hd.hip, fp32 at head dim 64 on csrc/attn_f32.hip;
                                blocks of other segments are skipped by per-block (min,
@@ -127,6 +132,7 @@ DEFAULTS: dict = {
     # attention (ops/attention.py, parallel/context.py)
     "attn_f32": 1,
     "attn_hd": 1,                 # bf16 head dims 32 .. 128 other than 64 on csrc/attn_hd.hip (0: composite)
+    "attn_lists": 1,              # block-list calls on csrc/attn_hd.hip / csrc/attn_f32.hip (0: composite)
     "attn_chunk": 0,              # 0: 8192 rows for < 32 rows per head, else 4096
     "attn_chunk_min": 8192,
     # weight-gradient side stream (ops/streams.py)
@@ -196,15 +202,19 @@ def get(key: str):
 
 
 def attention_route(head_dim: int, bf16: bool = True, window: int | None = None, *,
-                    segments: bool = False) -> str:
+                    segments: bool = False, lists: bool = False) -> str:
     """Kernel family of an attention call on the GPU by head dim and dtype (bf16, else fp32): ``"attn.hip"``,
     ``"attn_hd.hip"``, ``"attn_f32.hip"`` or ``"composite"`` — the rule ops/attention.py ``_route`` applies.
     ``window``: the call's sliding window (None: full attention).  csrc/attn.hip has no window, so a windowed bf16
     call at head dim 64 runs csrc/attn_hd.hip's 64-wide instantiation.  ``segments``: the call carries segment ids
     (sequence packing); csrc/attn.hip has none either, so the same holds.  The fp32 route is unchanged by both.
     A windowed call with global keys (LED) routes as the windowed call, except bf16 at head dim 32, where
-    csrc/attn_hd.hip serves no global keys and ops/attention.py ``_route`` takes the composite."""
-    if head_dim == 64 and (window is None and not segments or not bf16):
+    csrc/attn_hd.hip serves no global keys and ops/attention.py ``_route`` takes the composite.  ``lists``: the call
+    carries block lists (BigBird); it routes as a call with segments, with the same exception at head dim 32 and
+    ``attn_lists`` = 0 sending it to the composite."""
+    if lists and not get("attn_lists"):
+        return "composite"
+    if head_dim == 64 and (window is None and not segments and not lists or not bf16):
         return "attn.hip" if bf16 else ("attn_f32.hip" if get("attn_f32") else "composite")
     if bf16 and 32 <= head_dim <= 128 and head_dim % 8 == 0 and get("attn_hd"):
         return "attn_hd.hip"
