@@ -15,12 +15,34 @@
 //     the overall top-K is contained in the union of the per-beam top-K lists.
 //
 // A forced token (BOS at step 1, EOS at the last step) replaces the row by that single candidate with log-prob 0,
-// as transformers' ForcedBOS/EOS processors do after the bans.  Ties resolve to the lower flat index.
+// as transformers' ForcedBOS/EOS processors do after the bans.
+//
+// Order and ties.  The returned list is ordered by (fp32 candidate score descending, flat index beam * V + token
+// ascending): two candidates whose fp32 scores fl(bs + fl(fl(x - M) - logf(S))) are equal come out lower flat index
+// first.  Inside one beam the K candidates are picked on the stored logit (larger first, equal logits lower token
+// first); the score is monotone in the logit, so a beam's list is also its best K by score, up to logits whose scores
+// round to the same fp32 value.  A slot with no finite candidate left holds (-inf, beam * V + V - 1).
+//
+// Every row is walked with one fixed element -> thread map (thread t owns the VW-element groups t, t + 256, ... and
+// then a strided tail), whether its address allows 16-B loads or not, so the result depends on the values alone: the
+// same logits at another alignment or row stride give the same bits.
 #include "common.h"
 
 using namespace dllm;
 
 namespace {
+
+constexpr int kThreads = 256, kWaves = kThreads / 64;
+constexpr int kMaxBeams = 8, kMaxK = 16;  // candidate array: nb * K <= kMaxBeams * kMaxK
+// static LDS of beam_topk_kernel (red_v, red_i, cand_s, cand_i), counted with the dynamic ban bitmap against the limit
+constexpr size_t kStaticLds =
+    kWaves * (sizeof(float) + sizeof(int)) + kMaxBeams * kMaxK * (sizeof(float) + sizeof(int));
+constexpr size_t kLdsLimit = 64 * 1024;  // per workgroup without an opt-in attribute
+constexpr size_t kLdsAlign = 16;         // the dynamic segment's alignment (declared below)
+// the largest vocabulary whose ban bitmap (4 B per 32 tokens, placed at its alignment) fits beside the static arrays
+constexpr size_t kBitmapBytes = kLdsLimit - (kStaticLds + kLdsAlign - 1) / kLdsAlign * kLdsAlign;
+constexpr long kMaxVocab = (long)(kBitmapBytes / 4 * 32);
+static_assert(kStaticLds > 0 && kMaxVocab < (long)(kLdsLimit / 4 * 32), "the static arrays take part of the limit");
 
 struct BeamParams {
   const void* logits;  // [B * nb, V] rows with leading dimension ld (bf16 or fp32)
@@ -64,10 +86,11 @@ DLLM_DEVICE void insert(float (&tv)[K], int (&ti)[K], float v, int i) {
 template <typename T, int K>
 __global__ __launch_bounds__(256) void beam_topk_kernel(BeamParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red_v[4];
-  __shared__ int red_i[4];
-  __shared__ float cand_s[8 * 16];
-  __shared__ int cand_i[8 * 16];
+  __shared__ float red_v[kWaves];
+  __shared__ int red_i[kWaves];
+  __shared__ float cand_s[kMaxBeams * kMaxK];
+  __shared__ int cand_i[kMaxBeams * kMaxK];
+  static_assert(sizeof(red_v) + sizeof(red_i) + sizeof(cand_s) + sizeof(cand_i) == kStaticLds, "kStaticLds");
   uint32_t* bits = reinterpret_cast<uint32_t*>(smem);  // [ceil(V / 32)] ban bitmap of the current row
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int b = blockIdx.x, V = P.V, nwords = (V + 31) >> 5;
@@ -119,21 +142,32 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(BeamParams P) {
       }
       if (!bans || !((bits[c >> 5] >> (c & 31)) & 1u)) insert<K>(tv, ti, v, c);
     };
-    // 16-B loads (8 bf16 / 4 fp32 per lane) when the row is 16-B aligned; scalar otherwise and for the tail
+    // groups of VW elements per lane (8 bf16 / 4 fp32): one 16-B load when the row is 16-B aligned, VW scalar loads
+    // of the same elements otherwise (the same visit order either way); then the tail
     constexpr int VW = sizeof(T) == 2 ? 8 : 4;
     const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const int vend = vec ? V / VW * VW : 0;
-    for (int c0 = tid * VW; c0 < vend; c0 += 256 * VW) {
-      const u32x4 raw = *reinterpret_cast<const u32x4*>(x + c0);
-      if constexpr (sizeof(T) == 2) {
+    const int vend = V / VW * VW;
+    if (vec) {
+      for (int c0 = tid * VW; c0 < vend; c0 += 256 * VW) {
+        const u32x4 raw = *reinterpret_cast<const u32x4*>(x + c0);
+        if constexpr (sizeof(T) == 2) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          visit(bf2f((uint16_t)(raw[e] & 0xFFFFu)), c0 + 2 * e);
-          visit(bf2f((uint16_t)(raw[e] >> 16)), c0 + 2 * e + 1);
+          for (int e = 0; e < 4; ++e) {
+            visit(bf2f((uint16_t)(raw[e] & 0xFFFFu)), c0 + 2 * e);
+            visit(bf2f((uint16_t)(raw[e] >> 16)), c0 + 2 * e + 1);
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) visit(__uint_as_float(raw[e]), c0 + e);
         }
-      } else {
+      }
+    } else {
+      for (int c0 = tid * VW; c0 < vend; c0 += 256 * VW) {
+        float val[VW];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) visit(__uint_as_float(raw[e]), c0 + e);
+        for (int e = 0; e < VW; ++e) val[e] = ld1<T>(x, c0 + e);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) visit(val[e], c0 + e);
       }
     }
     for (int c = vend + tid; c < V; c += 256) visit(ld1<T>(x, c), c);
@@ -226,13 +260,18 @@ int launch(const BeamParams& p, int B, hipStream_t st) {
 
 }  // namespace
 
-// returns -4 on unsupported arguments (k_out > 16, nb > 8, V too large for the LDS bitmap)
+// the largest V dllm_beam_topk takes
+extern "C" int dllm_beam_topk_max_vocab() { return (int)kMaxVocab; }
+
+// returns -4 on unsupported arguments, before any launch (k_out > 16, nb > 8, V too large for the LDS bitmap next to
+// the kernel's static LDS): the caller runs the composite
 extern "C" int dllm_beam_topk(const void* logits, long ld, int is_bf16, const float* beam_scores, const int64_t* seqs,
                               long lds, int cur, int ngram, int ban_tok, int force_tok, int B, int nb, int V, int k_out,
                               float* top_s, int64_t* top_i, hipStream_t st) {
-  if (B <= 0 || nb <= 0 || nb > 8 || k_out <= 0 || k_out > 16 || V <= 0 || (V + 31) / 32 * 4 > 64 * 1024) return -4;
+  // the ban bitmap (dynamic LDS) and the kernel's static arrays share one workgroup's LDS: V <= kMaxVocab
+  if (B <= 0 || nb <= 0 || nb > kMaxBeams || k_out <= 0 || k_out > kMaxK || V <= 0 || V > kMaxVocab) return -4;
   const int K = k_out <= 2 ? 2 : k_out <= 4 ? 4 : k_out <= 8 ? 8 : 16;
-  if (nb * K > 8 * 16) return -4;
+  if (nb * K > kMaxBeams * kMaxK) return -4;
   BeamParams p{logits, ld, beam_scores, seqs, lds, cur, ngram, ban_tok, force_tok, nb, V, k_out, top_s, top_i};
   return is_bf16 ? launch<uint16_t>(p, B, st) : launch<float>(p, B, st);
 }

@@ -20,23 +20,28 @@ StepInputs step_inputs(const Tensor& logits, const Tensor& seqs, int64_t cur, co
 }
 
 // One beam-search step (csrc/beam.hip): logits [B * nb, V] (bf16 / fp32, unit inner stride), beam scores [B * nb]
-// fp32, generated prefix seqs [B * nb, L] int64 -> (top scores [B, k_out] fp32, flat indices [B, k_out] int64).
-std::vector<Tensor> beam_topk(const Tensor& logits, const Tensor& beam_scores, const Tensor& seqs, int64_t cur,
-                              int64_t ngram, int64_t ban_tok, int64_t force_tok, int64_t nb, int64_t k_out) {
+// fp32, generated prefix seqs [B * nb, L] int64 -> (rc, top scores [B, k_out] fp32, flat indices [B, k_out] int64).
+// rc -4: arguments the kernel does not take (nothing was launched or written; the caller runs the composite).
+std::tuple<int64_t, Tensor, Tensor> beam_topk(const Tensor& logits, const Tensor& beam_scores, const Tensor& seqs,
+                                              int64_t cur, int64_t ngram, int64_t ban_tok, int64_t force_tok,
+                                              int64_t nb, int64_t k_out) {
   const StepInputs in = step_inputs(logits, seqs, cur, "beam_topk");
   const float* scores_p = flat_ptr<const float>(beam_scores, logits, at::kFloat, exactly(logits.size(0)),
                                                 "beam_topk: beam_scores");
   TORCH_CHECK(nb > 0 && logits.size(0) % nb == 0, "beam_topk: rows must be a multiple of nb");
   const int64_t B = logits.size(0) / nb, V = logits.size(1);
   TORCH_CHECK(force_tok < V && ban_tok < V, "beam_topk: token id out of range");
+  TORCH_CHECK(k_out > 0, "beam_topk: k_out must be positive");
   auto top_s = at::empty({B, k_out}, beam_scores.options());
   auto top_i = at::empty({B, k_out}, seqs.options());
-  if (B > 0)
-    check_rc(dllm_beam_topk(in.logits.ptr, in.logits.ld, logits.scalar_type() == at::kBFloat16, scores_p, in.seqs.ptr,
-                            in.seqs.ld, (int)cur, (int)ngram, (int)ban_tok, (int)force_tok, (int)B, (int)nb, (int)V,
-                            (int)k_out, top_s.data_ptr<float>(), top_i.data_ptr<int64_t>(), stream()),
-             "beam_topk");
-  return {top_s, top_i};
+  if (B == 0) return {0, top_s, top_i};
+  if (V >= (1LL << 31) || B >= (1LL << 31) || nb >= (1LL << 31) || k_out >= (1LL << 31)) return {-4, top_s, top_i};
+  const int rc = dllm_beam_topk(in.logits.ptr, in.logits.ld, logits.scalar_type() == at::kBFloat16, scores_p,
+                                in.seqs.ptr, in.seqs.ld, (int)cur, (int)ngram, (int)ban_tok, (int)force_tok, (int)B,
+                                (int)nb, (int)V, (int)k_out, top_s.data_ptr<float>(), top_i.data_ptr<int64_t>(),
+                                stream());
+  if (rc != -4) check_rc(rc, "beam_topk");
+  return {rc, top_s, top_i};
 }
 
 // One sampling step (csrc/sample.hip): (rc, token [rows] int64, thresholds [rows, 2] fp32).  rc -4: arguments the
@@ -80,6 +85,7 @@ void kv_reorder(Tensor& cache, const Tensor& src, int64_t nb, int64_t n) {
 
 void bind_generate(pybind11::module& m) {
   m.def("beam_topk", &beam_topk);
+  m.def("beam_topk_max_vocab", []() { return (int64_t)dllm_beam_topk_max_vocab(); });
   m.def("kv_reorder", &kv_reorder);
   m.def("sample_step", &sample_step);
 }

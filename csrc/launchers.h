@@ -101,6 +101,7 @@ int dllm_gemm_w4(const GemmW4Params* pp, int b_kmajor, int persist, int epi, hip
 int dllm_beam_topk(const void* logits, long ld, int is_bf16, const float* beam_scores, const int64_t* seqs, long lds,
                    int cur, int ngram, int ban_tok, int force_tok, int B, int nb, int V, int k_out, float* top_s,
                    int64_t* top_i, hipStream_t st);
+int dllm_beam_topk_max_vocab();
 int dllm_kv_reorder(void* cache, const int64_t* src, int lk, int rows, int nb, int max_len, int hd, int n,
                     hipStream_t st);
 int dllm_sample_list_cap();

@@ -212,8 +212,8 @@ def _fused_beam_ok(logits, nb: int, penalty: float = 1.0) -> bool:
 def _beam_candidates(logits, beam_scores, seqs, cur, B, nb, proc, penalty: float = 1.0):
     """Top-2·nb candidates over nb·V per batch entry: (scores [B, 2nb], flat indices beam·V + token).  On the GPU one
     csrc/beam.hip launch (log_softmax normaliser + processors + beam score + top-k in one pass over the logits);
-    otherwise the torch composite of the same ops.  A repetition penalty acts on the log-probabilities, before the
-    bans (transformers' beam search), on the torch path only."""
+    otherwise, and for arguments the kernel does not take, the torch composite of the same ops.  A repetition penalty
+    acts on the log-probabilities, before the bans (transformers' beam search), on the torch path only."""
     min_length, ngram, forced_bos, forced_eos, max_length, eos = proc
     if _fused_beam_ok(logits, nb, penalty):
         from .. import _ext
@@ -223,9 +223,12 @@ def _beam_candidates(logits, beam_scores, seqs, cur, B, nb, proc, penalty: float
             force = forced_bos
         if forced_eos is not None and cur == max_length - 1:
             force = forced_eos
-        top_s, top_i = _ext.native().beam_topk(logits.contiguous(), beam_scores.reshape(-1).float().contiguous(), seqs,
-                                               cur, ngram or 0, ban, force, nb, 2 * nb)
-        return top_s, top_i
+        rc, top_s, top_i = _ext.native().beam_topk(logits.contiguous(), beam_scores.reshape(-1).float().contiguous(),
+                                                   seqs, cur, ngram or 0, ban, force, nb, 2 * nb)
+        if rc == 0:
+            return top_s, top_i
+        if rc != -4:  # -4: arguments the kernel does not take (a vocabulary past its LDS bitmap): the composite below
+            raise RuntimeError(f"beam_topk failed: rc={rc}")
     logp = _penalize(torch.log_softmax(logits.float(), dim=-1), seqs, cur, penalty)
     logp = _apply_processors_device(logp, seqs, cur, min_length, ngram, forced_bos, forced_eos, max_length, eos)
     V = logp.shape[-1]

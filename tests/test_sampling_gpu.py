@@ -3,6 +3,7 @@ the torch composite of models/generation.py on the same inputs, and whole sample
 import pytest
 import torch
 
+import gen_refs as G
 from distributed_llms_example_amd import _ext
 from distributed_llms_example_amd.models import build_model
 from distributed_llms_example_amd.models import generation as gen
@@ -143,6 +144,92 @@ def test_sample_step_processors(rows, V, dtype, case, spy):
             assert not (tok == eos).any()
         if case == "only_one":
             assert torch.equal(tok, only)
+
+
+@pytest.mark.parametrize("rows,V,dtype", SHAPES[:2])
+@pytest.mark.parametrize("ngram,cur", [(1, 0), (1, 17), (2, 1), (2, 2), (2, 17)])
+def test_sample_step_short_ngrams(rows, V, dtype, ngram, cur, spy):
+    """n = 1 (the composite's scatter path) and n = 2, with cur < n (no window yet), cur == n and a longer prefix."""
+    k, p, T, r = 50, 0.9, 0.7, 1.2
+    proc = (None, ngram, None, None, 40, 2)
+    logits, seqs = _make(rows, V, dtype, 11)
+    seqs = seqs % 12
+    best = logits.float().argmax(1)
+    if cur >= 17:  # a banned completion is the best token of every row
+        seqs[:, cur - 1] = 3
+        seqs[:, 4], seqs[:, 5] = 3, best
+    tok = gen._sample_step(logits, seqs, cur, proc, r, T, k, p, 78, cur)
+    assert len(spy) == 1 and spy[0][0] == 0
+    _check_step(logits, seqs, cur, proc, k, p, T, r, 78, cur, tok, spy[0][2])
+    if cur >= 17:
+        assert not (tok == best).any()
+
+
+def test_sample_step_prefix_longer_than_the_block(spy):
+    """cur = 1500 of L = 1600: the seen bitmap and the ban loops stride over the prefix by the 1024-thread block."""
+    rows, V, dtype = SHAPES[1]
+    L, cur = 1600, 1500
+    assert cur > 1024
+    k, p, T, r = 50, 0.9, 0.7, 1.2
+    proc = (None, 3, None, None, L, 2)
+    logits, seqs = _make(rows, V, dtype, 13, L=L)
+    seqs = seqs % 12
+    seqs[:, 1200:1202] = seqs[:, cur - 2:cur]  # a window past the first block trip bans the best token
+    best = logits.float().argmax(1)
+    seqs[:, 1202] = best
+    tok = gen._sample_step(logits, seqs, cur, proc, r, T, k, p, 79, 3)
+    assert len(spy) == 1 and spy[0][0] == 0
+    _check_step(logits, seqs, cur, proc, k, p, T, r, 79, 3, tok, spy[0][2])
+    assert not (tok == best).any()
+
+
+@pytest.mark.parametrize("rows,V,dtype", SHAPES[:2])
+def test_sample_step_sliced_inputs(rows, V, dtype, spy):
+    """Logits as a misaligned column slice of a wider buffer and prefixes as a slice with ld != L: the same token and
+    thresholds as from contiguous copies."""
+    k, p, T, r = 50, 0.9, 0.7, 1.2
+    cur, proc = 17, (None, 3, None, None, 40, 2)
+    logits, seqs = _make(rows, V, dtype, 17)
+    seqs = seqs % 12
+    W = V + 16 + (-V) % 8  # whole 16-B groups per row: every row of the slice starts 3 elements past a boundary
+    wide = torch.full((rows, W), 100.0, dtype=dtype, device="cuda")
+    wide[:, 3:3 + V] = logits
+    lv = wide[:, 3:3 + V]
+    assert all((lv.data_ptr() + q * W * lv.element_size()) % 16 for q in range(rows))
+    sw = torch.zeros(rows, 57, dtype=torch.long, device="cuda")
+    sw[:, 9:49] = seqs
+    sv = sw[:, 9:49]
+    assert lv.stride(0) != V and sv.stride(0) != 40
+    tok = gen._sample_step(lv, sv, cur, proc, r, T, k, p, 80, 4)
+    tok2 = gen._sample_step(logits, seqs, cur, proc, r, T, k, p, 80, 4)
+    assert len(spy) == 2 and spy[0][0] == 0 and spy[1][0] == 0
+    _check_step(logits, seqs, cur, proc, k, p, T, r, 80, 4, tok, spy[0][2])
+    assert torch.equal(tok, tok2) and torch.equal(spy[0][2], spy[1][2])
+
+
+@pytest.mark.parametrize("rows,V,dtype", SHAPES[:2])
+@pytest.mark.parametrize("T", [1.7, 3.0])
+def test_sample_step_temperatures_above_one(rows, V, dtype, T, spy):
+    k, p, r, cur = 5, 1.0, 1.0, 17
+    logits, seqs, pre = _inputs(rows, V, dtype, cur, PLAIN, k, p, T, r)
+    tok = gen._sample_step(logits, seqs, cur, PLAIN, r, T, k, p, 81, 5)
+    assert len(spy) == 1 and spy[0][0] == 0
+    _check_step(logits, seqs, cur, PLAIN, k, p, T, r, 81, 5, tok, spy[0][2], pre)
+
+
+def test_sample_step_keeps_ties_from_below_a_radix_bin_edge(spy):
+    """gen_refs.edge_topk_row: the k-th largest score is exactly 2.0, a bin edge of the coarse cut made before the
+    temperature, with neighbours 1 .. 3 ulps below it; at T = 1.7 some of them tie with the k-th value after the
+    division and the composite keeps them (tests/test_gen_refs_cpu.py confirms it): so must the kernel."""
+    V, k, T = 1000, 5, 1.7
+    x, kth, below = G.edge_topk_row(V, k)
+    logits = x.cuda()
+    seqs = torch.zeros(1, 8, dtype=torch.long, device="cuda")
+    kept = torch.isfinite(gen._sample_scores(logits, seqs, 1, PLAIN, 1.0, T, k, 1.0))[0]
+    assert int(kept.sum()) > k and kept[below].any() and not kept[below].all()
+    tok = gen._sample_step(logits, seqs, 1, PLAIN, 1.0, T, k, 1.0, 82, 6)
+    assert len(spy) == 1 and spy[0][0] == 0
+    _check_step(logits, seqs, 1, PLAIN, k, 1.0, T, 1.0, 82, 6, tok, spy[0][2])
 
 
 def _model(name):
