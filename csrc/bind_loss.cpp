@@ -1,5 +1,5 @@
-// Loss kernels: cross entropy (csrc/ce.hip) and the distillation loss (csrc/kd.hip), whole-vocabulary and
-// vocabulary-chunked forms.
+// Loss kernels: cross entropy (csrc/ce.hip), the distillation loss (csrc/kd.hip) and the preference loss
+// (csrc/pref.hip), whole-vocabulary and vocabulary-chunked forms.
 #include "bind_common.h"
 
 namespace dllm {
@@ -210,6 +210,130 @@ void kd_chunk_bwd(const Tensor& w_ce, const Tensor& w_kl, Tensor& student, const
            "kd_chunk_bwd");
 }
 
+// ------------------------------------------------------------------------------------------- preference loss
+// csrc/pref.hip: per-row log-probabilities of a policy's and a frozen reference's logits in one pass, the pairwise
+// loss over the 2P interleaved sequences, and the gradient over the policy logits.
+struct PrefIn {
+  void* policy;
+  const void* ref;  // nullptr: the policy alone
+  const int64_t* labels;
+};
+PrefIn pref_in(const Tensor& policy, const optional<Tensor>& ref, const Tensor& labels) {
+  PrefIn r;
+  r.policy = flat_ptr<void>(policy, policy, kLogitDtypes, at_least(0), "pref: policy");
+  TORCH_CHECK(policy.dim() == 2, "pref: policy must be contiguous [N, V]");
+  TORCH_CHECK(policy.size(1) > 0 && policy.size(1) <= INT_MAX, "pref: policy V out of range");
+  r.ref = nullptr;
+  if (has(ref)) {
+    TORCH_CHECK(ref->dim() == 2 && ref->size(0) == policy.size(0) && ref->size(1) == policy.size(1),
+                "pref: reference must have the policy's shape [N, V]");
+    r.ref = flat_ptr<const void>(*ref, policy, policy.scalar_type(), exactly(policy.numel()), "pref: reference");
+  }
+  r.labels = flat_ptr<const int64_t>(labels, policy, at::kLong, exactly(policy.size(0)), "pref: labels");
+  return r;
+}
+
+std::vector<Tensor> pref_fwd(const Tensor& policy, const optional<Tensor>& ref, const Tensor& labels,
+                             const optional<Tensor>& bias_p, const optional<Tensor>& bias_r, int64_t ignore) {
+  const PrefIn in = pref_in(policy, ref, labels);
+  const long N = policy.size(0);
+  const int V = policy.size(1);
+  Tensor bp, br;
+  const float* bp_p = f32_bias(bias_p, policy, V, bp, "pref: bias");
+  const float* br_p = f32_bias(bias_r, policy, V, br, "pref: ref_bias");
+  TORCH_CHECK(in.ref != nullptr || br_p == nullptr, "pref: ref_bias without a reference");
+  auto f32 = policy.options().dtype(at::kFloat);
+  auto lp_pi = at::empty({N}, f32), lp_ref = at::empty({N}, f32), lse = at::empty({N}, f32);
+  if (N > 0)
+    check_rc(dllm_pref_fwd(in.policy, in.ref, in.labels, bp_p, br_p, lp_pi.data_ptr<float>(),
+                           lp_ref.data_ptr<float>(), lse.data_ptr<float>(), N, V, ignore, is_bf16(policy), stream()),
+             "pref_fwd");
+  return {lp_pi, lp_ref, lse};
+}
+
+// (out [7] = {loss, rewards/chosen, rewards/rejected, rewards/margins, rewards/accuracies, logps/chosen,
+// logps/rejected}, pair_out [P, 8] = {loss, h, reward_c, reward_r, L_c, L_r, n_c, n_r}, coef [N]).  G: the upstream
+// scalar (none: 1); inv_pairs: 1 / P_step.  kind: 0 sigmoid, 1 hinge, 2 ipo.
+std::vector<Tensor> pref_pairs(const Tensor& lp_pi, const Tensor& lp_ref, const Tensor& labels,
+                               const optional<Tensor>& G, const Tensor& inv_pairs, int64_t T, int64_t V,
+                               int64_t ignore, double beta, int64_t kind, double eps, double sft_alpha) {
+  const int64_t N = lp_pi.numel();
+  TORCH_CHECK(T > 0 && T <= INT_MAX && N > 0 && N % (2 * T) == 0, "pref_pairs: N = ", N,
+              " rows are not 2 P T interleaved (chosen, rejected) sequences of T = ", T);
+  TORCH_CHECK(V > 0 && V <= INT_MAX, "pref_pairs: V out of range");
+  TORCH_CHECK(beta > 0.0, "pref_pairs: beta must be > 0");
+  TORCH_CHECK(eps >= 0.0 && eps < 0.5, "pref_pairs: label smoothing must lie in [0, 0.5)");
+  TORCH_CHECK(kind >= 0 && kind <= 2, "pref_pairs: kind must be 0 (sigmoid), 1 (hinge) or 2 (ipo)");
+  const int64_t P = N / (2 * T);
+  const float* lp_p = flat_ptr<const float>(lp_pi, lp_pi, at::kFloat, exactly(N), "pref_pairs: lp_pi");
+  const float* lr_p = flat_ptr<const float>(lp_ref, lp_pi, at::kFloat, exactly(N), "pref_pairs: lp_ref");
+  const int64_t* labels_p = flat_ptr<const int64_t>(labels, lp_pi, at::kLong, exactly(N), "pref_pairs: labels");
+  const float* g_p = has(G) ? flat_ptr<const float>(*G, lp_pi, at::kFloat, scalar(), "pref_pairs: G") : nullptr;
+  const float* ip_p = flat_ptr<const float>(inv_pairs, lp_pi, at::kFloat, scalar(), "pref_pairs: inv_pairs");
+  auto f32 = lp_pi.options().dtype(at::kFloat);
+  auto seq = at::empty({2 * P, 3}, f32), pair_out = at::empty({P, dllm_pref_pair_cols()}, f32);
+  auto out = at::empty({dllm_pref_out_cols()}, f32), coef = at::empty({N}, f32);
+  check_rc(dllm_pref_pairs(lp_p, lr_p, labels_p, g_p, ip_p, seq.data_ptr<float>(), pair_out.data_ptr<float>(),
+                           out.data_ptr<float>(), coef.data_ptr<float>(), P, (int)T, (int)V, ignore, beta, (int)kind,
+                           eps, sft_alpha, stream()),
+           "pref_pairs");
+  return {out, pair_out, coef};
+}
+
+Tensor pref_bwd(const Tensor& coef, Tensor policy, const Tensor& labels, const Tensor& lse,
+                const optional<Tensor>& bias_p, bool inplace) {
+  const PrefIn in = pref_in(policy, {}, labels);
+  const long N = policy.size(0);
+  const int V = policy.size(1);
+  const float* coef_p = flat_ptr<const float>(coef, policy, at::kFloat, exactly(N), "pref: coef");
+  const float* lse_p = flat_ptr<const float>(lse, policy, at::kFloat, exactly(N), "pref: lse");
+  Tensor bp;
+  const float* bp_p = f32_bias(bias_p, policy, V, bp, "pref: bias");
+  Tensor out = inplace ? policy : at::empty_like(policy);
+  if (N > 0)
+    check_rc(dllm_pref_bwd(coef_p, in.policy, in.labels, lse_p, bp_p, inplace ? in.policy : out.data_ptr(), N, V,
+                           is_bf16(policy), stream()),
+             "pref_bwd");
+  return out;
+}
+
+// the [N, Vc] bf16 chunks of the vocabulary-chunked form: same conventions as ce_chunk_* / kd_chunk_*
+void pref_chunk_fwd(const Tensor& policy, const Tensor& ref, const Tensor& labels, const optional<Tensor>& bias_p,
+                    const optional<Tensor>& bias_r, Tensor& state, Tensor& lp_pi, Tensor& lp_ref, Tensor& lse,
+                    int64_t c0, int64_t V, int64_t ignore, bool first, bool last, int64_t skip) {
+  const auto pl = chunk_logits(policy, "pref_chunk: policy");
+  const int64_t N = policy.size(0), Vc = policy.size(1);
+  const auto rf = rows<const void>(ref, policy, at::kBFloat16, kRows8.shape(N, Vc), "pref_chunk: reference");
+  const int64_t* labels_p = flat_ptr<const int64_t>(labels, policy, at::kLong, exactly(N), "pref_chunk: labels");
+  TORCH_CHECK(V > 0 && V <= INT_MAX && c0 >= 0 && c0 + Vc <= V, "pref_chunk: chunk outside the vocabulary");
+  TORCH_CHECK(skip >= 0 && skip < std::max<int64_t>(Vc, 1), "pref_chunk: skip out of range");
+  const float* bp_p = flat_ptr<const float>(bias_p, policy, at::kFloat, exactly(V), "pref_chunk: bias");
+  const float* br_p = flat_ptr<const float>(bias_r, policy, at::kFloat, exactly(V), "pref_chunk: ref_bias");
+  float* state_p = flat_ptr<float>(state, policy, at::kFloat, exactly(6 * N), "pref_chunk: state");
+  float* lp_p = flat_ptr<float>(lp_pi, policy, at::kFloat, exactly(N), "pref_chunk: lp_pi");
+  float* lr_p = flat_ptr<float>(lp_ref, policy, at::kFloat, exactly(N), "pref_chunk: lp_ref");
+  float* lse_p = flat_ptr<float>(lse, policy, at::kFloat, exactly(N), "pref_chunk: lse");
+  if (N == 0) return;
+  check_rc(dllm_pref_chunk_fwd(pl.ptr, pl.ld, rf.ptr, rf.ld, labels_p, bp_p, br_p, state_p, lp_p, lr_p, lse_p, N,
+                               (int)Vc, (int)c0, (int)V, ignore, first, last, (int)skip, stream()),
+           "pref_chunk_fwd");
+}
+
+void pref_chunk_bwd(const Tensor& coef, Tensor& policy, const Tensor& labels, const Tensor& lse,
+                    const optional<Tensor>& bias_p, int64_t c0, int64_t V, int64_t skip) {
+  const auto pl = chunk_logits(policy, "pref_chunk_bwd: policy");
+  const int64_t N = policy.size(0), Vc = policy.size(1);
+  const float* coef_p = flat_ptr<const float>(coef, policy, at::kFloat, exactly(N), "pref_chunk_bwd: coef");
+  const int64_t* labels_p = flat_ptr<const int64_t>(labels, policy, at::kLong, exactly(N), "pref_chunk_bwd: labels");
+  const float* lse_p = flat_ptr<const float>(lse, policy, at::kFloat, exactly(N), "pref_chunk_bwd: lse");
+  TORCH_CHECK(V > 0 && V <= INT_MAX && c0 >= 0 && c0 + Vc <= V, "pref_chunk_bwd: chunk outside the vocabulary");
+  TORCH_CHECK(skip >= 0 && skip < std::max<int64_t>(Vc, 1), "pref_chunk_bwd: skip out of range");
+  const float* bp_p = flat_ptr<const float>(bias_p, policy, at::kFloat, exactly(V), "pref_chunk_bwd: bias");
+  if (N == 0) return;
+  check_rc(dllm_pref_chunk_bwd(coef_p, pl.ptr, pl.ld, labels_p, lse_p, bp_p, N, (int)Vc, (int)c0, (int)skip, stream()),
+           "pref_chunk_bwd");
+}
+
 }  // namespace
 
 void bind_loss(pybind11::module& m) {
@@ -221,6 +345,11 @@ void bind_loss(pybind11::module& m) {
   m.def("kd_bwd", &kd_bwd, "student-logits gradient of the distillation loss, optionally in place");
   m.def("kd_chunk_fwd", &kd_chunk_fwd);
   m.def("kd_chunk_bwd", &kd_chunk_bwd);
+  m.def("pref_fwd", &pref_fwd, "per-row log-probabilities of policy and reference logits: (lp_pi, lp_ref, lse_pi)");
+  m.def("pref_pairs", &pref_pairs, "pairwise preference loss over 2P sequences: (out [7], pair_out [P, 8], coef [N])");
+  m.def("pref_bwd", &pref_bwd, "policy-logits gradient of the preference loss, optionally in place");
+  m.def("pref_chunk_fwd", &pref_chunk_fwd);
+  m.def("pref_chunk_bwd", &pref_chunk_bwd);
 }
 
 }  // namespace dllm

@@ -73,6 +73,23 @@ int dllm_kd_chunk_bwd(const float* w_ce, const float* w_kl, void* student, long 
                       const int64_t* labels, const float* stats, const float* bias_s, const float* bias_t, long N,
                       int Vc, int c0, int V, float eps, long ignore, float T, int skip, hipStream_t st);
 
+// ---- csrc/pref.hip
+int dllm_pref_fwd(const void* policy, const void* ref, const int64_t* labels, const float* bias_p, const float* bias_r,
+                  float* lp_pi, float* lp_ref, float* lse_pi, long N, int V, long ignore, int is_bf16, hipStream_t st);
+int dllm_pref_pair_cols();
+int dllm_pref_out_cols();
+int dllm_pref_pairs(const float* lp_pi, const float* lp_ref, const int64_t* labels, const float* G,
+                    const float* inv_pairs, float* seq_sum, float* pair_out, float* out, float* coef, long P, int T,
+                    int V, long ignore, double beta, int kind, double eps, double sft_alpha, hipStream_t st);
+int dllm_pref_bwd(const float* coef, const void* policy, const int64_t* labels, const float* lse_pi,
+                  const float* bias_p, void* dlogits, long N, int V, int is_bf16, hipStream_t st);
+int dllm_pref_chunk_fwd(const void* policy, long ld_p, const void* ref, long ld_r, const int64_t* labels,
+                        const float* bias_p, const float* bias_r, float* state, float* lp_pi, float* lp_ref,
+                        float* lse_pi, long N, int Vc, int c0, int V, long ignore, int first, int last, int skip,
+                        hipStream_t st);
+int dllm_pref_chunk_bwd(const float* coef, void* policy, long ld_p, const int64_t* labels, const float* lse_pi,
+                        const float* bias_p, long N, int Vc, int c0, int skip, hipStream_t st);
+
 // ---- csrc/adamw.hip, csrc/adafactor.hip
 int dllm_sq_norm(const void* g, long n, float* part, float* out, int is_bf16, hipStream_t st);
 int dllm_adamw(void* param, float* master, const void* grad, float* m, float* v, const uint8_t* wd_mask,

@@ -10,7 +10,8 @@ from __future__ import annotations
 import argparse
 import os
 
-from .data.dataset import convert_examples_to_features, load_samsum, synthetic_samsum_records
+from .data.dataset import (convert_examples_to_features, convert_pairs_to_features, load_samsum,
+                           synthetic_preference_records, synthetic_samsum_records)
 from .data.packing import pack_features
 from .data.tokenization import load_tokenizer
 from .models.config import resolve_config
@@ -95,6 +96,18 @@ def base_parser(description: str, defaults: dict | None = None) -> argparse.Argu
     g.add_argument("--student-layers", type=str, default=None, metavar="E,D",
                    help="build the student from the teacher with E encoder and D decoder layers (evenly spaced teacher "
                         "layers, layer 0 kept) instead of loading --model-ckpt; not with --model-overrides")
+    g.add_argument("--dpo-beta", type=float, default=None,
+                   help="preference optimisation (DPO) at this beta > 0 against a frozen reference policy: records are "
+                        "{id, dialogue, chosen, rejected}, the training loss becomes the pairwise preference loss "
+                        "(ops/preference.py); not with --teacher-ckpt, --pack-sequences or --context-parallel")
+    g.add_argument("--ref-ckpt", type=str, default=None,
+                   help="the frozen reference policy of --dpo-beta (anything --model-ckpt takes; default: a copy of "
+                        "the --model-ckpt model as loaded)")
+    g.add_argument("--dpo-loss", choices=["sigmoid", "ipo", "hinge"], default="sigmoid", help="pair loss of --dpo-beta")
+    g.add_argument("--dpo-label-smoothing", type=float, default=0.0,
+                   help="probability in [0, 0.5) that a pair's preference is flipped (sigmoid loss)")
+    g.add_argument("--dpo-sft-alpha", type=float, default=0.0,
+                   help="weight of an added length-averaged NLL term on the chosen target")
     return ap
 
 
@@ -137,6 +150,88 @@ def resolve_distill(args):
             args.student_layers = (e, d)
         args.model_ckpt = teacher
     return args
+
+
+def preference_on(args) -> bool:
+    return getattr(args, "dpo_beta", None) is not None
+
+
+def resolve_preference(args):
+    """Validate the preference-optimisation flags (loud errors that name the flag).  Returns ``args``; a no-op without
+    ``--dpo-beta``."""
+    if not preference_on(args):
+        if getattr(args, "ref_ckpt", None):
+            raise ValueError("--ref-ckpt needs --dpo-beta (it names the reference policy of the preference loss)")
+        return args
+    from .ops.preference import check_config
+    check_config(args.dpo_beta, getattr(args, "dpo_loss", "sigmoid"), getattr(args, "dpo_label_smoothing", 0.0))
+    if getattr(args, "teacher_ckpt", None):
+        raise ValueError("--teacher-ckpt and --dpo-beta exclude each other: a step trains on one loss")
+    if getattr(args, "pack_sequences", False):
+        raise NotImplementedError("--pack-sequences with --dpo-beta is not implemented: a packed row has no (chosen, "
+                                  "rejected) pair structure")
+    if getattr(args, "context_parallel", 1) > 1:
+        raise NotImplementedError("--context-parallel with --dpo-beta is not implemented (the reference's encoder is "
+                                  "not sharded)")
+    return args
+
+
+def preference_kwargs(args) -> dict:
+    """The ``dpo_*`` settings of TrainEngine / TrainingArguments / ``make_train_step`` (``{}`` without ``--dpo-beta``)."""
+    if not preference_on(args):
+        return {}
+    return {"dpo_beta": args.dpo_beta, "dpo_loss": args.dpo_loss, "dpo_label_smoothing": args.dpo_label_smoothing,
+            "dpo_sft_alpha": args.dpo_sft_alpha}
+
+
+def build_reference(args, model):
+    """The frozen reference policy of ``--dpo-beta`` (None without it): ``--ref-ckpt``, else a copy of ``model`` as it
+    stands — call it before adapters are attached or a step is taken.  The saved model is the policy alone."""
+    if not preference_on(resolve_preference(args)):
+        return None
+    import copy
+    ref = _load(args.ref_ckpt) if getattr(args, "ref_ckpt", None) else copy.deepcopy(model)
+    if ref.config.vocab_size != model.config.vocab_size:
+        raise ValueError(f"--ref-ckpt vocab_size {ref.config.vocab_size} and policy vocab_size "
+                         f"{model.config.vocab_size} differ (a reference with another vocabulary is not supported)")
+    return ref.eval().requires_grad_(False)
+
+
+def pref_logs(engine) -> dict:
+    """The six preference statistics of the engine's last micro-batch when it trains on pairs, else ``{}``."""
+    stats = getattr(engine, "last_pref_stats", None)
+    if getattr(engine, "reference", None) is None or stats is None:
+        return {}
+    return {k: round(float(v), 4) for k, v in stats.items()}
+
+
+def eval_targets(batch):
+    """The label rows generation is scored against: the chosen targets of a preference batch (``labels [2P, T]`` over
+    ``input_ids [P, S]``), else the labels."""
+    labels = batch["labels"]
+    return labels[0::2] if labels.shape[0] == 2 * batch["input_ids"].shape[0] else labels
+
+
+class PreferenceEval:
+    """Preference loss and ``rewards/accuracies`` over the validation pairs, next to generation and ROUGE."""
+
+    def __init__(self, engine):
+        self.engine, self.loss, self.acc, self.n = engine, 0.0, 0.0, 0
+
+    def add(self, batch):
+        if getattr(self.engine, "reference", None) is None:
+            return
+        import torch
+        with torch.no_grad():
+            out = self.engine.forward(batch)
+        self.loss += float(out.loss)
+        self.acc += float(out.pref_stats["rewards/accuracies"])
+        self.n += 1
+
+    def result(self) -> dict:
+        if not self.n:
+            return {}
+        return {"eval_loss": self.loss / self.n, "eval_rewards/accuracies": self.acc / self.n}
 
 
 def _load(ckpt: str, cfg=None):
@@ -218,6 +313,10 @@ def apply_overrides(cfg, spec: str | None):
 
 
 def load_records(args):
+    if args.synthetic and preference_on(args):
+        n = args.synthetic
+        return {"train": synthetic_preference_records(n, args.seed),
+                "validation": synthetic_preference_records(max(4, n // 4), args.seed + 1)}
     if args.synthetic:
         n = args.synthetic
         return {"train": synthetic_samsum_records(n, args.seed), "validation": synthetic_samsum_records(max(4, n // 4),
@@ -229,6 +328,12 @@ def load_records(args):
 def build_data(args, cfg):
     """(tokenizer, train_features, eval_features, eval_records) following convert_examples_to_features."""
     recs = load_records(args)
+    if preference_on(resolve_preference(args)):  # (dialogue, chosen, rejected) triples: data/collator.py interleaves
+        tok = load_tokenizer(args.model_ckpt, cfg, texts=[r[k] for k in ("dialogue", "chosen", "rejected")
+                                                          for r in recs["train"]])
+        ev_recs = recs["validation"][: args.max_eval_samples] if args.max_eval_samples else recs["validation"]
+        return tok, *(convert_pairs_to_features(r, tok, args.max_source_length, args.max_target_length)
+                      for r in (recs["train"], ev_recs))
     tok = load_tokenizer(args.model_ckpt, cfg, texts=[r["dialogue"] for r in recs["train"]] +
                          [r["summary"] for r in recs["train"]])
     tr = convert_examples_to_features(recs["train"], tok, args.max_source_length, args.max_target_length,
@@ -247,6 +352,7 @@ def build_data(args, cfg):
 
 
 def model_config(args):
+    resolve_preference(args)
     resolve_distill(args)
     cfg = apply_overrides(resolve_config(args.model_ckpt), args.model_overrides)
     if isinstance(getattr(args, "student_layers", None), tuple):

@@ -8,6 +8,11 @@
 Packed rows (data/packing.py: features that carry ``segment_ids``) have one fixed shape and their decoder inputs were
 built per segment by the packer, so they are stacked key by key as they are.
 
+Preference pairs (features that carry ``chosen_labels`` and ``rejected_labels``, data/dataset.py PreferenceDataset):
+``input_ids`` / ``attention_mask`` stay ``[P, S]``, one encoder row per prompt, and ``labels`` become ``[2P, T]``,
+interleaved: row ``2i`` is the chosen target of prompt ``i``, row ``2i + 1`` the rejected one, both padded to one
+``T``.  Decoder inputs are the per-row shift, as for any labels.
+
 LED (``model_type == "led"``): transformers' summarization recipe, the first token of every example is global.  The
 batch carries it twice, as ``global_attention_mask`` ``[B, S]`` (1 = global) and as ``global_index`` ``[B, 1]`` (the
 position, here 0): the index has a shape that does not depend on the data, so the model needs no host sync to size
@@ -70,8 +75,14 @@ class DataCollatorForSeq2Seq:
             gm[:, 0] = 1
             batch["global_attention_mask"] = gm
             batch["global_index"] = torch.zeros(ids.shape[0], 1, dtype=torch.int64)
-        if "labels" in features[0]:
-            labels = self._pad([np.asarray(f["labels"]) for f in features], self.label_pad_token_id)
+        if "chosen_labels" in features[0]:  # preference pairs: [2P, T], chosen / rejected interleaved
+            targets = [np.asarray(f[k]) for f in features for k in ("chosen_labels", "rejected_labels")]
+        elif "labels" in features[0]:
+            targets = [np.asarray(f["labels"]) for f in features]
+        else:
+            targets = None
+        if targets is not None:
+            labels = self._pad(targets, self.label_pad_token_id)
             batch["labels"] = labels
             if self.with_decoder_inputs:
                 dec = torch.full_like(labels, self.pad_token_id)

@@ -64,6 +64,48 @@ def convert_examples_to_features(records, tokenizer, max_source_length=1024, max
     return Seq2SeqFeatures(src["input_ids"], src["attention_mask"], labels, records)
 
 
+class PreferenceFeatures:
+    """Tokenised preference pairs: one prompt row and two target rows (chosen, rejected) per record.  ``labels`` (what
+    generation is scored against) are the chosen targets; data/collator.py interleaves the two target rows."""
+
+    def __init__(self, input_ids, attention_mask, chosen_labels, rejected_labels, records=None):
+        self.input_ids = np.asarray(input_ids, dtype=np.int32)
+        self.attention_mask = np.asarray(attention_mask, dtype=np.int8)
+        self.chosen_labels = np.asarray(chosen_labels, dtype=np.int32)
+        self.rejected_labels = np.asarray(rejected_labels, dtype=np.int32)
+        self.labels = self.chosen_labels
+        self.records = records
+
+    def __len__(self):
+        return len(self.input_ids)
+
+    def __getitem__(self, i):
+        return {"input_ids": self.input_ids[i], "attention_mask": self.attention_mask[i],
+                "chosen_labels": self.chosen_labels[i], "rejected_labels": self.rejected_labels[i]}
+
+    @property
+    def column_names(self):
+        return ["input_ids", "attention_mask", "chosen_labels", "rejected_labels"]
+
+
+def convert_pairs_to_features(records, tokenizer, max_source_length=1024, max_target_length=128, text_key="dialogue"):
+    """``{"id", "dialogue", "chosen", "rejected"}`` records -> :class:`PreferenceFeatures`.  Pad positions of both
+    targets are -100: a sequence log-probability sums the target's own tokens only."""
+    for r in records:
+        if "chosen" not in r or "rejected" not in r:
+            raise ValueError("--dpo-beta needs records with 'chosen' and 'rejected' summaries, got keys "
+                             f"{sorted(r)}")
+    src = tokenizer([r[text_key] for r in records], padding="max_length", truncation=True,
+                    max_length=max_source_length)
+    out = []
+    for key in ("chosen", "rejected"):
+        tgt = tokenizer(text_target=[r[key] for r in records], padding="max_length", truncation=True,
+                        max_length=max_target_length)
+        lab = np.asarray(tgt["input_ids"], dtype=np.int32)
+        out.append(np.where(np.asarray(tgt["attention_mask"]) == 1, lab, -100))
+    return PreferenceFeatures(src["input_ids"], src["attention_mask"], out[0], out[1], records)
+
+
 class SyntheticSeq2Seq:
     """Random token ids of the SAMSum feature shape (what bench.py and the perf configs train on)."""
 
@@ -104,6 +146,18 @@ def synthetic_samsum_records(n: int, seed: int = 0) -> list[dict]:
             turns.append(f"{who}: " + " ".join(r.choice(_WORDS) for _ in range(r.randint(3, 12))))
         summary = f"{a} and {b} " + " ".join(r.choice(_WORDS) for _ in range(r.randint(4, 12))) + "."
         out.append({"id": f"syn{i:06d}", "dialogue": "\r\n".join(turns), "summary": summary})
+    return out
+
+
+def synthetic_preference_records(n: int, seed: int = 0) -> list[dict]:
+    """Text records in the preference schema ``{"id", "dialogue", "chosen", "rejected"}``: the SAMSum-schema record's
+    summary is the chosen one, the rejected one is another draw of words."""
+    r = random.Random(seed + 7)
+    out = []
+    for rec in synthetic_samsum_records(n, seed):
+        a = rec["summary"].split()[0]
+        rejected = f"{a} " + " ".join(r.choice(_WORDS) for _ in range(r.randint(4, 12))) + "."
+        out.append({"id": rec["id"], "dialogue": rec["dialogue"], "chosen": rec["summary"], "rejected": rejected})
     return out
 
 

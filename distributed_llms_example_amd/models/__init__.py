@@ -4,9 +4,10 @@ Blenderbot / LED (models/bart.py)."""
 from .bart import BartForConditionalGeneration
 from .config import PRESETS, Seq2SeqConfig, resolve_config
 from .distill import Distill, make_student
+from .preference import Preference
 from .hf_io import build_model, from_hf_state_dict, from_pretrained, save_pretrained, to_hf_state_dict
 from .t5 import T5ForConditionalGeneration
 
 __all__ = ["PRESETS", "Seq2SeqConfig", "resolve_config", "build_model", "from_pretrained", "save_pretrained",
            "to_hf_state_dict", "from_hf_state_dict", "T5ForConditionalGeneration", "BartForConditionalGeneration",
-           "Distill", "make_student"]
+           "Distill", "make_student", "Preference"]

@@ -66,6 +66,7 @@ from . import bigbird
 from .blocks import run_block
 from .config import Seq2SeqConfig
 from .distill import lm_output as distill_lm_output
+from .preference import check_batch as preference_check_batch, lm_output as preference_lm_output
 from .output import Seq2SeqLMOutput
 
 
@@ -578,11 +579,21 @@ class BartForConditionalGeneration(nn.Module):
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, labels=None,
                 label_smoothing: float = 0.0, return_logits: bool = False, encoder_outputs=None, segment_ids=None,
                 decoder_segment_ids=None, position_ids=None, decoder_position_ids=None, global_attention_mask=None,
-                global_index=None, distill=None):
+                global_index=None, distill=None, preference=None):
         # distill: the teacher's LM-head operands and the loss weights (models/distill.py Distill); None: plain CE
+        # preference: the reference policy's LM-head operands and the loss settings (models/preference.py Preference);
+        # labels are then [2P, T] interleaved (chosen, rejected) rows over P prompts: the encoder runs once per prompt
+        if preference is not None:
+            if distill is not None or any(t is not None for t in (segment_ids, decoder_segment_ids, position_ids,
+                                                                  decoder_position_ids)):
+                raise ValueError("preference= takes neither distill= nor packed inputs (segment ids)")
+            preference_check_batch(input_ids if encoder_outputs is None else encoder_outputs, labels)
         dec, enc = self._decoder_hidden(input_ids, attention_mask, decoder_input_ids, labels, encoder_outputs,
                                         segment_ids, decoder_segment_ids, position_ids, decoder_position_ids,
                                         global_attention_mask, global_index)
+        if preference is not None:
+            return preference_lm_output(dec, self.output_embedding(), labels, preference, enc=enc,
+                                        bias=self.logits_bias(), return_logits=return_logits)
         if distill is not None:
             return distill_lm_output(dec, self.output_embedding(), labels, distill, enc=enc, bias=self.logits_bias(),
                                      label_smoothing=label_smoothing, return_logits=return_logits)

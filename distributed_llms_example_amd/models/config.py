@@ -443,6 +443,8 @@ PRESETS["bigbird-tiny"] = _bartlike("bigbird_pegasus", "bigbird-tiny", 512, 64, 
                                     eos=1, bos=2, start=2, attention_type="block_sparse", block_size=8,
                                     num_random_blocks=2, use_bias=False)
 PRESETS["t5-tiny"] = _t5("t5-tiny", 64, 128, 2, 4, vocab=512, d_kv=16)
+# the policy / reference of the preference-optimisation tests and of a --dpo-beta smoke run
+PRESETS["dpo-tiny"] = PRESETS["t5-tiny"].replace(name="dpo-tiny")
 PRESETS["t5-tiny-gated"] = _t5("t5-tiny-gated", 64, 96, 2, 4, ff="gated-gelu", tie=False, vocab=512, d_kv=16)
 PRESETS["umt5-tiny"] = _t5("umt5-tiny", 64, 96, 2, 4, ff="gated-gelu", tie=True, vocab=512, d_kv=16, flavor="umt5")
 # radius 5: a 23-token input spans several windows

@@ -14,6 +14,8 @@ class Seq2SeqLMOutput:
     # distillation (forward(distill=...), models/distill.py): the detached CE and KL means of the combined loss
     ce_loss: torch.Tensor | None = None
     kd_loss: torch.Tensor | None = None
+    # preference optimisation (forward(preference=...), models/preference.py): the six detached statistics
+    pref_stats: dict | None = None
 
     def __getitem__(self, i):
         return (self.loss, self.logits)[i]

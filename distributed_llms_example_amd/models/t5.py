@@ -40,6 +40,7 @@ from ..ops.rng import default_rng
 from .blocks import run_block
 from .config import Seq2SeqConfig
 from .distill import lm_output as distill_lm_output
+from .preference import check_batch as preference_check_batch, lm_output as preference_lm_output
 from .output import Seq2SeqLMOutput
 
 
@@ -391,12 +392,19 @@ class T5ForConditionalGeneration(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, labels=None,
                 label_smoothing: float = 0.0, return_logits: bool = False, encoder_outputs=None, segment_ids=None,
-                decoder_segment_ids=None, position_ids=None, decoder_position_ids=None, distill=None):
+                decoder_segment_ids=None, position_ids=None, decoder_position_ids=None, distill=None,
+                preference=None):
         # (position ids of a packed batch: the relative bias needs none, j - i inside an example is what it was)
         # distill: the teacher's LM-head operands and the loss weights (models/distill.py Distill); None: plain CE
+        # preference: the reference policy's LM-head operands and the loss settings (models/preference.py Preference);
+        # labels are then [2P, T] interleaved (chosen, rejected) rows over P prompts: the encoder runs once per prompt
+        if preference is not None:
+            if distill is not None or segment_ids is not None or decoder_segment_ids is not None:
+                raise ValueError("preference= takes neither distill= nor packed inputs (segment ids)")
+            preference_check_batch(input_ids if encoder_outputs is None else encoder_outputs, labels)
         dec, enc = self._decoder_hidden(input_ids, attention_mask, decoder_input_ids, labels, encoder_outputs,
                                         segment_ids, decoder_segment_ids)
-        return self._lm_output(dec, enc, labels, label_smoothing, return_logits, distill)
+        return self._lm_output(dec, enc, labels, label_smoothing, return_logits, distill, preference)
 
     def _decoder_hidden(self, input_ids, attention_mask, decoder_input_ids, labels, encoder_outputs, segment_ids,
                         decoder_segment_ids):
@@ -446,7 +454,11 @@ class T5ForConditionalGeneration(nn.Module):
         enc = encoder_outputs if encoder_outputs is not None else self.encode(input_ids, attention_mask, seg=(es, es))
         return self.decode(decoder_input_ids, enc, attention_mask, seg=(ds, ds), cross_seg=(ds, es)), enc
 
-    def _lm_output(self, dec, enc, labels, label_smoothing, return_logits, distill=None):
+    def _lm_output(self, dec, enc, labels, label_smoothing, return_logits, distill=None, preference=None):
+        if preference is not None:
+            scale = self.config.d_model ** -0.5 if self.config.scale_decoder_outputs else None
+            return preference_lm_output(dec, self.output_embedding(), labels, preference, enc=enc, scale=scale,
+                                        return_logits=return_logits)
         if distill is not None:
             scale = self.config.d_model ** -0.5 if self.config.scale_decoder_outputs else None
             return distill_lm_output(dec, self.output_embedding(), labels, distill, enc=enc, scale=scale,

@@ -38,6 +38,12 @@ distillation loss              csrc/kd.hip (``kd`` = fused): CE + KL to a teache
                                both logits tensors count against ``lmhead_full_mb``, above
                                it vocabulary chunks (``kd_chunk_*``); ``composite``: the
                                torch ops.  The GEMM-epilogue CE does not serve this loss
+preference loss                csrc/pref.hip (``pref`` = fused): per-row log-probabilities    pref_step.txt
+(DPO / IPO / hinge against a   of the policy's and the reference's logits in one pass over
+frozen reference)              both [N, V] tensors, one small launch for the pair losses,
+                               gradient in place; both logits tensors count against
+                               ``lmhead_full_mb``, above it vocabulary chunks
+                               (``pref_chunk_*``); ``composite``: the torch ops
 attention                      csrc/attn.hip bf16 flash kernels; fp32 inputs on the fp32      r4_t5base_fp32_b16_summary.txt
                                MFMA kernels of csrc/attn_f32.hip (``attn_f32`` = 1)
 cross-attention backward       one pass: dQ folded into the short-query dK/dV kernel (one    attn_sq_onepass_ab.txt
@@ -125,6 +131,8 @@ DEFAULTS: dict = {
     "lmhead_chunk_mb": 128.0,
     # distillation loss (ops/distill.py): csrc/kd.hip, or the torch composite
     "kd": "fused",                # fused | composite
+    # preference loss (ops/preference.py): csrc/pref.hip, or the torch composite
+    "pref": "fused",              # fused | composite
     # low-rank adapters (ops/lora.py): csrc/lora.hip, or the composite on torch matmuls
     "lora": "fused",              # fused | lib
     # Adafactor (ops/optim.py FusedAdafactor): csrc/adafactor.hip, or the per-unit torch composite

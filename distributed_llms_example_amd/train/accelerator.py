@@ -259,7 +259,8 @@ class Accelerator:
         return m.no_sync() if m is not None else contextlib.nullcontext()
 
     def make_train_step(self, model, optimizer, graph: bool | None = None, teacher=None, kd_alpha: float = 0.5,
-                        kd_temperature: float = 2.0):
+                        kd_temperature: float = 2.0, reference=None, dpo_beta: float = 0.1, dpo_loss: str = "sigmoid",
+                        dpo_label_smoothing: float = 0.0, dpo_sft_alpha: float = 0.0):
         """The reference loop's per-batch body — ``outputs = model(**batch); accelerator.backward(outputs.loss);
         optimizer.step(); optimizer.zero_grad()`` (ref/train-accelerator.py:219-228) — as one callable
         ``step(batch) -> loss``, run by train/graph.py's StepRunner: replayed from a HIP graph once the batch shape
@@ -268,7 +269,9 @@ class Accelerator:
         next step only (call it every iteration to clip every step); a captured graph holds the clip it was captured
         with, so a step whose clip differs drops the graph and the runner captures again (StepRunner.invalidate).
         ``teacher``: a frozen model to distil from (train/engine.py ``set_teacher``); ``step.engine`` then carries the
-        last micro-batch's ``last_ce_loss`` / ``last_kd_loss`` for logging."""
+        last micro-batch's ``last_ce_loss`` / ``last_kd_loss`` for logging.  ``reference``: a frozen reference policy
+        to optimise preferences against (``set_reference``, with the ``dpo_*`` settings); ``step.engine`` then carries
+        ``last_pref_stats``."""
         from .engine import TrainEngine
         from .graph import StepRunner
         m = model if isinstance(model, PreparedModel) else self._model
@@ -276,7 +279,9 @@ class Accelerator:
         if self.gradient_accumulation_steps != 1:
             raise ValueError("make_train_step: one micro-batch per optimizer step (use accumulate() for GA)")
         eng = TrainEngine.from_parts(m.module, self.env, m.flat, m.reducer, po.opt, max_grad_norm=None,
-                                     teacher=teacher, kd_alpha=kd_alpha, kd_temperature=kd_temperature)
+                                     teacher=teacher, kd_alpha=kd_alpha, kd_temperature=kd_temperature,
+                                     reference=reference, dpo_beta=dpo_beta, dpo_loss=dpo_loss,
+                                     dpo_label_smoothing=dpo_label_smoothing, dpo_sft_alpha=dpo_sft_alpha)
         runner = StepRunner(eng, enabled=graph)
 
         def step(batch: dict) -> torch.Tensor:

@@ -14,10 +14,12 @@ import torch
 
 from ..data.packing import PACKED_KEYS
 from ..models.distill import Distill
+from ..models.preference import Preference, check_batch as check_preference_batch
 from ..ops import gemm
 from ..ops import rng as rng_mod
 from ..ops import streams
 from ..ops.distill import check_weights
+from ..ops.preference import check_config as check_preference
 from ..ops.optim import FusedAdafactor, FusedAdamW
 from ..utils import profiling
 from ..parallel.env import DistEnv
@@ -45,20 +47,29 @@ def token_count(labels: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
     return (labels != ignore_index).sum()
 
 
+def pair_count(labels: torch.Tensor) -> torch.Tensor:
+    """Preference pairs of a micro-batch (``labels [2P, T]``: interleaved chosen / rejected rows), as a device scalar."""
+    return torch.full((), labels.shape[0] // 2, dtype=torch.int64, device=labels.device)
+
+
 class TrainEngine:
     def __init__(self, model: torch.nn.Module, env: DistEnv, *, lr: float = 5e-5, weight_decay: float = 0.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float | None = 1.0,
                  dtype: torch.dtype = torch.bfloat16, bucket_mb: float | str = DEFAULT_BUCKET_MB, overlap: bool = True,
                  no_decay=default_no_decay, label_smoothing: float = 0.0, grad_dtype: torch.dtype | None = None,
                  force_reducer: bool = False, grad_reduce_dtype: str | None = None, optim: str = "adamw",
-                 teacher: torch.nn.Module | None = None, kd_alpha: float = 0.5, kd_temperature: float = 2.0):
+                 teacher: torch.nn.Module | None = None, kd_alpha: float = 0.5, kd_temperature: float = 2.0,
+                 reference: torch.nn.Module | None = None, dpo_beta: float = 0.1, dpo_loss: str = "sigmoid",
+                 dpo_label_smoothing: float = 0.0, dpo_sft_alpha: float = 0.0):
         """``bucket_mb``: MiB per all-reduce bucket, or "auto" (parallel/reducer.py choose_bucket_mb: probed on the
         job's process group, recorded in ``reducer.bucket_choice``).  ``grad_reduce_dtype``: "bf16" compresses each bucket
         for the wire only (fp32 accumulation kept), None / "fp32" reduces the gradient buffer as it is.  ``optim``:
         "adamw", or "adafactor" as the HF Trainer builds it (scale_parameter=False, relative_step=False, the learning
         rate from ``lr``; ``betas`` / ``eps`` are AdamW's and unused).  ``teacher``: a frozen model to distil from
         (``set_teacher``): training steps then minimise (1 - kd_alpha) CE + kd_alpha T^2 KL(teacher || student) at
-        temperature ``kd_temperature`` (ops/distill.py)."""
+        temperature ``kd_temperature`` (ops/distill.py).  ``reference``: a frozen reference policy (``set_reference``):
+        training steps then minimise the preference loss (ops/preference.py) of batches of (prompt, chosen, rejected)
+        triples, normalised by pairs."""
         self.env = env
         self.model = model.to(device=env.device, dtype=dtype)
         self.dtype = dtype
@@ -86,6 +97,42 @@ class TrainEngine:
         self.step_seed: rng_mod.StepSeed | None = None
         self._init_defer()
         self.set_teacher(teacher, kd_alpha, kd_temperature)
+        self.set_reference(reference, dpo_beta, dpo_loss, dpo_label_smoothing, dpo_sft_alpha)
+
+    def set_reference(self, model: torch.nn.Module | None, beta: float = 0.1, kind: str = "sigmoid",
+                      label_smoothing: float = 0.0, sft_alpha: float = 0.0) -> None:
+        """Preference optimisation against the frozen reference policy ``model`` (None: plain CE).  Like a teacher
+        (``set_teacher``) the reference is cast to the compute dtype, put in ``eval()`` and frozen; it lives outside the
+        flat parameters, the reducer, the optimizer and the checkpoints, and runs under ``no_grad`` in a seed scope of
+        its own, on the step's stream.  Batches then carry ``labels [2P, T]`` (interleaved chosen / rejected rows) over
+        ``input_ids [P, S]``, and ``forward_backward`` normalises by pairs."""
+        self.reference = None
+        self.dpo = (float(beta), str(kind), float(label_smoothing), float(sft_alpha))
+        self.last_pref_stats = None
+        if model is None:
+            return
+        check_preference(beta, kind, label_smoothing)
+        if self.teacher is not None:
+            raise ValueError("a reference policy (--dpo-beta) and a teacher (--teacher-ckpt) exclude each other")
+        rv, pv = model.config.vocab_size, self.model.config.vocab_size
+        if rv != pv:
+            raise ValueError(f"reference (--ref-ckpt) vocab_size {rv} and policy vocab_size {pv} differ (a reference "
+                             "with another vocabulary is not supported)")
+        if model is self.model:
+            raise ValueError("the reference must be a model of its own (a frozen copy), not the policy")
+        self._check_reference_cp()
+        self.reference = model.to(device=self.env.device, dtype=self.dtype).eval().requires_grad_(False)
+
+    def _check_reference_cp(self) -> None:
+        enc = getattr(self.model, "encoder", None)
+        if getattr(enc, "_cp_group", False) is not False:
+            raise NotImplementedError("--context-parallel with --dpo-beta is not implemented: the reference's encoder "
+                                      "is not sharded")
+
+    def item_count(self, labels: torch.Tensor) -> torch.Tensor:
+        """What an optimizer step's loss is normalised by, counted on one micro-batch (a device scalar): preference
+        pairs with a reference policy, else non-ignored target tokens."""
+        return pair_count(labels) if self.reference is not None else token_count(labels)
 
     def set_teacher(self, teacher: torch.nn.Module | None, alpha: float = 0.5, temperature: float = 2.0) -> None:
         """Distil from ``teacher`` (None: plain CE).  The teacher is cast to the compute dtype, put in ``eval()`` and
@@ -96,6 +143,8 @@ class TrainEngine:
         self.last_ce_loss = self.last_kd_loss = None
         if teacher is None:
             return
+        if getattr(self, "reference", None) is not None:
+            raise ValueError("a teacher (--teacher-ckpt) and a reference policy (--dpo-beta) exclude each other")
         check_weights(alpha, temperature)
         tv, sv = teacher.config.vocab_size, self.model.config.vocab_size
         if tv != sv:
@@ -141,7 +190,9 @@ class TrainEngine:
     @classmethod
     def from_parts(cls, model: torch.nn.Module, env: DistEnv, flat: FlatParams, reducer: GradReducer | None,
                    optimizer: FusedAdamW, max_grad_norm: float | None = None, label_smoothing: float = 0.0,
-                   teacher: torch.nn.Module | None = None, kd_alpha: float = 0.5, kd_temperature: float = 2.0):
+                   teacher: torch.nn.Module | None = None, kd_alpha: float = 0.5, kd_temperature: float = 2.0,
+                   reference: torch.nn.Module | None = None, dpo_beta: float = 0.1, dpo_loss: str = "sigmoid",
+                   dpo_label_smoothing: float = 0.0, dpo_sft_alpha: float = 0.0):
         """An engine over state another front end already built (train/accelerator.py: the prepared model's flat
         buffers and reducer, the prepared optimizer), so its loop can run the same step — and the same HIP-graph
         step runner (train/graph.py) — as the Trainer."""
@@ -152,6 +203,7 @@ class TrainEngine:
         eng.step_seed = None
         eng._init_defer()
         eng.set_teacher(teacher, kd_alpha, kd_temperature)
+        eng.set_reference(reference, dpo_beta, dpo_loss, dpo_label_smoothing, dpo_sft_alpha)
         return eng
 
     def enable_step_seeds(self, start: int | None = None) -> rng_mod.StepSeed:
@@ -178,7 +230,9 @@ class TrainEngine:
 
     def forward(self, batch: dict, distill: bool = True):
         """The model's forward on ``batch``.  With a teacher (``set_teacher``) the teacher runs first, under ``no_grad``,
-        and the loss is the distillation loss; ``distill=False`` (evaluation) keeps plain CE on the student alone."""
+        and the loss is the distillation loss; ``distill=False`` (evaluation) keeps plain CE on the student alone.
+        With a reference policy (``set_reference``) the reference runs first, the same way, and the loss is the
+        preference loss of the batch's pairs, in training and in evaluation alike."""
         self.flat.reset_pending()
         # packed rows (data/packing.py) carry their segment and position ids; other batches none of these keys
         packed = {k: batch[k] for k in PACKED_KEYS if k in batch}
@@ -193,6 +247,17 @@ class TrainEngine:
                     input_ids=batch["input_ids"], attention_mask=batch.get("attention_mask"),
                     decoder_input_ids=batch.get("decoder_input_ids"), labels=batch["labels"], **packed)
             packed["distill"] = Distill(th, tw, tb, self.kd_alpha, self.kd_temperature)
+        if self.reference is not None:
+            self._check_reference_cp()
+            if any(k in batch for k in PACKED_KEYS):
+                raise NotImplementedError("--pack-sequences with --dpo-beta is not implemented: a packed row has no "
+                                          "(chosen, rejected) pair structure")
+            check_preference_batch(batch["input_ids"], batch["labels"])
+            with torch.no_grad(), rng_mod.rng_scope(0):  # a seed stream of its own, as the teacher's
+                rh, rw, rb = self.reference.lm_head_operands(
+                    input_ids=batch["input_ids"], attention_mask=batch.get("attention_mask"),
+                    decoder_input_ids=batch.get("decoder_input_ids"), labels=batch["labels"], **packed)
+            packed["preference"] = Preference(rh, rw, rb, *self.dpo)
         return self.model(input_ids=batch["input_ids"], attention_mask=batch.get("attention_mask"),
                           decoder_input_ids=batch.get("decoder_input_ids"), labels=batch["labels"],
                           label_smoothing=self.label_smoothing, **packed)
@@ -208,7 +273,8 @@ class TrainEngine:
                          num_items: torch.Tensor | None = None, dp_ranks: int | None = None) -> torch.Tensor:
         """Forward + backward of one micro-batch; returns its mean loss (detached).
 
-        ``num_items``: the GLOBAL number of non-ignored target tokens of the whole optimizer step (all GA
+        ``num_items``: the GLOBAL number of non-ignored target tokens (with a reference policy: of preference pairs,
+        ``item_count``) of the whole optimizer step (all GA
         micro-batches on all data-parallel ranks, a device scalar).  Given, the gradient is that of
         Σ token losses / num_items — every token weighs the same however the tokens are spread over
         micro-batches and ranks (HF Trainer ``num_items_in_batch``); the reducer's average
@@ -243,10 +309,11 @@ class TrainEngine:
                 loss = out.loss
                 # the distillation loss's components of this micro-batch (None without a teacher), for logging
                 self.last_ce_loss, self.last_kd_loss = getattr(out, "ce_loss", None), getattr(out, "kd_loss", None)
+                self.last_pref_stats = getattr(out, "pref_stats", None)  # the preference statistics, likewise
             with profiling.range("backward" if sync else "backward(no_sync)"):
                 if num_items is not None:
                     w = dp_ranks if dp_ranks is not None else (self.reducer.world if self.reducer is not None else 1)
-                    scale = token_count(batch["labels"]).to(torch.float32) * w / num_items.to(torch.float32)
+                    scale = self.item_count(batch["labels"]).to(torch.float32) * w / num_items.to(torch.float32)
                     (loss * scale).backward()
                 else:
                     (loss / grad_accum if grad_accum > 1 else loss).backward()

@@ -34,7 +34,7 @@ from ..utils.logging import get_logger
 from .callbacks import CallbackHandler, DefaultFlowCallback, TrainerControl, TrainerState
 from ..utils import faults
 from .checkpoint import latest_checkpoint, load_checkpoint, save_checkpoint
-from .engine import TrainEngine, default_no_decay, token_count
+from .engine import TrainEngine, default_no_decay
 from .graph import StepRunner, graphs_enabled
 from .schedule import LRScheduler
 
@@ -80,6 +80,10 @@ class TrainingArguments:
     resume_from_checkpoint: str | None = None
     kd_alpha: float = 0.5  # distillation (Trainer(teacher=...)): weight of the KL term, and its temperature
     kd_temperature: float = 2.0
+    dpo_beta: float = 0.1  # preference optimisation (Trainer(reference=...)): ops/preference.py's settings
+    dpo_loss: str = "sigmoid"
+    dpo_label_smoothing: float = 0.0
+    dpo_sft_alpha: float = 0.0
     nan_guard: bool = True  # raise when the (logged, already synchronised) mean loss is NaN/Inf
     # Run an optimizer step's gradient-accumulation micro-batches as fewer, larger forward/backward passes (same
     # samples, same token-count normalisation, same single optimizer step).  The reference accumulates 16 micro-batches
@@ -112,7 +116,8 @@ class TrainOutput:
 
 class Trainer:
     def __init__(self, model, args: TrainingArguments, train_dataset=None, eval_dataset=None, data_collator=None,
-                 callbacks=None, tokenizer=None, processing_class=None, compute_metrics=None, env=None, teacher=None):
+                 callbacks=None, tokenizer=None, processing_class=None, compute_metrics=None, env=None, teacher=None,
+                 reference=None):
         self.args = args
         self.env = env or init_distributed(timeout_s=args.ddp_timeout)
         self.tokenizer = processing_class if processing_class is not None else tokenizer
@@ -138,7 +143,9 @@ class Trainer:
                                   grad_reduce_dtype=args.grad_reduce_dtype,
                                   no_decay=default_no_decay, label_smoothing=args.label_smoothing_factor,
                                   optim="adafactor" if args.optim == "adafactor" else "adamw",
-                                  teacher=teacher, kd_alpha=args.kd_alpha, kd_temperature=args.kd_temperature)
+                                  teacher=teacher, kd_alpha=args.kd_alpha, kd_temperature=args.kd_temperature,
+                                  reference=reference, dpo_beta=args.dpo_beta, dpo_loss=args.dpo_loss,
+                                  dpo_label_smoothing=args.dpo_label_smoothing, dpo_sft_alpha=args.dpo_sft_alpha)
         self.model = self.engine.model
         self.train_dataset = train_dataset
         self.eval_dataset = eval_dataset
@@ -320,7 +327,7 @@ class Trainer:
                     self._batch_shape = [int(b0["labels"].shape[0]), int(b0["input_ids"].shape[1]),
                                          int(b0["labels"].shape[1])]
                 done += len(group)
-                num_items = sum(token_count(b["labels"]) for b in group)
+                num_items = sum(eng.item_count(b["labels"]) for b in group)  # tokens; pairs with a reference policy
                 if self.dp_world > 1:
                     dist.all_reduce(num_items)
                     if self.cp_group is not None:  # every CP rank of a DP group counted the same batch
@@ -347,7 +354,7 @@ class Trainer:
                 for pb, loss in zip(passes, losses):
                     # logged loss: token-weighted mean (sum of token losses / tokens), the same number whether the
                     # micro-batches run one by one or merged into passes of different token counts
-                    ntok = sum(token_count(b["labels"]) for b in pb).float()
+                    ntok = sum(eng.item_count(b["labels"]) for b in pb).float()
                     tr_loss_sum += loss.float() * ntok
                     tr_loss_n += ntok
                 if cap == -1:  # decide from the first (uncoalesced) step's measured activation memory
@@ -385,6 +392,10 @@ class Trainer:
                     if eng.teacher is not None and eng.last_ce_loss is not None:  # the last micro-batch's components
                         kd = collectives.mean_across_processes(
                             {"ce_loss": float(eng.last_ce_loss), "kd_loss": float(eng.last_kd_loss)}, env.device)
+                        kd = {k: round(v, 4) for k, v in kd.items()}
+                    if eng.reference is not None and eng.last_pref_stats is not None:  # the last micro-batch's
+                        kd = collectives.mean_across_processes(
+                            {k: float(v) for k, v in eng.last_pref_stats.items()}, env.device)
                         kd = {k: round(v, 4) for k, v in kd.items()}
                     self.log({"loss": round(mean, 4), **kd,
                               "grad_norm": float(last_norm) if last_norm is not None else None,
@@ -450,6 +461,7 @@ class Trainer:
         # evaluation shards samples over every rank, full sequences (no context parallelism)
         loader, _ = self._loader(ds, self.args.per_device_eval_batch_size, False, cp=False)
         tot = torch.zeros((), device=self.env.device, dtype=torch.float64)
+        acc = torch.zeros((), device=self.env.device, dtype=torch.float64)
         n = 0
         if self.cp_group is not None:
             self.model.enable_context_parallel(enable=False)
@@ -457,12 +469,17 @@ class Trainer:
             for batch in loader:
                 out = self.engine.forward(self._to_device(batch), distill=False)  # plain CE on the student alone
                 tot += out.loss.double()
+                if out.pref_stats is not None:  # with a reference policy: the preference loss of the validation pairs
+                    acc += out.pref_stats["rewards/accuracies"].double()
                 n += 1
         finally:
             if self.cp_group is not None:
                 self.model.enable_context_parallel(self.cp_group)
-        m = collectives.mean_across_processes({"eval_loss": float(tot) / max(1, n)}, self.env.device)
-        metrics = {"eval_loss": m["eval_loss"], "epoch": round(self.state.epoch, 4)}
+        vals = {"eval_loss": float(tot) / max(1, n)}
+        if self.engine.reference is not None:
+            vals["eval_rewards/accuracies"] = float(acc) / max(1, n)
+        m = collectives.mean_across_processes(vals, self.env.device)
+        metrics = {**m, "epoch": round(self.state.epoch, 4)}
         self.log(metrics)
         self.handler.fire("on_evaluate", self.args, self.state, self.control, metrics=metrics)
         return metrics

@@ -24,9 +24,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from torch.utils.data import DataLoader  # noqa: E402
 
-from distributed_llms_example_amd.cli import (base_parser, build_data, build_models, eval_batch_size,  # noqa: E402
-                                              kd_logs, maybe_apply_lora,
-                                              model_config)
+from distributed_llms_example_amd.cli import (PreferenceEval, base_parser, build_data, build_models,  # noqa: E402
+                                              build_reference, eval_batch_size, eval_targets, kd_logs,
+                                              maybe_apply_lora, model_config, pref_logs, preference_kwargs)
 from distributed_llms_example_amd.data.collator import DataCollatorForSeq2Seq  # noqa: E402
 from distributed_llms_example_amd.utils import faults  # noqa: E402
 from distributed_llms_example_amd.ops.rng import manual_seed  # noqa: E402
@@ -56,6 +56,7 @@ class ModelTrainer:
         self.model, self.teacher = build_models(args, self.cfg)
         if self.cfg.gradient_checkpointing:
             self.model.gradient_checkpointing_enable()
+        self.reference = build_reference(args, self.model)  # --dpo-beta: a frozen copy, before adapters are attached
         maybe_apply_lora(self.model, args, print if self.accelerator.is_main_process else None)
 
     def dump(self, logs):
@@ -86,7 +87,8 @@ class ModelTrainer:
         lr_scheduler = get_scheduler("linear", optimizer, num_warmup_steps=1, num_training_steps=max_train_steps)
         metric = rouge.load("rouge")
         train_step = acc.make_train_step(model, optimizer, teacher=self.teacher, kd_alpha=a.kd_alpha,
-                                         kd_temperature=a.kd_temperature)
+                                         kd_temperature=a.kd_temperature, reference=self.reference,
+                                         **preference_kwargs(a))
         self.dump({"comm": train_step.runner.comm_report()})  # bucket choice and step schedules of this run
         self.logger.info(f"***** Running training ***** examples={len(train_ds)} epochs={a.num_epochs}")
         completed = 0
@@ -110,7 +112,8 @@ class ModelTrainer:
                     t_warm = time.perf_counter()
                 faults.maybe_inject(completed, acc.process_index)
                 if completed % 300 == 0:
-                    self.dump({"loss": loss.item(), **kd_logs(train_step.engine), "step": completed})
+                    self.dump({"loss": loss.item(), **kd_logs(train_step.engine), **pref_logs(train_step.engine),
+                               "step": completed})
                 if completed >= max_train_steps:
                     break
             torch.cuda.synchronize() if acc.device.type == "cuda" else None
@@ -125,12 +128,14 @@ class ModelTrainer:
                 tp["train_steady_samples_per_second"] = round(per_step * (completed - warm) / (t1 - t_warm), 3)
             self.dump(tp)
             model.eval()
+            pref_eval = PreferenceEval(train_step.engine)  # --dpo-beta: the preference loss of the validation pairs
             for batch in eval_dl:
+                pref_eval.add(batch)
                 with torch.no_grad():
                     gen = acc.unwrap_model(model).generate(batch["input_ids"], attention_mask=batch["attention_mask"],
                                                            max_length=a.gen_max_length, num_beams=a.num_beams)
                     gen = acc.pad_across_processes(gen, dim=1, pad_index=tokenizer.pad_token_id)
-                    labels = acc.pad_across_processes(batch["labels"], dim=1, pad_index=-100)
+                    labels = acc.pad_across_processes(eval_targets(batch), dim=1, pad_index=-100)
                     gen = acc.gather(gen).cpu().numpy()
                     labels = acc.gather(labels).cpu().numpy()
                     labels = np.where(labels != -100, labels, tokenizer.pad_token_id)
@@ -138,7 +143,7 @@ class ModelTrainer:
                     refs = tokenizer.batch_decode(labels, skip_special_tokens=True)
                     metric.add_batch(predictions=preds, references=refs)
             metrics = metric.compute(use_stemmer=True)
-            self.dump(acc.reduce_mean(metrics))
+            self.dump(acc.reduce_mean({**metrics, **pref_eval.result()}))
         if output_dir is not None:
             acc.wait_for_everyone()
             acc.save_model(model, output_dir)

@@ -50,7 +50,9 @@ def run(env, args):
     import numpy as np
     from torch.utils.data import DataLoader
 
-    from distributed_llms_example_amd.cli import build_data, build_models, kd_logs, maybe_apply_lora, model_config
+    from distributed_llms_example_amd.cli import (PreferenceEval, build_data, build_models, build_reference,
+                                                  eval_targets, kd_logs, maybe_apply_lora, model_config, pref_logs,
+                                                  preference_kwargs)
     from distributed_llms_example_amd.data.collator import DataCollatorForSeq2Seq
     from distributed_llms_example_amd.ops.rng import manual_seed
     from distributed_llms_example_amd.parallel import collectives
@@ -78,13 +80,15 @@ def run(env, args):
     model, teacher = build_models(args, cfg)
     if cfg.gradient_checkpointing:
         model.gradient_checkpointing_enable()
+    reference = build_reference(args, model)  # --dpo-beta: a frozen copy, before adapters are attached
     maybe_apply_lora(model, args, print if env.is_main_process else None)
     dtype = torch.bfloat16 if (args.precision or ("bf16" if env.device.type == "cuda" else "fp32")) == "bf16" \
         else torch.float32
     eng = TrainEngine(model, env, lr=args.learning_rate, weight_decay=0.0, max_grad_norm=None, dtype=dtype,
                       bucket_mb=args.bucket_mb or "auto", overlap=not args.no_overlap, no_decay=None,
                       grad_reduce_dtype=args.grad_reduce_dtype, optim=args.optim, teacher=teacher,
-                      kd_alpha=args.kd_alpha, kd_temperature=args.kd_temperature)
+                      kd_alpha=args.kd_alpha, kd_temperature=args.kd_temperature, reference=reference,
+                      **preference_kwargs(args))
     collator = DataCollatorForSeq2Seq.for_model(cfg, pad_to_multiple_of=8)
     # partition_dataset (ref/train-task.py:176-191)
     world = env.world_size
@@ -118,23 +122,27 @@ def run(env, args):
             completed += 1
             faults.maybe_inject(completed, env.rank)
             if completed % 100 == 0:
-                dump_metrics({"loss": float(loss), **kd_logs(eng), "step": completed}, env.is_main_process)
+                dump_metrics({"loss": float(loss), **kd_logs(eng), **pref_logs(eng), "step": completed},
+                             env.is_main_process)
             if completed >= max_steps:
                 break
         eng.train(False)
+        pref_eval = PreferenceEval(eng)  # --dpo-beta: the preference loss of the validation pairs
         for batch in eval_dl:
             batch = {k: v.to(dev) for k, v in batch.items()}
+            pref_eval.add(batch)
             with torch.no_grad():
                 gen = eng.model.generate(batch["input_ids"], attention_mask=batch["attention_mask"],
                                          max_length=args.gen_max_length, num_beams=args.num_beams)
             gen = collectives.pad_across_processes(gen, dim=1, pad_index=tok.pad_token_id)
-            labels = collectives.pad_across_processes(batch["labels"], dim=1, pad_index=-100)
+            labels = collectives.pad_across_processes(eval_targets(batch), dim=1, pad_index=-100)
             gen = collectives.gather(gen).cpu().numpy()
             labels = collectives.gather(labels).cpu().numpy()
             labels = np.where(labels != -100, labels, tok.pad_token_id)
             metric.add_batch(predictions=tok.batch_decode(gen, skip_special_tokens=True),
                              references=tok.batch_decode(labels, skip_special_tokens=True))
         result = {k: round(v * 100, 4) for k, v in metric.compute(use_stemmer=True).items()}
+        result.update(pref_eval.result())
         result["epoch"] = epoch
         avg = collectives.mean_across_processes(result, dev)
         if env.is_main_process:

@@ -20,8 +20,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("TRANSFORMERS_NO_ADVISORY_WARNINGS", "true")
 
-from distributed_llms_example_amd.cli import (base_parser, build_data, build_models, eval_batch_size,  # noqa: E402
-                                              maybe_apply_lora, model_config)
+from distributed_llms_example_amd.cli import (base_parser, build_data, build_models, build_reference,  # noqa: E402
+                                              eval_batch_size, maybe_apply_lora, model_config, preference_kwargs)
 from distributed_llms_example_amd.data.collator import DataCollatorForSeq2Seq  # noqa: E402
 from distributed_llms_example_amd.parallel.env import init_distributed  # noqa: E402
 from distributed_llms_example_amd.platform import valohai  # noqa: E402
@@ -52,6 +52,7 @@ def run(args):
     model, teacher = build_models(args, cfg)
     if cfg.gradient_checkpointing:
         model.gradient_checkpointing_enable()
+    reference = build_reference(args, model)  # --dpo-beta: a frozen copy, before adapters are attached
     maybe_apply_lora(model, args, print if env.is_main_process else None)
     targs = TrainingArguments(
         output_dir=output_dir, num_train_epochs=args.num_epochs, warmup_steps=args.warmup_steps,
@@ -63,10 +64,10 @@ def run(args):
         bf16=None if args.precision is None else args.precision == "bf16",
         ddp_bucket_cap_mb=args.bucket_mb, overlap_comm=not args.no_overlap, grad_reduce_dtype=args.grad_reduce_dtype,
         context_parallel_size=args.context_parallel, kd_alpha=args.kd_alpha, kd_temperature=args.kd_temperature,
-        coalesce_grad_accum=getattr(args, "coalesce_grad_accum", "auto"))
+        coalesce_grad_accum=getattr(args, "coalesce_grad_accum", "auto"), **preference_kwargs(args))
     trainer = Trainer(model=model, args=targs, tokenizer=tok, data_collator=DataCollatorForSeq2Seq.for_model(cfg),
                       train_dataset=train_ds, eval_dataset=eval_ds, callbacks=[PrinterCallback], env=env,
-                      teacher=teacher)
+                      teacher=teacher, reference=reference)
     resume = True if args.resume_from == "latest" else args.resume_from
     trainer.train(resume_from_checkpoint=resume)
     trainer.save_model(output_dir)
