@@ -11,10 +11,6 @@ using namespace dllm;
 
 namespace {
 
-// eps * mean_v(x_v).  Without smoothing the term is left out, not multiplied by 0: a banned token's -inf logit (BART
-// final_logits_bias) makes the row's sum of logits -inf, and 0 * -inf would turn a finite loss into NaN.
-DLLM_DEVICE float smooth_term(float eps, float sum_x, int V) { return eps != 0.f ? eps * sum_x / (float)V : 0.f; }
-
 template <typename T>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
                                                      const float* __restrict__ bias, float* __restrict__ loss_out,

@@ -9,6 +9,9 @@
 //      student exponential: lse(s/T) is lse(s).
 // bwd: ds_v = w_ce (softmax(s)_v - eps/V - (1-eps)[v==y]) + w_kl T (q_v - p_v), w_ce / w_kl device scalars (no host
 //      sync), written in the logits dtype, optionally in place over the student logits.  The teacher gets no gradient.
+// -inf logits: a column with p_v = 0 adds nothing to kl whatever s_v is; p_v > 0 with s_v = -inf gives kl = +inf (not
+//      NaN); with eps == 0 the smoothing term is absent (row_walk.h smooth_term), so ce stays finite with -inf off the
+//      label; the gradient is finite wherever stats is.
 // No atomics: every sum has a fixed order, reruns are bit-identical.
 #include "common.h"
 #include "row_walk.h"
@@ -23,6 +26,13 @@ namespace {
 // vectors; the student's in fwd); the other rows' 16-B groups are read through element-aligned vector types
 // (Vec16::load_e), for which the compiler emits whatever the target's unaligned-access mode allows (one dwordx4 on
 // gfx950) — no row's alignment is assumed from another's.
+
+// -inf logits (a banned token: BART's final_logits_bias).  A column whose teacher weight w = exp((t - m_t)/T) is 0
+// contributes nothing to A, whatever s is: w (t - s) would be 0 * -inf, or 0 * NaN when both models ban the column.
+// A column with w > 0 and s = -inf makes A, and with it kl, +inf; such an A is carried through a rescale whose factor
+// has underflowed to 0 as 0 (its columns' weights are 0 at the new maximum), never as inf * 0.
+DLLM_DEVICE float kd_term(float w, float d) { return w != 0.f ? w * d : 0.f; }
+DLLM_DEVICE float kd_rescale(float a, float f) { return f != 0.f ? a * f : 0.f; }
 
 // Per-thread running state of the three softmaxes of one row.
 template <bool T1>
@@ -62,8 +72,15 @@ struct KdAcc {
         a += w * (t[k] - s[k]);
       }
       const float f = mt == -INFINITY ? 0.f : __expf((mt - nt) * invT);
+      float An = A * f + a;
+      if (An != An) {  // a zero weight met an infinite factor (0 * inf): the group again, by the rules above.  The
+        a = 0.f;       // selects stay out of the common path: one per column cost the T != 1 forward 2 %.
+#pragma unroll
+        for (int k = 0; k < E; ++k) a += kd_term(__expf((t[k] - nt) * invT), t[k] - s[k]);
+        An = kd_rescale(A, f) + a;
+      }
       zt = zt * f + e;
-      A = A * f + a;
+      A = An;
       mt = nt;
     }
 #pragma unroll
@@ -87,7 +104,7 @@ DLLM_DEVICE KdRow kd_block_merge(const KdAcc<T1>& a, float invT, float* red) {
   r.Mt = block_max<256>(a.mt, red);
   const float ft = a.mt == -INFINITY ? 0.f : __expf((a.mt - r.Mt) * invT);
   r.Zt = block_sum<256>(a.zt * ft, red);
-  r.A = block_sum<256>(a.A * ft, red);
+  r.A = block_sum<256>(kd_rescale(a.A, ft), red);
   return r;
 }
 
@@ -137,7 +154,7 @@ __global__ __launch_bounds__(256) void kd_fwd_kernel(const T* __restrict__ stude
     if (y != ignore && y >= 0 && y < V) {
       float xy = Elem<T>::load(x + y);
       if (bias_s != nullptr) xy += bias_s[y];
-      ce = lse_s - (1.f - eps) * xy - eps * r.SX / (float)V;
+      ce = lse_s - (1.f - eps) * xy - smooth_term(eps, r.SX, V);
       kl = r.A / r.Zt * invT - lse_tT + lse_sT;
     }
     ce_out[row] = ce;
@@ -261,7 +278,7 @@ __global__ __launch_bounds__(256) void kd_chunk_fwd_kernel(const uint16_t* __res
     const float go = mt == -INFINITY ? 0.f : __expf((mt - nt) * invT);
     const float gn = r.Mt == -INFINITY ? 0.f : __expf((r.Mt - nt) * invT);
     zt = zt * go + r.Zt * gn;
-    A = A * go + r.A * gn;
+    A = kd_rescale(A, go) + kd_rescale(r.A, gn);
     mt = nt;
     if (y >= c0 + skip && y < c0 + Vc)
       sy = Elem<uint16_t>::load(x + (y - c0)) + (bias_s != nullptr ? bias_s[y] : 0.f);
@@ -271,7 +288,7 @@ __global__ __launch_bounds__(256) void kd_chunk_fwd_kernel(const uint16_t* __res
       const float lse_sT = T1 ? lse_s : ms * invT + __logf(zsT);
       const float lse_tT = mt * invT + __logf(zt);
       const bool valid = y != ignore && y >= 0 && y < V;
-      ce_out[row] = valid ? lse_s - (1.f - eps) * sy - eps * sx / (float)V : 0.f;
+      ce_out[row] = valid ? lse_s - (1.f - eps) * sy - smooth_term(eps, sx, V) : 0.f;
       kl_out[row] = valid ? A / zt * invT - lse_tT + lse_sT : 0.f;
       stats[row * 3 + 0] = lse_s;
       stats[row * 3 + 1] = lse_sT;

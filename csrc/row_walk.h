@@ -56,6 +56,10 @@ struct Vec16 {
   }
 };
 
+// eps * mean_v(x_v).  Without smoothing the term is left out, not multiplied by 0: a banned token's -inf logit (BART
+// final_logits_bias) makes the row's sum of logits -inf, and 0 * -inf would turn a finite loss into NaN.
+DLLM_DEVICE float smooth_term(float eps, float sum_x, int V) { return eps != 0.f ? eps * sum_x / (float)V : 0.f; }
+
 // bias[i .. i + 3] of a vocabulary chunk: one 16-B load when that address is 16-B aligned, else four scalar loads (the
 // ragged vocab tail chunk starts at c0 = V - Vc, odd for BART's V = 50265)
 DLLM_DEVICE f32x4 bias4(const float* __restrict__ bias, int i) {

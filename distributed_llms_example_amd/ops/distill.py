@@ -41,7 +41,10 @@ def check_weights(alpha: float, temperature: float) -> None:
 
 
 def _reference(student_logits, teacher_logits, labels, bias, teacher_bias, smoothing, ignore_index, alpha, temperature):
-    """(loss, ce, kl) of the definition in plain torch (fp32 math; fp64 logits stay fp64)."""
+    """(loss, ce, kl) of the definition in plain torch (fp32 math; fp64 logits stay fp64).  ``-inf`` logits (a banned
+    token in a logits bias): a column with ``p_v = 0`` adds nothing to ``kl`` whatever ``s_v`` is (``0 * -inf`` is
+    never formed, forward or backward), ``p_v > 0`` with ``s_v = -inf`` gives ``kl = +inf``, and the gradient stays
+    finite."""
     up = torch.float64 if student_logits.dtype == torch.float64 else torch.float32
     s = student_logits.to(up)
     t = teacher_logits.detach().to(up)
@@ -54,7 +57,8 @@ def _reference(student_logits, teacher_logits, labels, bias, teacher_bias, smoot
     ce_sum = F.cross_entropy(s, labels, ignore_index=ignore_index, label_smoothing=smoothing, reduction="sum")
     logp = F.log_softmax(t / temperature, dim=-1)
     logq = F.log_softmax(s / temperature, dim=-1)
-    kl_rows = (logp.exp() * (logp - logq)).sum(-1)
+    p = logp.exp()
+    kl_rows = (p * torch.where(p > 0, logp - logq, torch.zeros_like(logp))).sum(-1)
     kl_sum = torch.where(valid, kl_rows, torch.zeros_like(kl_rows)).sum()
     ce = ce_sum / count
     kl = kl_sum / count

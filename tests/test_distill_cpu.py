@@ -82,6 +82,48 @@ def test_composite_takes_both_biases():
     torch.testing.assert_close(loss.double(), ref, rtol=1e-5, atol=0)
 
 
+@pytest.mark.parametrize("who", ["teacher", "both", "student"])
+@pytest.mark.parametrize("T", [1.0, 2.0, 0.7])
+def test_composite_obeys_the_inf_contract(who, T):
+    """-inf bias entries (banned tokens) on the teacher, on both models (a student made by ``make_student`` carries the
+    teacher's bias) and on the student alone, eps = 0: the composite's ce and kl equal the fp64 reference of
+    tests/loss_refs.py (kl finite where only p_v = 0 columns are banned, +inf where the student bans a column the
+    teacher gives mass), and the autograd gradient is finite and equals the reference's."""
+    import loss_refs as L
+    N, V, alpha = 7, 1003, 0.5
+    case = L.kd_case(N, V, torch.float32, hot_scale=L.INF_HOT_SCALE)
+    bs, bt, labels = L.kd_ban(case, case["bs"], case["bt"], L.kd_banned_columns(V), who, V)
+    labels = torch.where(L.valid_rows(labels, -100, V), labels, torch.full_like(labels, -100))
+    count = int((labels != -100).sum())
+    ce_r, kl_r, _, ds_r = L.kd_ref(case["s"], case["t"], labels, bs, bt, 0.0, -100, V, T, (1 - alpha) / count,
+                                   alpha / count)
+    assert bool(torch.isfinite(ce_r).all()) and bool(torch.isfinite(ds_r).all())
+    sg = case["s"].clone().requires_grad_(True)
+    loss, ce, kl = D.distill_loss(sg, case["t"], labels, bias=bs, teacher_bias=bt, label_smoothing=0.0, alpha=alpha,
+                                  temperature=T)
+    loss.backward()
+    torch.testing.assert_close(ce.double(), ce_r.sum() / count, rtol=1e-5, atol=0)
+    if who == "student":
+        assert kl.item() == float("inf") and loss.item() == float("inf")
+        assert bool(torch.isinf(kl_r[labels != -100]).all())
+    else:
+        assert bool(torch.isfinite(kl_r).all())
+        torch.testing.assert_close(kl.double(), kl_r.sum() / count, rtol=1e-5, atol=1e-7)
+        torch.testing.assert_close(loss.double(), (1 - alpha) * ce_r.sum() / count + alpha * T * T * kl_r.sum() / count,
+                                   rtol=1e-5, atol=1e-7)
+    assert bool(torch.isfinite(sg.grad).all())
+    rows = labels != -100
+    assert R.row_err(sg.grad[rows], ds_r[rows]) < R.ROW_BOUND[torch.float32]
+    assert not sg.grad[~rows].any()
+    # the definition is unchanged on finite inputs: the fp64 composite is the fp64 reference
+    s64 = case["s"].double()
+    _, ce64, kl64 = D.distill_loss(s64, case["t"].double(), labels, bias=case["bs"].double(),
+                                   teacher_bias=case["bt"].double(), label_smoothing=0.1, alpha=alpha, temperature=T)
+    ce_f, kl_f, _, _ = L.kd_ref(case["s"], case["t"], labels, case["bs"], case["bt"], 0.1, -100, V, T)
+    torch.testing.assert_close(ce64, ce_f.sum() / count, rtol=1e-12, atol=0)
+    torch.testing.assert_close(kl64, kl_f.sum() / count, rtol=1e-10, atol=0)
+
+
 def test_lm_head_distill_loss_composite_equals_full():
     """The no-materialised-logits entry on its composite path (CPU, fp32) against the loss on explicit logits: loss,
     components, dh and dW; the student and the teacher differ in width."""

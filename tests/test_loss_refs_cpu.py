@@ -7,7 +7,11 @@
 * the chunk-state merge {max, sum exp, sum x, x_label} over ``_chunks(V, vc)``, emulated in fp64, equals ``ce_ref``:
   the algorithm and the chunk table, apart from the kernel;
 * a property test of ``_chunks`` / ``_chunk_cols`` (pure Python) over every V in 1..2100 and three real vocabularies;
-* the exactness headroom of the embedding-backward operands.
+* the exactness headroom of the embedding-backward operands;
+* the distillation references: ``kd_ref`` against torch's losses and autograd in float64, its ``-inf`` contract against
+  hand-computed values at V = 3, ``kd_chunk_merge_ref`` equal to it on both hand-made chunk tables (the ``-inf``
+  patterns included), and the comp rule for ``kd_loss_abs_term`` / ``kd_abs_term`` on exactly the inputs of
+  tests/test_kd_kernels_gpu.py (``loss_refs.kd_case`` draws them on the CPU for both).
 """
 import pytest
 import torch
@@ -254,3 +258,178 @@ def test_chunk_tables_cover_every_column_once(monkeypatch):
                 assert chunks[-1][2] == 8 - V % 8 and all(s == 0 for _, _, s in chunks[:-1]), (V, vc, chunks)
             else:
                 assert all(s == 0 for _, _, s in chunks), (V, vc, chunks)
+
+
+# ------------------------------------------------------------------------------------------------- distillation (kd)
+NINF = float("-inf")
+
+
+@pytest.mark.parametrize("bias", ["none", "student", "both"])
+@pytest.mark.parametrize("eps", [0.0, 0.1])
+@pytest.mark.parametrize("T", L.KD_TEMPS)
+@pytest.mark.parametrize("N,V", [(1, 7), (5, 1001), (37, 1003), (12, 2056)])
+def test_kd_ref_matches_autograd_float64(N, V, T, eps, bias):
+    """``kd_ref`` against torch's own losses and autograd in fp64: ds is the gradient of w_ce sum ce + w_kl T^2 sum kl
+    over the valid rows."""
+    case = L.kd_case(N, V, F32)
+    bs, bt = L.kd_biases(case, bias)
+    labels = case["labels"]
+    ce, kl, stats, ds = L.kd_ref(case["s"], case["t"], labels, bs, bt, eps, L.IGNORE, V, T, L.W_CE, L.W_KL)
+    s64 = case["s"].double().requires_grad_(True)
+    sb = s64 + bs.double() if bs is not None else s64
+    tb = case["t"].double() + (bt.double() if bt is not None else 0.0)
+    valid = L.valid_rows(labels, L.IGNORE, V)
+    ce_t = F.cross_entropy(sb, _torch_labels(labels, V), reduction="none", label_smoothing=eps, ignore_index=L.IGNORE)
+    kl_t = F.kl_div(F.log_softmax(sb / T, -1), F.log_softmax(tb / T, -1), reduction="none", log_target=True).sum(-1)
+    kl_t = kl_t * valid
+    (L.W_CE * ce_t.sum() + L.W_KL * T * T * kl_t.sum()).backward()
+    assert _close(ce, ce_t.detach()) < TIGHT and _close(kl, kl_t.detach()) < TIGHT
+    assert _close(ds, s64.grad) < TIGHT
+    for j, x in enumerate((sb, sb / T, tb / T)):
+        assert _close(stats[:, j], torch.logsumexp(x.detach(), 1)) < TIGHT
+    assert not ce[~valid].any() and not kl[~valid].any() and not ds[~valid].any()
+    assert bool(torch.isfinite(stats).all()) and bool((kl >= -TIGHT).all())
+    assert ds.sum(1).abs().max().item() < TIGHT  # both parts of a row's gradient sum to 0
+
+
+def test_kd_ref_inf_contract_by_hand():
+    """V = 3, T = 2, label 0, eps = 0, values chosen so that every softmax is a ratio of small integers."""
+    ln = lambda v: torch.log(torch.tensor(float(v), dtype=F64)).item()  # noqa: E731
+    lab = torch.tensor([0])
+    t = torch.tensor([[2 * ln(3), 0.0, NINF]], dtype=F64)  # p = (3/4, 1/4, 0)
+    # both models ban column 2: q = (1/2, 1/2, 0)
+    s = torch.tensor([[0.0, 0.0, NINF]], dtype=F64)
+    ce, kl, stats, ds = L.kd_ref(s, t, lab, None, None, 0.0, L.IGNORE, 3, 2.0, 0.5, 0.25)
+    assert abs(kl.item() - (0.75 * ln(1.5) + 0.25 * ln(0.5))) < TIGHT
+    assert abs(ce.item() - ln(2)) < TIGHT
+    assert _close(stats, torch.tensor([[ln(2), ln(2), ln(4)]], dtype=F64)) < TIGHT
+    want = 0.5 * torch.tensor([[-0.5, 0.5, 0.0]], dtype=F64) \
+        + 0.25 * 2.0 * torch.tensor([[-0.25, 0.25, 0.0]], dtype=F64)
+    assert _close(ds, want) < TIGHT and ds[0, 2].item() == 0.0
+    # the teacher alone bans it: q = (1/4, 1/4, 1/2); the column adds nothing
+    s = torch.tensor([[0.0, 0.0, 2 * ln(2)]], dtype=F64)
+    ce, kl, stats, ds = L.kd_ref(s, t, lab, None, None, 0.0, L.IGNORE, 3, 2.0, 0.5, 0.25)
+    assert abs(kl.item() - 0.75 * ln(3)) < TIGHT
+    sm = torch.softmax(s, 1)
+    want = 0.5 * (sm - torch.tensor([[1.0, 0.0, 0.0]], dtype=F64)) \
+        + 0.25 * 2.0 * torch.tensor([[-0.5, 0.0, 0.5]], dtype=F64)
+    assert _close(ds, want) < TIGHT
+    # the same -inf delivered by the biases instead
+    b = torch.tensor([0.0, 0.0, NINF], dtype=F64)
+    out = L.kd_ref(s, torch.tensor([[2 * ln(3), 0.0, 5.0]], dtype=F64), lab, None, b, 0.0, L.IGNORE, 3, 2.0, 0.5, 0.25)
+    assert abs(out[1].item() - 0.75 * ln(3)) < TIGHT and _close(out[3], want) < TIGHT
+    # the student alone bans it, the teacher gives it mass: p = (3/5, 1/5, 1/5); kl = +inf, everything else finite
+    t = torch.tensor([[2 * ln(3), 0.0, 0.0]], dtype=F64)
+    s = torch.tensor([[0.0, 0.0, NINF]], dtype=F64)
+    ce, kl, stats, ds = L.kd_ref(s, t, lab, None, None, 0.0, L.IGNORE, 3, 2.0, 0.5, 0.25)
+    assert kl.item() == float("inf") and abs(ce.item() - ln(2)) < TIGHT
+    assert _close(stats, torch.tensor([[ln(2), ln(2), ln(5)]], dtype=F64)) < TIGHT
+    want = 0.5 * torch.tensor([[-0.5, 0.5, 0.0]], dtype=F64) \
+        + 0.25 * 2.0 * torch.tensor([[0.5 - 0.6, 0.5 - 0.2, -0.2]], dtype=F64)
+    assert _close(ds, want) < TIGHT
+    # an invalid row stays 0 with -inf present
+    ce, kl, stats, ds = L.kd_ref(s, t, torch.tensor([3]), None, None, 0.0, L.IGNORE, 3, 2.0)
+    assert ce.item() == 0.0 and kl.item() == 0.0 and not ds.any() and bool(torch.isfinite(stats).all())
+    # the chunk algorithm on the same rows: one column per chunk
+    for sv, tv, klv in ((torch.tensor([[0.0, 0.0, NINF]], dtype=F64), torch.tensor([[2 * ln(3), 0.0, NINF]], dtype=F64),
+                         0.75 * ln(1.5) + 0.25 * ln(0.5)), (s, t, float("inf"))):
+        ce2, kl2, stats2, _ = L.kd_chunk_merge_ref(sv, tv, lab, None, None, 0.0, L.IGNORE, 3, 2.0,
+                                                   [(0, 1, 0), (1, 1, 0), (2, 1, 0)])
+        assert kl2.item() == klv or abs(kl2.item() - klv) < TIGHT
+        assert abs(ce2.item() - ln(2)) < TIGHT and bool(torch.isfinite(stats2).all())
+
+
+@pytest.mark.parametrize("bias", ["none", "both"])
+@pytest.mark.parametrize("eps", [0.0, 0.1])
+@pytest.mark.parametrize("T", L.KD_TEMPS)
+@pytest.mark.parametrize("ti", [0, 1])
+def test_kd_chunk_merge_equals_kd_ref(ti, T, eps, bias):
+    V, chunks = [(1032, L.HAND_TABLE), (2056, L.WIDE_TABLE)][ti]
+    _assert_table(V, chunks, grid=4)
+    case = L.kd_case(9, V, BF16)
+    bs, bt = L.kd_biases(case, bias)
+    args = (case["s"], case["t"], case["labels"], bs, bt, eps, L.IGNORE, V, T)
+    ce_r, kl_r, stats_r, _ = L.kd_ref(*args)
+    ce, kl, stats, state = L.kd_chunk_merge_ref(*args, chunks)
+    assert _close(ce, ce_r) < TIGHT and _close(kl, kl_r) < 1e-10 and _close(stats, stats_r) < TIGHT
+    # the state after the last chunk is consistent with stats
+    assert _close(state[:, 0] + torch.log(state[:, 1]), stats_r[:, 0]) < TIGHT
+    assert _close(state[:, 0] / T + torch.log(state[:, 4]), stats_r[:, 1]) < TIGHT
+    assert _close(state[:, 5] / T + torch.log(state[:, 6]), stats_r[:, 2]) < TIGHT
+    if eps == 0.0:  # the -inf patterns: teacher only, both, student only
+        ban = L.kd_banned_columns(V, chunks)
+        for who in ("teacher", "both", "student"):
+            b_s, b_t, lab = L.kd_ban(case, bs, bt, ban, who, V)
+            args = (case["s"], case["t"], lab, b_s, b_t, 0.0, L.IGNORE, V, T)
+            ce_r, kl_r, stats_r, _ = L.kd_ref(*args)
+            ce, kl, stats, _ = L.kd_chunk_merge_ref(*args, chunks)
+            valid = L.valid_rows(lab, L.IGNORE, V)
+            assert bool(torch.isfinite(ce_r).all()) and bool(torch.isfinite(stats_r).all())
+            assert bool((kl_r[valid] == float("inf")).all()) == (who == "student")
+            assert _close(ce, ce_r) < TIGHT and _close(stats, stats_r) < TIGHT
+            assert torch.equal(torch.isinf(kl), torch.isinf(kl_r))
+            fin = torch.isfinite(kl_r)
+            assert _close(kl[fin], kl_r[fin]) < 1e-10
+
+
+def _kd_fp32(s, t, labels, bs, bt, eps, V, T, stats_r, w_ce, w_kl):
+    """The fp32 torch composite of the distillation loss per row (the expressions of ops/distill.py ``_reference``), a
+    plain fp32 evaluation of the cancelling form the kernels use, the three lse, and the gradient from the
+    fp32-rounded reference stats as the backward kernels get them."""
+    sb = s.float() + bs if bs is not None else s.float()
+    tb = t.float() + bt if bt is not None else t.float()
+    ce = F.cross_entropy(sb, _torch_labels(labels, V), reduction="none", label_smoothing=eps, ignore_index=L.IGNORE)
+    logp, logq = F.log_softmax(tb / T, -1), F.log_softmax(sb / T, -1)
+    p = logp.exp()
+    valid = L.valid_rows(labels, L.IGNORE, V)
+    kl = (p * torch.where(p > 0, logp - logq, torch.zeros_like(logp))).sum(-1) * valid
+    stats = torch.stack([torch.logsumexp(sb, 1), torch.logsumexp(sb / T, 1), torch.logsumexp(tb / T, 1)], 1)
+    klc = ((torch.softmax(tb / T, -1) * (tb - sb)).sum(-1) / T - stats[:, 2] + stats[:, 1]) * valid
+    st = stats_r.float()
+    hit = torch.zeros_like(sb).scatter_(1, labels.clamp(0, V - 1).view(-1, 1), 1.0 - eps)
+    f = lambda v: torch.tensor(v, dtype=F32)  # noqa: E731
+    d = f(w_ce) * (torch.exp(sb - st[:, 0:1]) - f(eps / V) - hit) \
+        + f(w_kl * T) * (torch.exp(sb / T - st[:, 1:2]) - torch.exp(tb / T - st[:, 2:3]))
+    return ce, kl, klc, stats, d * valid.view(-1, 1)
+
+
+def _kd_margin(case, V, dtype, T, eps, bias, steps):
+    bs, bt = L.kd_biases(case, bias)
+    s, t, labels = case["s"], case["t"], case["labels"]
+    ce_r, kl_r, stats_r, d_r = L.kd_ref(s, t, labels, bs, bt, eps, L.IGNORE, V, T, L.W_CE, L.W_KL)
+    ce_term, kl_term = L.kd_loss_abs_term(s, t, labels, bs, bt, eps, L.IGNORE, V, T, steps)
+    ce, kl, klc, stats, d = _kd_fp32(s, t, labels, bs, bt, eps, V, T, stats_r, L.W_CE, L.W_KL)
+    bound = L.grad_bound(d_r, L.kd_abs_term(s, t, labels, bs, bt, eps, L.IGNORE, V, T, L.W_CE, L.W_KL), F32)
+    figs = {"ce": L.abs_worst(ce, ce_r, ce_term), "kl composite": L.abs_worst(kl, kl_r, kl_term),
+            "kl cancelling form": L.abs_worst(klc, kl_r, kl_term),
+            "stats": L.row_metric(stats, stats_r) / L.LOSS_BOUND, "ds": L.grad_worst(d, d_r, bound)[0]}
+    for name, val in figs.items():
+        assert val <= QUARTER, (name, val, V, dtype, T, eps, bias)
+    return figs
+
+
+@pytest.mark.parametrize("bias", ["none", "student", "both"])
+@pytest.mark.parametrize("eps", [0.0, 0.1])
+@pytest.mark.parametrize("T", L.KD_TEMPS)
+@pytest.mark.parametrize("dt", ["bf16", "fp32"])
+@pytest.mark.parametrize("N,V", L.KD_SHAPES)
+def test_kd_composite_margin(N, V, dt, T, eps, bias):
+    """The comp rule on exactly the inputs of tests/test_kd_kernels_gpu.py::test_kd_fwd_bwd: the fp32 composite's ce and
+    kl per row, a plain fp32 evaluation of the cancelling form, the three lse and the gradient all sit at or under a
+    quarter of the bounds the GPU test applies."""
+    dtype = BF16 if dt == "bf16" else F32
+    figs = _kd_margin(L.kd_case(N, V, dtype), V, dtype, T, eps, bias, L.kd_steps(V, dtype))
+    print(f"[fig] kd margin N={N} V={V} {dt} T={T} eps={eps} bias={bias}: " +
+          ", ".join(f"{k} x{v:.3g}" for k, v in figs.items()))
+
+
+@pytest.mark.parametrize("T", L.KD_TEMPS)
+@pytest.mark.parametrize("ti", [0, 1])
+def test_kd_composite_margin_chunk_tables(ti, T):
+    """The same on the inputs of the direct chunk-kernel test (bf16, both tables, with the tables' step count)."""
+    V, chunks = [(1032, L.HAND_TABLE), (2056, L.WIDE_TABLE)][ti]
+    for N in L.KD_CHUNK_ROWS:
+        case = L.kd_case(N, V, BF16, labels=lambda n, v, g: L.kd_chunk_labels(n, v, chunks, g))
+        for eps in (0.0, 0.1):
+            for bias in ("none", "both"):
+                _kd_margin(case, V, BF16, T, eps, bias, L.kd_steps(V, BF16, chunks))
