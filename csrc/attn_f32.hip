@@ -14,6 +14,10 @@
 // Block lists (AttnParamsT::kl_ptr / kl_idx / ql_ptr / ql_idx): as in csrc/attn_hd.hip, forward and dQ follow the query
 // block's list of key blocks and dK / dV the key block's list of query blocks, repeats included (list_range), in
 // instantiations of their own (template parameter LISTS): the kernels of every other call are the code they were.
+// Soft cap (AttnParamsT::softcap > 0): as in csrc/attn_hd.hip the score is c tanh(scale s / c) before every mask, and
+// dQ and dK / dV scale dS by 1 - tanh^2, in instantiations of their own (template parameter CAP).  tanh is the device
+// library's tanhf: the exp2 form of the bf16 family cancels near 0 (absolute error ~6e-8, times c = 50 a 3e-6 error
+// on the score), tanhf is relatively accurate there.
 //
 // Layout trick (no transposes through LDS for P or dS): the 16x16x4 f32 MFMA's C/D map puts rows 4g .. 4g+3
 // (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction index k = g from
@@ -85,7 +89,7 @@ DLLM_DEVICE f32x4 rd_col4(const float* tr, int col, int r4) {
 // the segment hooks (3, 2, 2): with it the unsegmented fp32 step measures as before, at fewer registers
 // (profiles/packing_regression_gate.txt; without it 0.7 % slower).
 // ================================================================================================ forward
-template <bool DROP, bool LISTS = false>
+template <bool DROP, bool LISTS = false, bool CAP = false>
 __global__ __launch_bounds__(NT, 3) void attn_f32_fwd_kernel(AttnF32Params P) {
   __shared__ __attribute__((aligned(16))) float Ks[BKY * D];
   __shared__ __attribute__((aligned(16))) float Vt[D * BKY];
@@ -112,6 +116,7 @@ __global__ __launch_bounds__(NT, 3) void attn_f32_fwd_kernel(AttnF32Params P) {
   }
   const uint32_t rh = DROP ? mix32(eff_seed(P.seed), (uint32_t)((long)bh * P.Sq + rowc)) : 0u;
   const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
+  const float capinv = CAP ? 1.f / P.softcap : 0.f;
   float m = -INFINITY, l = 0.f;
   f32x4 acc[4];
 #pragma unroll
@@ -153,6 +158,7 @@ __global__ __launch_bounds__(NT, 3) void attn_f32_fwd_kernel(AttnF32Params P) {
       for (int i = 0; i < 4; ++i) {
         const int key = k0 + 16 * t + 4 * g + i;
         float x = st[t][i] * P.scale;
+        if constexpr (CAP) x = P.softcap * tanhf(x * capinv);
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
         if (hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key, vis, t, i))
           x = -INFINITY;
@@ -239,7 +245,7 @@ __global__ __launch_bounds__(NT) void attn_f32_delta_kernel(AttnF32Params P) {
   if (r < rows && j == 0) P.delta[r] = s;
 }
 
-template <bool DROP, bool LISTS = false>
+template <bool DROP, bool LISTS = false, bool CAP = false>
 __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
   __shared__ __attribute__((aligned(16))) float Ks[BKY * D];
   __shared__ __attribute__((aligned(16))) float Kt[D * BKY];
@@ -271,6 +277,7 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
   const float dlt = row_ok ? P.delta[(long)bh * P.Sq + row] : 0.f;
   const uint32_t rh = DROP ? mix32(eff_seed(P.seed), (uint32_t)((long)bh * P.Sq + rowc)) : 0u;
   const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
+  const float capinv = CAP ? 1.f / P.softcap : 0.f;
   const bool want_dlut = P.dlut != nullptr && P.lut != nullptr;
   // the row's dQ address, formed here as in csrc/attn_hd.hip: two vector registers through the walk instead of the
   // eight scalar ones of the base and strides, which the walk's own scalars would otherwise push out to spills
@@ -320,13 +327,18 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
       for (int i = 0; i < 4; ++i) {
         const int key = k0 + 16 * t + 4 * g + i;
         const int di = key - row - (k0 - q0 - 63);
-        float x = st[t][i] * P.scale;
+        float x = st[t][i] * P.scale, dtanh = 1.f;  // dtanh = 1 - tanh^2, the cap's derivative
+        if constexpr (CAP) {
+          const float th = tanhf(x * capinv);
+          x = P.softcap * th;
+          dtanh = 1.f - th * th;
+        }
         if (P.lut) x += Ls[di];
         const bool msk =
             hidden(vis, t, i) || (P.causal && key > row + P.causal_off) || off_band(P, row, key, vis, t, i);
         const float pr = msk ? 0.f : __expf(x - lse);
         const float dpk = DROP ? (((kb4 >> i) & 1u) ? dpt[t][i] * dscale : 0.f) : dpt[t][i];
-        const float ds = pr * (dpk - dlt);
+        const float ds = CAP ? pr * (dpk - dlt) * dtanh : pr * (dpk - dlt);
         st[t][i] = ds;
         if (want_dlut) Ds[(16 * w + c) * (BKY + 1) + 16 * t + 4 * g + i] = ds;  // 0 for rows >= Sq (lse = inf)
       }
@@ -370,7 +382,7 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dq_kernel(AttnF32Params P) {
   }
 }
 
-template <bool DROP, bool LISTS = false>
+template <bool DROP, bool LISTS = false, bool CAP = false>
 __global__ __launch_bounds__(NT, 2) void attn_f32_dkdv_kernel(AttnF32Params P) {
   __shared__ __attribute__((aligned(16))) float Qs[BQ * D];
   __shared__ __attribute__((aligned(16))) float Qt[D * BQ];
@@ -398,6 +410,7 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dkdv_kernel(AttnF32Params P) {
     }
   }
   const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
+  const float capinv = CAP ? 1.f / P.softcap : 0.f;
   const uint32_t seed = DROP ? eff_seed(P.seed) : 0u;
   const bool kok = key_ok(P, b, key);
   const int ksg = P.q_seg ? seg_at(P.k_seg, b, P.Sk, key) : 0;
@@ -449,10 +462,15 @@ __global__ __launch_bounds__(NT, 2) void attn_f32_dkdv_kernel(AttnF32Params P) {
 
 extern "C" int dllm_attn_f32_fwd(AttnF32Params* pp, hipStream_t st) {
   const AttnF32Params& P = *pp;
+  // the binding checks it first: no cap with a bias LUT, segments, global keys or lists
+  if (P.softcap > 0.f && (P.kl_ptr != nullptr || P.lut != nullptr || P.q_seg != nullptr || P.k_glob != nullptr)) return -2;
   dim3 grid((P.Sq + BQ - 1) / BQ, P.B * P.H);
   if (P.kl_ptr != nullptr) {  // the instantiations that follow block lists
     if (P.p_drop > 0.f) hipLaunchKernelGGL((attn_f32_fwd_kernel<true, true>), grid, dim3(NT), 0, st, P);
     else hipLaunchKernelGGL((attn_f32_fwd_kernel<false, true>), grid, dim3(NT), 0, st, P);
+  } else if (P.softcap > 0.f) {  // the instantiations that cap the scores
+    if (P.p_drop > 0.f) hipLaunchKernelGGL((attn_f32_fwd_kernel<true, false, true>), grid, dim3(NT), 0, st, P);
+    else hipLaunchKernelGGL((attn_f32_fwd_kernel<false, false, true>), grid, dim3(NT), 0, st, P);
   } else if (P.p_drop > 0.f) hipLaunchKernelGGL(attn_f32_fwd_kernel<true>, grid, dim3(NT), 0, st, P);
   else hipLaunchKernelGGL(attn_f32_fwd_kernel<false>, grid, dim3(NT), 0, st, P);
   DLLM_CHECK_LAUNCH();
@@ -461,6 +479,7 @@ extern "C" int dllm_attn_f32_fwd(AttnF32Params* pp, hipStream_t st) {
 
 extern "C" int dllm_attn_f32_bwd(AttnF32Params* pp, hipStream_t st) {
   const AttnF32Params& P = *pp;
+  if (P.softcap > 0.f && (P.kl_ptr != nullptr || P.lut != nullptr || P.q_seg != nullptr || P.k_glob != nullptr)) return -2;
   const long rows = (long)P.B * P.H * P.Sq;
   hipLaunchKernelGGL(attn_f32_delta_kernel, dim3((unsigned)((rows + NT / 16 - 1) / (NT / 16))), dim3(NT), 0, st, P);
   DLLM_CHECK_LAUNCH();
@@ -472,6 +491,14 @@ extern "C" int dllm_attn_f32_bwd(AttnF32Params* pp, hipStream_t st) {
     } else {
       hipLaunchKernelGGL((attn_f32_dq_kernel<false, true>), gq, dim3(NT), 0, st, P);
       hipLaunchKernelGGL((attn_f32_dkdv_kernel<false, true>), gk, dim3(NT), 0, st, P);
+    }
+  } else if (P.softcap > 0.f) {  // the instantiations that cap the scores
+    if (P.p_drop > 0.f) {
+      hipLaunchKernelGGL((attn_f32_dq_kernel<true, false, true>), gq, dim3(NT), 0, st, P);
+      hipLaunchKernelGGL((attn_f32_dkdv_kernel<true, false, true>), gk, dim3(NT), 0, st, P);
+    } else {
+      hipLaunchKernelGGL((attn_f32_dq_kernel<false, false, true>), gq, dim3(NT), 0, st, P);
+      hipLaunchKernelGGL((attn_f32_dkdv_kernel<false, false, true>), gk, dim3(NT), 0, st, P);
     }
   } else if (P.p_drop > 0.f) {
     hipLaunchKernelGGL(attn_f32_dq_kernel<true>, gq, dim3(NT), 0, st, P);

@@ -37,7 +37,12 @@
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int rl = 16 * t + 4 * g + i, row = q0 + rl;
-        float x = sc[t][i] * P.scale;
+        float x = sc[t][i] * P.scale, dtanh = 1.f;  // dtanh = 1 - tanh^2, the cap's derivative
+        if constexpr (CAP) {
+          const float th = tanhf(x * capinv);
+          x = P.softcap * th;
+          dtanh = 1.f - th * th;
+        }
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
         const bool msk = hidden(vis, t, i) || (P.causal && key > row + P.causal_off) ||
                          (P.window >= 0 && off_band_w(kwin, row, key));
@@ -45,7 +50,7 @@
         const bool kp = DROP ? keep_key(Rh[rl], key, P.thr) : true;
         const float dpk = kp ? dp[t][i] * dscale : 0.f;
         pd[t][i] = kp ? pr * dscale : 0.f;
-        sc[t][i] = pr * (dpk - Rd[rl]);
+        sc[t][i] = CAP ? pr * (dpk - Rd[rl]) * dtanh : pr * (dpk - Rd[rl]);
       }
     }
 #pragma unroll

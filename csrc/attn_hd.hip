@@ -7,8 +7,8 @@
 // (its output row is 0) — parallel/context.py _merge combines blocks by it.
 //
 // The real head dim D (D % 8 == 0, 32 <= D <= DP) is a runtime field: columns D .. DP-1 are staged as zeros and never
-// stored.  bias / kpm / causal / window are runtime flags; only DP, DROP and LISTS are template parameters (24 kernel
-// instantiations, and 18 that follow block lists).
+// stored.  bias / kpm / causal / window are runtime flags; only DP, DROP, LISTS and CAP are template parameters (24
+// kernel instantiations, 18 that follow block lists and 18 that cap the scores).
 //
 // Sliding window (AttnParamsT::window >= 0, LongT5-local; Sq == Sk, not causal): forward and dQ walk only the key
 // blocks that intersect [q0 - w, q0 + 63 + w], dK / dV only the query blocks that intersect [k0 - w, k0 + 63 + w]
@@ -36,6 +36,14 @@
 // every other call it cost scalar spills (dQ) or occupancy, so those are the code they were
 // (profiles/attn_block_lists.txt).  No causal, window, segments or global keys with lists, and none at head dim 32
 // (the launchers refuse, the op takes the composite).
+//
+// Soft cap (AttnParamsT::softcap > 0, Gemma 2 / T5Gemma): the score is c tanh(scale s / c), formed before the log2(e)
+// factor and every mask; dQ and dK / dV recompute the tanh and scale dS by 1 - tanh^2.  Like the lists it lives in
+// instantiations of its own (template parameter CAP, head dims other than 32, never with LISTS): the per-score VALU
+// work (an exp2, a reciprocal and three multiply-adds) and its registers stay out of the kernels of every other call,
+// which are the code they were (profiles/attn_softcap.txt).  Capped calls at head dim 64 run here too: csrc/attn.hip
+// has no cap.  No bias LUT, segments, global keys or lists with a cap, and none at head dim 32 (the launchers refuse,
+// the op takes the composite).
 //
 // Layout trick of csrc/attn_f32.hip, carried over to the 16x16x32 bf16 MFMA: its C/D map puts rows 4g .. 4g+3
 // (g = lane >> 4) of column (lane & 15) in a lane's 4 registers, and its A/B maps take reduction indices k = 8g + j
@@ -69,6 +77,10 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 DLLM_DEVICE f32x4 mma(bf16x8v a, bf16x8v b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 DLLM_DEVICE float ex2(float x) { return __builtin_amdgcn_exp2f(x); }  // v_exp_f32: exp2(-inf) = 0
+
+// tanh(z) from z2 = 2 log2(e) z: 1 - 2 / (1 + exp2(z2)).  Saturates exactly: exp2 = inf gives 1, exp2 = 0 gives -1.
+// Its absolute error (a few 1e-8 from the cancellation near 0) is far below bf16's.
+DLLM_DEVICE float tanh_ex2(float z2) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + ex2(z2)); }
 
 // LDS image of a 64-row tile: [64][DP + 8] bf16, row-major.  The 16-B pad per row spreads the 16 rows of one
 // ds_read_b128 fragment read over all banks (row stride = DP / 2 + 4 dwords: 4 r mod 64 distinct for r < 16).
@@ -151,7 +163,7 @@ constexpr int occ_dq(int DP, bool DROP) {
 constexpr int occ_dkdv(int DP) { return DP == 32 ? 3 : DP == 64 ? 3 : 2; }
 
 // ================================================================================================ forward
-template <int DP, bool DROP, bool LISTS = false>
+template <int DP, bool DROP, bool LISTS = false, bool CAP = false>
 __global__ __launch_bounds__(NT, occ_fwd(DP, DROP)) void attn_hd_fwd_kernel(AttnHdParams P) {
   constexpr int KS = DP / 32, DT = DP / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[Img<DP>::SIZE];
@@ -170,6 +182,9 @@ __global__ __launch_bounds__(NT, occ_fwd(DP, DROP)) void attn_hd_fwd_kernel(Attn
   const uint32_t rh = DROP ? mix32(eff_seed(P.seed), (uint32_t)((long)bh * P.Sq + rowc)) : 0u;
   const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
   const float scale2 = P.scale * LOG2E;
+  // soft cap: x = c log2(e) tanh(scale s / c), tanh from exp2(2 log2(e) z) (tanh_ex2)
+  const float capz2 = CAP ? P.scale / P.softcap * (2.f * LOG2E) : 0.f;
+  const float capc2 = CAP ? P.softcap * LOG2E : 0.f;
   float m = -INFINITY, l = 0.f;
   f32x4 acc[DT];
 #pragma unroll
@@ -246,7 +261,7 @@ __global__ __launch_bounds__(NT) void attn_hd_delta_kernel(AttnHdParams P) {
   if (r < rows && j == 0) P.delta[r] = s;
 }
 
-template <int DP, bool DROP, bool LISTS = false>
+template <int DP, bool DROP, bool LISTS = false, bool CAP = false>
 __global__ __launch_bounds__(NT, occ_dq(DP, DROP)) void attn_hd_dq_kernel(AttnHdParams P) {
   constexpr int KS = DP / 32, DT = DP / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Ks[Img<DP>::SIZE];
@@ -270,6 +285,9 @@ __global__ __launch_bounds__(NT, occ_dq(DP, DROP)) void attn_hd_dq_kernel(AttnHd
   const uint32_t rh = DROP ? mix32(eff_seed(P.seed), (uint32_t)((long)bh * P.Sq + rowc)) : 0u;
   const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
   const float scale2 = P.scale * LOG2E;
+  // soft cap: x = c log2(e) tanh(scale s / c), tanh from exp2(2 log2(e) z) (tanh_ex2)
+  const float capz2 = CAP ? P.scale / P.softcap * (2.f * LOG2E) : 0.f;
+  const float capc2 = CAP ? P.softcap * LOG2E : 0.f;
   const bool want_dlut = P.dlut != nullptr && P.lut != nullptr;
   // the row's dQ address, formed here: two vector registers through the walk instead of the eight scalar ones of the
   // base and strides, which the walk's own scalars would otherwise push out to spills
@@ -324,7 +342,7 @@ __global__ __launch_bounds__(NT, occ_dq(DP, DROP)) void attn_hd_dq_kernel(AttnHd
   }
 }
 
-template <int DP, bool DROP, bool LISTS = false>
+template <int DP, bool DROP, bool LISTS = false, bool CAP = false>
 __global__ __launch_bounds__(NT, occ_dkdv(DP)) void attn_hd_dkdv_kernel(AttnHdParams P) {
   constexpr int KS = DP / 32, DT = DP / 16;
   __shared__ __attribute__((aligned(16))) uint16_t Qs[Img<DP>::SIZE];
@@ -343,6 +361,9 @@ __global__ __launch_bounds__(NT, occ_dkdv(DP)) void attn_hd_dkdv_kernel(AttnHdPa
   load_row_frags<DP>(P.v + (long)b * P.v_sb + (long)keyc * P.v_ss + (long)h * P.v_sh, g, P.D, vf);
   const float dscale = DROP ? 1.f / (1.f - P.p_drop) : 1.f;
   const float scale2 = P.scale * LOG2E;
+  // soft cap: x = c log2(e) tanh(scale s / c), tanh from exp2(2 log2(e) z) (tanh_ex2)
+  const float capz2 = CAP ? P.scale / P.softcap * (2.f * LOG2E) : 0.f;
+  const float capc2 = CAP ? P.softcap * LOG2E : 0.f;
   const uint32_t seed = DROP ? eff_seed(P.seed) : 0u;
   const bool kok = key_ok(P, b, key);
   const int ksg = P.q_seg ? seg_at(P.k_seg, b, P.Sk, key) : 0;
@@ -401,6 +422,14 @@ int launch_fwd(const AttnHdParams& P, hipStream_t st) {
       return 0;
     }
   }
+  if constexpr (DP != 32) {  // the instantiations that cap the scores (none at head dim 32, never with lists)
+    if (P.softcap > 0.f) {
+      if (P.p_drop > 0.f) hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, true, false, true>), grid, dim3(NT), 0, st, P);
+      else hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, false, false, true>), grid, dim3(NT), 0, st, P);
+      DLLM_CHECK_LAUNCH();
+      return 0;
+    }
+  }
   if (P.p_drop > 0.f) hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, true>), grid, dim3(NT), 0, st, P);
   else hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, false>), grid, dim3(NT), 0, st, P);
   DLLM_CHECK_LAUNCH();
@@ -423,6 +452,19 @@ int launch_bwd(const AttnHdParams& P, hipStream_t st) {
       return 0;
     }
   }
+  if constexpr (DP != 32) {  // the instantiations that cap the scores, as in launch_fwd
+    if (P.softcap > 0.f) {
+      if (P.p_drop > 0.f) {
+        hipLaunchKernelGGL((attn_hd_dq_kernel<DP, true, false, true>), gq, dim3(NT), 0, st, P);
+        hipLaunchKernelGGL((attn_hd_dkdv_kernel<DP, true, false, true>), gk, dim3(NT), 0, st, P);
+      } else {
+        hipLaunchKernelGGL((attn_hd_dq_kernel<DP, false, false, true>), gq, dim3(NT), 0, st, P);
+        hipLaunchKernelGGL((attn_hd_dkdv_kernel<DP, false, false, true>), gk, dim3(NT), 0, st, P);
+      }
+      DLLM_CHECK_LAUNCH();
+      return 0;
+    }
+  }
   if (P.p_drop > 0.f) {
     hipLaunchKernelGGL((attn_hd_dq_kernel<DP, true>), gq, dim3(NT), 0, st, P);
     hipLaunchKernelGGL((attn_hd_dkdv_kernel<DP, true>), gk, dim3(NT), 0, st, P);
@@ -440,7 +482,8 @@ int launch_bwd(const AttnHdParams& P, hipStream_t st) {
 extern "C" int dllm_attn_hd_fwd(AttnHdParams* pp, hipStream_t st) {
   const AttnHdParams& P = *pp;
   if (P.D < 32 || P.D > 128 || P.D % 8) return -1;
-  if (P.D == 32 && (P.k_glob != nullptr || P.kl_ptr != nullptr)) return -2;  // the binding checks it first
+  if (P.D == 32 && (P.k_glob != nullptr || P.kl_ptr != nullptr || P.softcap > 0.f)) return -2;  // the binding checks it
+  if (P.softcap > 0.f && (P.kl_ptr != nullptr || P.lut != nullptr || P.q_seg != nullptr || P.k_glob != nullptr)) return -2;
   switch ((P.D + 31) / 32) {
     case 1: return launch_fwd<32>(P, st);
     case 2: return launch_fwd<64>(P, st);
@@ -452,7 +495,8 @@ extern "C" int dllm_attn_hd_fwd(AttnHdParams* pp, hipStream_t st) {
 extern "C" int dllm_attn_hd_bwd(AttnHdParams* pp, hipStream_t st) {
   const AttnHdParams& P = *pp;
   if (P.D < 32 || P.D > 128 || P.D % 8) return -1;
-  if (P.D == 32 && (P.k_glob != nullptr || P.kl_ptr != nullptr)) return -2;
+  if (P.D == 32 && (P.k_glob != nullptr || P.kl_ptr != nullptr || P.softcap > 0.f)) return -2;
+  if (P.softcap > 0.f && (P.kl_ptr != nullptr || P.lut != nullptr || P.q_seg != nullptr || P.k_glob != nullptr)) return -2;
   const long rows = (long)P.B * P.H * P.Sq;
   hipLaunchKernelGGL(attn_hd_delta_kernel, dim3((unsigned)((rows + NT / 16 - 1) / (NT / 16))), dim3(NT), 0, st, P);
   DLLM_CHECK_LAUNCH();

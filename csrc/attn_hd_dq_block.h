@@ -30,14 +30,21 @@
       for (int i = 0; i < 4; ++i) {
         const int key = k0 + 16 * t + 4 * g + i;
         const int di = key - row - (k0 - q0 - 63);
-        float x = st[t][i] * scale2;
+        float x, dtanh = 1.f;  // dtanh = 1 - tanh^2, the cap's derivative
+        if constexpr (CAP) {
+          const float th = tanh_ex2(st[t][i] * capz2);
+          x = capc2 * th;
+          dtanh = 1.f - th * th;
+        } else {
+          x = st[t][i] * scale2;
+        }
         if (P.lut) x += Ls[di];
         const bool msk =
             hidden(vis, t, i) || (P.causal && key > row + P.causal_off) ||
             (DP != 32 ? off_band(P, row, key, vis, t, i) : off_band(P, row, key));
         const float pr = msk ? 0.f : ex2(x - lse);
         const float dpk = DROP ? (((kb4 >> i) & 1u) ? dpt[t][i] * dscale : 0.f) : dpt[t][i];
-        const float ds = pr * (dpk - dlt);
+        const float ds = CAP ? pr * (dpk - dlt) * dtanh : pr * (dpk - dlt);
         st[t][i] = ds;
         if (want_dlut) Ds[(16 * w + c) * (BKY + 1) + 16 * t + 4 * g + i] = ds;  // 0 for rows >= Sq (lse = inf)
       }

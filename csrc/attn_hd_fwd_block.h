@@ -27,7 +27,9 @@
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int key = k0 + 16 * t + 4 * g + i;
-        float x = st[t][i] * scale2;
+        float x;
+        if constexpr (CAP) x = capc2 * tanh_ex2(st[t][i] * capz2);  // c tanh(scale s / c), in log2 units
+        else x = st[t][i] * scale2;
         if (P.lut) x += Ls[key - row - (k0 - q0 - 63)];
         if (hidden(vis, t, i) || (P.causal && key > row + P.causal_off) ||
             (DP != 32 ? off_band(P, row, key, vis, t, i) : off_band(P, row, key)))

@@ -51,6 +51,14 @@
 // and its gradient, and dropout (the keep hash indexes (b, h, row, key), so the copies of a repeated key are kept or
 // dropped together), not with causal, a window, segments or global keys (the binding rejects each); csrc/attn.hip has
 // none, and csrc/attn_hd.hip none at head dim 32 (the binding rejects it).
+// Soft cap (Gemma 2 / T5Gemma attn_logit_softcapping): with softcap = c > 0 the score of (i, j) is c * tanh(scale *
+// q_i.k_j / c), formed before every mask (and, in the bf16 family, before the log2(e) factor); backward recomputes t =
+// tanh(.) and scales dS by 1 - t^2: dS_raw = P o (dP_kept - delta) o (1 - t^2).  It lives in kernel instantiations of
+// its own (template parameter CAP), so a call without a cap runs the code it ran before.  The cap composes with kpm,
+// causal (Sq != Sk included), a window and dropout, not with the bias LUT, segments, global keys or block lists (the
+// binding rejects each); csrc/attn.hip has none, and csrc/attn_hd.hip none at head dim 32 (the binding rejects it).
+// The bf16 family forms tanh as 1 - 2 / (1 + exp2(2 log2(e) z)), which saturates to +-1 at +-inf; the fp32 family
+// uses the device library's tanhf, relatively accurate near 0 where that form cancels.
 // Bias: lut[h][(j - i) + Sq - 1] is added to the scaled score.
 // LSE: [B, H, Sq] fp32, forward writes and backward reads; +inf marks a row without a visible key (its output row is
 // 0).  The bf16 families store it in log2 units (scores are scaled by log2(e), softmax by exp2), fp32 in natural-log
@@ -112,6 +120,8 @@ struct AttnParamsT {
   const int* ql_idx;   // [nnz] 64-query block indices, dK / dV: the transpose of kl, multiplicities kept
   int Hl;          // heads of the block lists: H, or 1 (shared by all heads); 0 without lists
   int l_nnz;       // length of kl_idx and of ql_idx
+  // soft cap, after the block lists for the same reason
+  float softcap;   // 0: none; c > 0: the score is c * tanh(scale * q.k / c) (csrc/attn_hd.hip, csrc/attn_f32.hip only)
 };
 
 using AttnF32Params = AttnParamsT<float>;

@@ -1,6 +1,8 @@
 // Attention (csrc/attn.hip, csrc/attn_f32.hip, csrc/attn_hd.hip).
 #include "bind_common.h"
 
+#include <cmath>
+
 namespace dllm {
 namespace {
 
@@ -219,6 +221,21 @@ void set_lists(P& p, const Tensor& q, const optional<Tensor>& kl_ptr, const opti
   p.ql_idx = p.l_nnz ? flat_ptr<const int>(*ql_idx, q, at::kInt, at_least(0), "ql_idx") : p.ql_ptr;
 }
 
+// the soft cap of csrc/attn_params.h: with nothing but kpm, causal, a window and dropout
+template <class P>
+void set_softcap(P& p, double softcap) {
+  p.softcap = 0.f;
+  if (softcap == 0.0) return;
+  TORCH_CHECK(softcap > 0.0 && std::isfinite(softcap), "attention: softcap must be finite and >= 0, got ", softcap);
+  TORCH_CHECK(p.lut == nullptr, "attention: a soft cap with a bias LUT is unsupported");
+  TORCH_CHECK(p.q_seg == nullptr, "attention: a soft cap with segments is unsupported");
+  TORCH_CHECK(p.k_glob == nullptr, "attention: a soft cap with global keys is unsupported");
+  TORCH_CHECK(p.kl_ptr == nullptr, "attention: a soft cap with block lists is unsupported");
+  TORCH_CHECK(!(std::is_same<P, AttnHdParams>::value && p.D == 32),
+              "attn_hd: a soft cap at head dim 32 is not served (csrc/attn_hd.hip)");
+  p.softcap = (float)softcap;
+}
+
 template <class P>
 std::vector<Tensor> attn_small_fwd(const AttnFamily<P>& f, int64_t D, const Tensor& q, const Tensor& k,
                                    const Tensor& v, const optional<Tensor>& kpm, const optional<Tensor>& lut,
@@ -227,13 +244,14 @@ std::vector<Tensor> attn_small_fwd(const AttnFamily<P>& f, int64_t D, const Tens
                                    const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
                                    const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
                                    const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
-                                   const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
+                                   const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx, double softcap) {
   P prm{};
   fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
   set_window(prm, window);
   set_segments(prm, q, q_seg, k_seg, q_blk, k_blk);
   set_global(prm, q, k_glob, k_gblk);
   set_lists(prm, q, kl_ptr, kl_idx, ql_ptr, ql_idx);
+  set_softcap(prm, softcap);
   check_limits_small(prm);
   auto out = fill_fwd(prm, q);
   check_rc(f.fwd(&prm, stream()), f.fwd_name);
@@ -250,13 +268,14 @@ std::vector<Tensor> attn_small_bwd(const AttnFamily<P>& f, int64_t D, const Tens
                                    const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
                                    const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
                                    const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
-                                   const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
+                                   const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx, double softcap) {
   P prm{};
   fill_common(prm, f, D, q, k, v, kpm, lut, scale, causal, p, seed);
   set_window(prm, window);
   set_segments(prm, q, q_seg, k_seg, q_blk, k_blk);
   set_global(prm, q, k_glob, k_gblk);
   set_lists(prm, q, kl_ptr, kl_idx, ql_ptr, ql_idx);
+  set_softcap(prm, softcap);
   check_limits_small(prm);
   auto r = fill_bwd(prm, f, q, o, dout, lse, dq_out, dk_out, dv_out, need_dlut);
   check_rc(f.bwd(&prm, stream()), f.bwd_name);
@@ -270,10 +289,10 @@ std::vector<Tensor> attn_f32_fwd(const Tensor& q, const Tensor& k, const Tensor&
                                  const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
                                  const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
                                  const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
-                                 const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
+                                 const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx, double softcap) {
   return attn_small_fwd(kAttnF32, 64, q, k, v, kpm, lut, scale, causal, p, seed, window, q_seg, k_seg, q_blk,
                         k_blk, k_glob, k_gblk, kl_ptr, kl_idx,
-                        ql_ptr, ql_idx);
+                        ql_ptr, ql_idx, softcap);
 }
 
 std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
@@ -285,10 +304,10 @@ std::vector<Tensor> attn_f32_bwd(const Tensor& dout, const Tensor& q, const Tens
                                  const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
                                  const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
                                  const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
-                                 const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
+                                 const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx, double softcap) {
   return attn_small_bwd(kAttnF32, 64, dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed, need_dlut, dq_out,
                         dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk, k_glob, k_gblk, kl_ptr, kl_idx,
-                        ql_ptr, ql_idx);
+                        ql_ptr, ql_idx, softcap);
 }
 
 // the head dim of an attn_hd call: what csrc/attn_hd.hip is instantiated for (padded to 32, 16-B rows)
@@ -306,10 +325,10 @@ std::vector<Tensor> attn_hd_fwd(const Tensor& q, const Tensor& k, const Tensor& 
                                 const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
                                 const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
                                 const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
-                                const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
+                                const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx, double softcap) {
   return attn_small_fwd(kAttnHd, attn_hd_dim(q, k), q, k, v, kpm, lut, scale, causal, p, seed, window, q_seg, k_seg,
                         q_blk, k_blk, k_glob, k_gblk, kl_ptr, kl_idx,
-                        ql_ptr, ql_idx);
+                        ql_ptr, ql_idx, softcap);
 }
 
 std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
@@ -321,10 +340,10 @@ std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tenso
                                 const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
                                 const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
                                 const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
-                                const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx) {
+                                const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx, double softcap) {
   return attn_small_bwd(kAttnHd, attn_hd_dim(q, k), dout, q, k, v, o, lse, kpm, lut, scale, causal, p, seed,
                         need_dlut, dq_out, dk_out, dv_out, window, q_seg, k_seg, q_blk, k_blk, k_glob, k_gblk, kl_ptr, kl_idx,
-                        ql_ptr, ql_idx);
+                        ql_ptr, ql_idx, softcap);
 }
 
 // ---- csrc/attn.hip: the same helpers, plus its extras (dropout bit planes, saturated-bias ranges, rowrec, column sums)
@@ -439,26 +458,30 @@ void bind_attn(pybind11::module& m) {
         py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1,
         py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
         py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
-        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none());
+        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none(),
+        py::arg("softcap") = 0.0);
   m.def("attn_f32_bwd", &attn_f32_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
         py::arg("dv_out") = py::none(), py::arg("window") = -1, py::arg("q_seg") = py::none(),
         py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
         py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
-        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none());
+        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none(),
+        py::arg("softcap") = 0.0);
   m.def("attn_hd_fwd", &attn_hd_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
         py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1,
         py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
         py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
-        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none());
+        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none(),
+        py::arg("softcap") = 0.0);
   m.def("attn_hd_bwd", &attn_hd_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
         py::arg("dv_out") = py::none(), py::arg("window") = -1, py::arg("q_seg") = py::none(),
         py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
         py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
-        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none());
+        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none(),
+        py::arg("softcap") = 0.0);
 }
 
 }  // namespace dllm

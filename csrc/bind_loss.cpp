@@ -2,6 +2,8 @@
 // (csrc/pref.hip), whole-vocabulary and vocabulary-chunked forms.
 #include "bind_common.h"
 
+#include <cmath>
+
 namespace dllm {
 namespace {
 
@@ -22,8 +24,10 @@ void* ce_logits(const Tensor& logits) {
   return p;
 }
 
+// softcap (all four): c > 0 caps the logits to c tanh(x / c) inside the kernels' pass; 0: none
 std::vector<Tensor> ce_fwd(const Tensor& logits, const Tensor& labels, const optional<Tensor>& bias, double eps,
-                           int64_t ignore) {
+                           int64_t ignore, double softcap) {
+  TORCH_CHECK(softcap >= 0.0 && std::isfinite(softcap), "ce: softcap must be finite and >= 0, got ", softcap);
   const void* lp = ce_logits(logits);
   const long N = logits.size(0);
   const int V = logits.size(1);
@@ -34,13 +38,14 @@ std::vector<Tensor> ce_fwd(const Tensor& logits, const Tensor& labels, const opt
   auto loss = at::empty({N}, f32), lse = at::empty({N}, f32);
   if (N > 0)
     check_rc(dllm_ce_fwd(lp, labels_p, bp, loss.data_ptr<float>(), lse.data_ptr<float>(), N, V, (float)eps, ignore,
-                         is_bf16(logits), stream()),
+                         is_bf16(logits), (float)softcap, stream()),
              "ce_fwd");
   return {loss, lse};
 }
 
 Tensor ce_bwd(const Tensor& scale, Tensor logits, const Tensor& labels, const Tensor& lse,
-              const optional<Tensor>& bias, double eps, int64_t ignore, bool inplace) {
+              const optional<Tensor>& bias, double eps, int64_t ignore, bool inplace, double softcap) {
+  TORCH_CHECK(softcap >= 0.0 && std::isfinite(softcap), "ce: softcap must be finite and >= 0, got ", softcap);
   void* lp = ce_logits(logits);
   const float* scale_p = flat_ptr<const float>(scale, logits, at::kFloat, scalar(), "ce: scale");
   const long N = logits.size(0);
@@ -52,7 +57,7 @@ Tensor ce_bwd(const Tensor& scale, Tensor logits, const Tensor& labels, const Te
   Tensor out = inplace ? logits : at::empty_like(logits);
   if (N > 0)
     check_rc(dllm_ce_bwd(scale_p, lp, labels_p, lse_p, bp, inplace ? lp : out.data_ptr(), N, V, (float)eps, ignore,
-                         is_bf16(logits), stream()),
+                         is_bf16(logits), (float)softcap, stream()),
              "ce_bwd");
   return out;
 }
@@ -65,7 +70,9 @@ Rows<void> chunk_logits(const Tensor& logits, const char* what) {
 }
 
 void ce_chunk_fwd(const Tensor& logits, const Tensor& labels, const optional<Tensor>& bias, Tensor& state, Tensor& loss,
-                  Tensor& lse, int64_t c0, int64_t V, double eps, int64_t ignore, bool first, bool last, int64_t skip) {
+                  Tensor& lse, int64_t c0, int64_t V, double eps, int64_t ignore, bool first, bool last, int64_t skip,
+                  double softcap) {
+  TORCH_CHECK(softcap >= 0.0 && std::isfinite(softcap), "ce_chunk: softcap must be finite and >= 0, got ", softcap);
   const auto lg = chunk_logits(logits, "ce_chunk: logits");
   const int64_t N = logits.size(0), Vc = logits.size(1);
   const int64_t* labels_p = flat_ptr<const int64_t>(labels, logits, at::kLong, exactly(N), "ce_chunk: labels");
@@ -77,12 +84,14 @@ void ce_chunk_fwd(const Tensor& logits, const Tensor& labels, const optional<Ten
   const float* bp = flat_ptr<const float>(bias, logits, at::kFloat, exactly(V), "ce_chunk: bias");
   if (N == 0) return;
   check_rc(dllm_ce_chunk_fwd(lg.ptr, lg.ld, labels_p, bp, state_p, loss_p, lse_p, N, (int)Vc, (int)c0, (int)V,
-                             (float)eps, ignore, first, last, (int)skip, stream()),
+                             (float)eps, ignore, first, last, (int)skip, (float)softcap, stream()),
            "ce_chunk_fwd");
 }
 
 void ce_chunk_bwd(const Tensor& scale, Tensor& logits, const Tensor& labels, const Tensor& lse,
-                  const optional<Tensor>& bias, int64_t c0, int64_t V, double eps, int64_t ignore, int64_t skip) {
+                  const optional<Tensor>& bias, int64_t c0, int64_t V, double eps, int64_t ignore, int64_t skip,
+                  double softcap) {
+  TORCH_CHECK(softcap >= 0.0 && std::isfinite(softcap), "ce_chunk_bwd: softcap must be finite and >= 0, got ", softcap);
   const auto lg = chunk_logits(logits, "ce_chunk_bwd: logits");
   const int64_t N = logits.size(0), Vc = logits.size(1);
   const float* scale_p = flat_ptr<const float>(scale, logits, at::kFloat, scalar(), "ce_chunk_bwd: scale");
@@ -93,7 +102,7 @@ void ce_chunk_bwd(const Tensor& scale, Tensor& logits, const Tensor& labels, con
   const float* bp = flat_ptr<const float>(bias, logits, at::kFloat, exactly(V), "ce_chunk_bwd: bias");
   if (N == 0) return;
   check_rc(dllm_ce_chunk_bwd(scale_p, lg.ptr, lg.ld, labels_p, lse_p, bp, N, (int)Vc, (int)c0, (int)V, (float)eps,
-                             ignore, (int)skip, stream()),
+                             ignore, (int)skip, (float)softcap, stream()),
            "ce_chunk_bwd");
 }
 
@@ -337,10 +346,16 @@ void pref_chunk_bwd(const Tensor& coef, Tensor& policy, const Tensor& labels, co
 }  // namespace
 
 void bind_loss(pybind11::module& m) {
-  m.def("ce_fwd", &ce_fwd);
-  m.def("ce_bwd", &ce_bwd);
-  m.def("ce_chunk_fwd", &ce_chunk_fwd);
-  m.def("ce_chunk_bwd", &ce_chunk_bwd);
+  m.def("ce_fwd", &ce_fwd, py::arg("logits"), py::arg("labels"), py::arg("bias"), py::arg("eps"), py::arg("ignore"),
+        py::arg("softcap") = 0.0);
+  m.def("ce_bwd", &ce_bwd, py::arg("scale"), py::arg("logits"), py::arg("labels"), py::arg("lse"), py::arg("bias"),
+        py::arg("eps"), py::arg("ignore"), py::arg("inplace"), py::arg("softcap") = 0.0);
+  m.def("ce_chunk_fwd", &ce_chunk_fwd, py::arg("logits"), py::arg("labels"), py::arg("bias"), py::arg("state"),
+        py::arg("loss"), py::arg("lse"), py::arg("c0"), py::arg("V"), py::arg("eps"), py::arg("ignore"),
+        py::arg("first"), py::arg("last"), py::arg("skip"), py::arg("softcap") = 0.0);
+  m.def("ce_chunk_bwd", &ce_chunk_bwd, py::arg("scale"), py::arg("logits"), py::arg("labels"), py::arg("lse"),
+        py::arg("bias"), py::arg("c0"), py::arg("V"), py::arg("eps"), py::arg("ignore"), py::arg("skip"),
+        py::arg("softcap") = 0.0);
   m.def("kd_fwd", &kd_fwd, "distillation loss forward (CE + KL to the teacher): (ce_rows, kl_rows, stats [N, 3])");
   m.def("kd_bwd", &kd_bwd, "student-logits gradient of the distillation loss, optionally in place");
   m.def("kd_chunk_fwd", &kd_chunk_fwd);

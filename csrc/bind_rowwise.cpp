@@ -1,5 +1,5 @@
 // Row-wise kernels: norms (csrc/norm.hip), activations and dropout (csrc/act.hip), column sums (csrc/colsum.hip,
-// csrc/norm.hip) and the embedding backward (csrc/embed.hip).
+// csrc/norm.hip), the embedding backward (csrc/embed.hip) and the rotary position embedding (csrc/rope.hip).
 #include "bind_common.h"
 
 namespace dllm {
@@ -15,7 +15,7 @@ const void* dense_rows(const Tensor& x, const char* name, const char* shape_msg)
 // ------------------------------------------------------------------------------------------- norms
 std::vector<Tensor> norm_fwd(const Tensor& x, const optional<Tensor>& resid, const Tensor& w,
                              const optional<Tensor>& b, double eps, double p, int64_t seed, int64_t kind,
-                             bool want_s) {
+                             bool want_s, double w_offset) {
   const void* xp = dense_rows(x, "x", "x must be contiguous [N, d]");
   const int N = x.size(0), d = x.size(1);
   TORCH_CHECK(d % 4 == 0 && d <= 2048, "norm: d must be a multiple of 4 and <= 2048, got ", d);
@@ -32,7 +32,7 @@ std::vector<Tensor> norm_fwd(const Tensor& x, const optional<Tensor>& resid, con
   if (N > 0)
     check_rc(dllm_norm_fwd(xp, rp, wp, bp, out.data_ptr(), need_s ? s.data_ptr() : nullptr,
                            kind == 1 ? mean.data_ptr<float>() : nullptr, rstd.data_ptr<float>(), N, d, (float)eps,
-                           (float)p, (uint32_t)seed, (int)kind, is_bf16(x), stream()),
+                           (float)p, (uint32_t)seed, (int)kind, is_bf16(x), (float)w_offset, stream()),
              "norm_fwd");
   return {out, s, mean, rstd};
 }
@@ -41,7 +41,7 @@ std::vector<Tensor> norm_bwd(const optional<Tensor>& dout_o, const optional<Tens
                              const Tensor& w, const optional<Tensor>& b, const optional<Tensor>& mean,
                              const Tensor& rstd, double p, int64_t seed, int64_t kind, bool want_stream,
                              const optional<Tensor>& dw_acc, const optional<Tensor>& db_acc, bool want_colsum,
-                             bool partials_only) {
+                             bool partials_only, double w_offset) {
   const void* sp = dense_rows(s, "s", "s must be contiguous [N, d]");
   const int N = s.size(0), d = s.size(1);
   Tensor dout = has(dout_o) ? dout_o->contiguous() : at::zeros_like(s);
@@ -93,7 +93,7 @@ std::vector<Tensor> norm_bwd(const optional<Tensor>& dout_o, const optional<Tens
                            db.defined() ? db.data_ptr<float>() : nullptr, dw_acc_p, db_acc_p,
                            want_colsum ? dxs_part.data_ptr<float>() : nullptr, /*dxs=*/nullptr, N, d, (float)p,
                            (uint32_t)seed, (int)kind, is_bf16(s), acc && dw_acc->scalar_type() == at::kFloat,
-                           stream()),
+                           (float)w_offset, stream()),
              "norm_bwd");
   if (partials_only) return {dx, dstream, dw_part, db_part, dxs_part};
   return {dx, dstream, dw, db, dxs_part};
@@ -176,14 +176,51 @@ void embed_bwd(const Tensor& ids_sorted, const Tensor& perm, const Tensor& dy, T
            "embed_bwd");
 }
 
+// ------------------------------------------------------------------------------------------- rotary embedding
+// x [B, S, n, H, D] (a strided view, head dim contiguous) rotated in place by the positions' cos / sin rows
+// (csrc/rope.hip); sign -1: the backward.  Returns x.
+Tensor rope_fwd(Tensor x, const Tensor& pos, const Tensor& cos, const Tensor& sin, double sign) {
+  const std::string where = residency_fault(x, x);
+  TORCH_CHECK(where.empty(), "rope: x ", where);
+  const bool bf = is_bf16(x);
+  const int64_t E = bf ? 8 : 4;
+  TORCH_CHECK(x.dim() == 5, "rope: x must be [B, S, n, H, D], got ", x.sizes());
+  const int64_t B = x.size(0), S = x.size(1), n = x.size(2), H = x.size(3), D = x.size(4);
+  TORCH_CHECK(D % (2 * E) == 0, "rope: head dim must be a multiple of ", 2 * E, " (16-B chunks per half), got ", D);
+  TORCH_CHECK(x.stride(4) == 1, "rope: head dim must be contiguous");
+  for (int i = 0; i < 4; ++i)
+    TORCH_CHECK(x.stride(i) % E == 0, "rope: strides must be multiples of ", E, " elements (16-B vector loads)");
+  const std::string al = align_fault(x, 16);
+  TORCH_CHECK(al.empty(), "rope: x ", al);
+  TORCH_CHECK(sign == 1.0 || sign == -1.0, "rope: sign must be 1 or -1");
+  TORCH_CHECK((pos.dim() == 1 && pos.size(0) == S) || (pos.dim() == 2 && pos.size(0) == B && pos.size(1) == S),
+              "rope: pos must be int32 [S] or [B, S] = [", B, ", ", S, "], got ", pos.sizes());
+  const int* pos_p = flat_ptr<const int>(pos, x, at::kInt, exactly(pos.dim() == 1 ? S : B * S), "rope: pos");
+  TORCH_CHECK(cos.dim() == 2 && cos.size(1) == D / 2 && cos.size(0) > 0 && cos.size(0) < INT_MAX &&
+                  sin.sizes() == cos.sizes(),
+              "rope: cos / sin must be fp32 [max_pos, D / 2]");
+  const float* cp = flat_ptr<const float>(cos, x, at::kFloat, exactly(cos.numel(), 16), "rope: cos");
+  const float* sp = flat_ptr<const float>(sin, x, at::kFloat, exactly(sin.numel(), 16), "rope: sin");
+  TORCH_CHECK(B * S * n * H * (D / 2 / E) < ((int64_t)1 << 38) && B < INT_MAX && S < INT_MAX && H < INT_MAX &&
+                  n < INT_MAX, "rope: too large");
+  if (x.numel() == 0) return x;
+  check_rc(dllm_rope(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), x.stride(3), (int)n, (int)B, (int)S, (int)H,
+                     (int)D, pos_p, pos.dim() == 1 ? 0 : S, cp, sp, (int)cos.size(0), (float)sign, bf, stream()),
+           "rope_fwd");
+  return x;
+}
+
 }  // namespace
 
 void bind_rowwise(pybind11::module& m) {
-  m.def("norm_fwd", &norm_fwd);
+  m.def("rope_fwd", &rope_fwd, py::arg("x"), py::arg("pos"), py::arg("cos"), py::arg("sin"), py::arg("sign") = 1.0,
+        "rotary position embedding of the slots of x [B, S, n, H, D], in place (sign -1: the backward)");
+  m.def("norm_fwd", &norm_fwd, py::arg("x"), py::arg("resid"), py::arg("w"), py::arg("b"), py::arg("eps"),
+        py::arg("p"), py::arg("seed"), py::arg("kind"), py::arg("want_s"), py::arg("w_offset") = 0.0);
   m.def("norm_bwd", &norm_bwd, py::arg("dout"), py::arg("ds"), py::arg("s"), py::arg("w"), py::arg("b"),
         py::arg("mean"), py::arg("rstd"), py::arg("p"), py::arg("seed"), py::arg("kind"), py::arg("want_stream"),
         py::arg("dw_acc") = py::none(), py::arg("db_acc") = py::none(), py::arg("want_colsum") = false,
-        py::arg("partials_only") = false);
+        py::arg("partials_only") = false, py::arg("w_offset") = 0.0);
   m.def("act_fwd", &act_fwd);
   m.def("act_bwd", &act_bwd);
   m.def("dropout_fwd", &dropout_fwd);

@@ -23,12 +23,13 @@ DLLM_SEED_STEP_TUS(DLLM_DECLARE_SEED_STEP)
 
 // ---- csrc/norm.hip
 int dllm_norm_fwd(const void* x, const void* resid, const void* w, const void* b, void* out, void* s_out, float* mean,
-                  float* rstd, int N, int d, float eps, float p, uint32_t seed, int kind, int is_bf16, hipStream_t st);
+                  float* rstd, int N, int d, float eps, float p, uint32_t seed, int kind, int is_bf16, float w_offset,
+                  hipStream_t st);
 int dllm_norm_bwd_grid(int N);
 int dllm_norm_bwd(const void* dout, const void* ds_extra, const void* s, const void* w, const float* mean,
                   const float* rstd, void* dx, void* dstream, float* dw_part, float* db_part, float* dw, float* db,
                   void* dw_acc, void* db_acc, float* dxs_part, float* dxs, int N, int d, float p, uint32_t seed,
-                  int kind, int is_bf16, int acc_f32, hipStream_t st);
+                  int kind, int is_bf16, int acc_f32, float w_offset, hipStream_t st);
 int dllm_colsum_partials_acc(const float* part, void* out, int out_is_bf16, int G, int d, hipStream_t st);
 
 // ---- csrc/act.hip
@@ -45,15 +46,16 @@ int dllm_embed_bwd(const int64_t* ids, const int64_t* perm, const void* dy, long
                    void* out, long V, long padding_idx, int out_f32, hipStream_t st);
 
 // ---- csrc/ce.hip
+// cap: the soft cap c of x' = c tanh(x / c) (0: none), in all four
 int dllm_ce_fwd(const void* logits, const int64_t* labels, const float* bias, float* loss, float* lse, long N, int V,
-                float eps, long ignore, int is_bf16, hipStream_t st);
+                float eps, long ignore, int is_bf16, float cap, hipStream_t st);
 int dllm_ce_bwd(const float* scale, const void* logits, const int64_t* labels, const float* lse, const float* bias,
-                void* dlogits, long N, int V, float eps, long ignore, int is_bf16, hipStream_t st);
+                void* dlogits, long N, int V, float eps, long ignore, int is_bf16, float cap, hipStream_t st);
 int dllm_ce_chunk_fwd(const void* logits, long ld, const int64_t* labels, const float* bias, float* state, float* loss,
                       float* lse, long N, int Vc, int c0, int V, float eps, long ignore, int first, int last, int skip,
-                      hipStream_t st);
+                      float cap, hipStream_t st);
 int dllm_ce_chunk_bwd(const float* scale, void* logits, long ld, const int64_t* labels, const float* lse,
-                      const float* bias, long N, int Vc, int c0, int V, float eps, long ignore, int skip,
+                      const float* bias, long N, int Vc, int c0, int V, float eps, long ignore, int skip, float cap,
                       hipStream_t st);
 int dllm_ce_merge(const float* part, int np, long pstride, const float* xlab, const int64_t* labels, float* loss,
                   float* lse, long N, int V, float eps, long ignore, hipStream_t st);
@@ -108,6 +110,11 @@ int dllm_attn_f32_fwd(AttnF32Params* pp, hipStream_t st);
 int dllm_attn_f32_bwd(AttnF32Params* pp, hipStream_t st);
 int dllm_attn_hd_fwd(AttnHdParams* pp, hipStream_t st);
 int dllm_attn_hd_bwd(AttnHdParams* pp, hipStream_t st);
+
+// ---- csrc/rope.hip: rotate the `n` listed slots of x [B, S, *, H, D] in place (x_sn: the slot stride; strides in
+// elements); pos [B, S] (pos_sb = S) or [S] (pos_sb = 0); cos / sin fp32 [max_pos, D / 2]; sign -1: the backward
+int dllm_rope(void* x, long x_sb, long x_ss, long x_sn, long x_sh, int n, int B, int S, int H, int D, const int* pos,
+              long pos_sb, const float* cos, const float* sin, int max_pos, float sign, int is_bf16, hipStream_t st);
 
 // ---- csrc/gemm.hip, csrc/gemm_fused.hip, csrc/gemm_w4.hip (variant: GEMM_FUSED_V_*, epi: W4_EPI_*; gemm_params.h)
 int dllm_wgrad_reduce(const GemmWgradParams* pp, hipStream_t st);

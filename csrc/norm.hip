@@ -3,7 +3,8 @@
 // One wave64 owns one row; the row stays in registers (up to MAXV*256 columns, 4 elements / lane /
 // chunk, 8-byte bf16 vector loads) so the residual stream is read once and written once.
 // fwd:  s = (resid) + dropout(x)          [stored if resid or dropout]
-//       out = norm(s) * w (+ b)            [RMS: T5 (fp32 variance, weight only); LN: BART]
+//       out = norm(s) * (w + w_offset) (+ b) [RMS: T5 (fp32 variance, weight only); LN: BART; w_offset = 1: Gemma's
+//                                             zero-centred weights.  dw is the gradient of the stored w either way]
 // bwd:  ds = norm_bwd(dout) + ds_extra     [ds_extra = gradient of the stream from later layers]
 //       dx = dropout_bwd(ds);  dstream = ds (optional);  dw/db via per-block column partials.
 // Dropout keep-decision for element row*d + col: common.h dropout4 / ops/rng.py keep_mask.
@@ -17,13 +18,15 @@ DLLM_SEED_STEP_TU(norm)
 
 namespace {
 
-template <typename T, int KIND, int MAXV>
+// OFF: the weight is read as w + woff (RMSNorm only; instantiations of their own, so that the kernels of every call
+// without an offset are the code they were)
+template <typename T, int KIND, int MAXV, bool OFF>
 __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* __restrict__ x, const T* __restrict__ resid,
                                                        const T* __restrict__ w, const T* __restrict__ b,
                                                        T* __restrict__ out, T* __restrict__ s_out,
                                                        float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                        int N, int d, float eps, float p, uint32_t seed,
-                                                       uint32_t thr) {
+                                                       uint32_t thr, float woff) {
   if (p > 0.f) seed = eff_seed(seed);
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -73,6 +76,7 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* __restrict__ x, 
     const int col = (c * 64 + lane) * 4;
     if (col < d) {
       f32x4 wv = Elem<T>::load4(w + col);
+      if constexpr (OFF) wv += woff;
       f32x4 o = (v[c] - mean) * rstd * wv;
       if (KIND == 1 && b != nullptr) o += Elem<T>::load4(b + col);
       Elem<T>::store4(out + base + col, o);
@@ -88,14 +92,15 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* __restrict__ x, 
 // iteration (d <= 1024) with every load of both rows (s, dout, ds_extra) issued before the first reduction, the weight row
 // hoisted out of the loop, and out-of-range columns / the missing second row read a clamped address and are
 // zeroed instead of branched around, so the body stays straight-line.
-template <typename T, int KIND, int MAXV, bool EX>
+template <typename T, int KIND, int MAXV, bool EX, bool OFF>
 __global__ __launch_bounds__(256) void norm_bwd_kernel(const T* __restrict__ dout, const T* __restrict__ ds_extra,
                                                        const T* __restrict__ s, const T* __restrict__ w,
                                                        const float* __restrict__ mean_in,
                                                        const float* __restrict__ rstd_in, T* __restrict__ dx,
                                                        T* __restrict__ dstream, float* __restrict__ dw_part,
                                                        float* __restrict__ db_part, float* __restrict__ dxs_part,
-                                                       int N, int d, float p, uint32_t seed, uint32_t thr) {
+                                                       int N, int d, float p, uint32_t seed, uint32_t thr,
+                                                       float woff) {
   if (p > 0.f) seed = eff_seed(seed);
   extern __shared__ __attribute__((aligned(16))) float red[];  // [4][d]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -111,7 +116,9 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(const T* __restrict__ dou
     const int col = (c * 64 + lane) * 4;
     cm[c] = col < d ? 1.f : 0.f;
     cof[c] = col < d ? col : 0;
-    wgt[c] = Elem<T>::load4(w + cof[c]) * cm[c];
+    wgt[c] = Elem<T>::load4(w + cof[c]);
+    if constexpr (OFF) wgt[c] += woff;
+    wgt[c] = wgt[c] * cm[c];
     adw[c] = adb[c] = adx[c] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   constexpr int R = MAXV <= 4 ? 2 : 1;  // rows per iteration (registers: d = 2048 stays at one row)
@@ -237,15 +244,15 @@ __global__ __launch_bounds__(1024) void col_sum_acc_kernel(const float* __restri
   }
 }
 
-template <typename T, int KIND>
+template <typename T, int KIND, bool OFF>
 int launch_fwd(const void* x, const void* resid, const void* w, const void* b, void* out, void* s_out, float* mean,
-               float* rstd, int N, int d, float eps, float p, uint32_t seed, hipStream_t st) {
+               float* rstd, int N, int d, float eps, float p, uint32_t seed, float woff, hipStream_t st) {
   const int chunks = (d + 255) / 256;
   dim3 grid((N + 3) / 4), block(256);
   const uint32_t thr = drop_threshold(p);
 #define L(MV)                                                                                                     \
-  hipLaunchKernelGGL((norm_fwd_kernel<T, KIND, MV>), grid, block, 0, st, (const T*)x, (const T*)resid,           \
-                     (const T*)w, (const T*)b, (T*)out, (T*)s_out, mean, rstd, N, d, eps, p, seed, thr)
+  hipLaunchKernelGGL((norm_fwd_kernel<T, KIND, MV, OFF>), grid, block, 0, st, (const T*)x, (const T*)resid,           \
+                     (const T*)w, (const T*)b, (T*)out, (T*)s_out, mean, rstd, N, d, eps, p, seed, thr, woff)
   if (chunks <= 1) L(1);
   else if (chunks <= 2) L(2);
   else if (chunks <= 3) L(3);
@@ -257,11 +264,11 @@ int launch_fwd(const void* x, const void* resid, const void* w, const void* b, v
   return 0;
 }
 
-template <typename T, int KIND>
+template <typename T, int KIND, bool OFF>
 int launch_bwd(const void* dout, const void* ds_extra, const void* s, const void* w, const float* mean,
                const float* rstd, void* dx, void* dstream, float* dw_part, float* db_part, float* dw, float* db,
                void* dw_acc, void* db_acc, float* dxs_part, float* dxs, int N, int d, float p, uint32_t seed, int G,
-               int acc_f32, hipStream_t st) {
+               int acc_f32, float woff, hipStream_t st) {
   const int chunks = (d + 255) / 256;
   dim3 grid(G), block(256);
   const size_t lds = (size_t)4 * d * sizeof(float);
@@ -269,13 +276,13 @@ int launch_bwd(const void* dout, const void* ds_extra, const void* s, const void
 #define L(MV)                                                                                                     \
   do {                                                                                                            \
     if (ds_extra != nullptr)                                                                                      \
-      hipLaunchKernelGGL((norm_bwd_kernel<T, KIND, MV, true>), grid, block, lds, st, (const T*)dout,              \
+      hipLaunchKernelGGL((norm_bwd_kernel<T, KIND, MV, true, OFF>), grid, block, lds, st, (const T*)dout,         \
                          (const T*)ds_extra, (const T*)s, (const T*)w, mean, rstd, (T*)dx, (T*)dstream, dw_part,  \
-                         db_part, dxs_part, N, d, p, seed, thr);                                                  \
+                         db_part, dxs_part, N, d, p, seed, thr, woff);                                                \
     else                                                                                                          \
-      hipLaunchKernelGGL((norm_bwd_kernel<T, KIND, MV, false>), grid, block, lds, st, (const T*)dout,             \
+      hipLaunchKernelGGL((norm_bwd_kernel<T, KIND, MV, false, OFF>), grid, block, lds, st, (const T*)dout,        \
                          (const T*)ds_extra, (const T*)s, (const T*)w, mean, rstd, (T*)dx, (T*)dstream, dw_part,  \
-                         db_part, dxs_part, N, d, p, seed, thr);                                                  \
+                         db_part, dxs_part, N, d, p, seed, thr, woff);                                                \
   } while (0)
   if (chunks <= 1) L(1);
   else if (chunks <= 2) L(2);
@@ -310,14 +317,14 @@ int launch_bwd(const void* dout, const void* ds_extra, const void* s, const void
 
 extern "C" int dllm_norm_fwd(const void* x, const void* resid, const void* w, const void* b, void* out, void* s_out,
                              float* mean, float* rstd, int N, int d, float eps, float p, uint32_t seed, int kind,
-                             int is_bf16, hipStream_t st) {
+                             int is_bf16, float w_offset, hipStream_t st) {
   if (d % 4 != 0) return -2;
-  if (is_bf16) {
-    return kind ? launch_fwd<uint16_t, 1>(x, resid, w, b, out, s_out, mean, rstd, N, d, eps, p, seed, st)
-                : launch_fwd<uint16_t, 0>(x, resid, w, b, out, s_out, mean, rstd, N, d, eps, p, seed, st);
-  }
-  return kind ? launch_fwd<float, 1>(x, resid, w, b, out, s_out, mean, rstd, N, d, eps, p, seed, st)
-              : launch_fwd<float, 0>(x, resid, w, b, out, s_out, mean, rstd, N, d, eps, p, seed, st);
+  if (w_offset != 0.f && kind != 0) return -2;  // the offset is RMSNorm's
+#define A x, resid, w, b, out, s_out, mean, rstd, N, d, eps, p, seed, w_offset, st
+  if (w_offset != 0.f) return is_bf16 ? launch_fwd<uint16_t, 0, true>(A) : launch_fwd<float, 0, true>(A);
+  if (is_bf16) return kind ? launch_fwd<uint16_t, 1, false>(A) : launch_fwd<uint16_t, 0, false>(A);
+  return kind ? launch_fwd<float, 1, false>(A) : launch_fwd<float, 0, false>(A);
+#undef A
 }
 
 // Number of partial rows the caller must allocate for dw_part/db_part: the workgroup cap, 512 = 2 per CU (each wave
@@ -343,12 +350,14 @@ extern "C" int dllm_norm_bwd_grid(int N) {
 extern "C" int dllm_norm_bwd(const void* dout, const void* ds_extra, const void* s, const void* w, const float* mean,
                              const float* rstd, void* dx, void* dstream, float* dw_part, float* db_part, float* dw,
                              float* db, void* dw_acc, void* db_acc, float* dxs_part, float* dxs, int N, int d, float p,
-                             uint32_t seed, int kind, int is_bf16, int acc_f32, hipStream_t st) {
+                             uint32_t seed, int kind, int is_bf16, int acc_f32, float w_offset, hipStream_t st) {
   if (d % 4 != 0) return -2;
   const int G = dllm_norm_bwd_grid(N);
 #define A dout, ds_extra, s, w, mean, rstd, dx, dstream, dw_part, db_part, dw, db, dw_acc, db_acc, dxs_part, dxs, N, d, p, \
-          seed, G, acc_f32, st
-  if (is_bf16) return kind ? launch_bwd<uint16_t, 1>(A) : launch_bwd<uint16_t, 0>(A);
-  return kind ? launch_bwd<float, 1>(A) : launch_bwd<float, 0>(A);
+          seed, G, acc_f32, w_offset, st
+  if (w_offset != 0.f && kind != 0) return -2;  // the offset is RMSNorm's
+  if (w_offset != 0.f) return is_bf16 ? launch_bwd<uint16_t, 0, true>(A) : launch_bwd<float, 0, true>(A);
+  if (is_bf16) return kind ? launch_bwd<uint16_t, 1, false>(A) : launch_bwd<uint16_t, 0, false>(A);
+  return kind ? launch_bwd<float, 1, false>(A) : launch_bwd<float, 0, false>(A);
 #undef A
 }

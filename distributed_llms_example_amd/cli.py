@@ -339,6 +339,9 @@ def build_data(args, cfg):
     tr = convert_examples_to_features(recs["train"], tok, args.max_source_length, args.max_target_length,
                                       ignore_pad_labels=args.ignore_pad_labels)
     if getattr(args, "pack_sequences", False):
+        if cfg.model_type == "t5gemma":
+            raise NotImplementedError("--pack-sequences is not implemented for T5Gemma (the attention kernels have no "
+                                      "soft cap with segments)")
         if cfg.local_encoder:
             raise NotImplementedError("--pack-sequences is not implemented for LongT5 (windowed attention takes no "
                                       "segments)")

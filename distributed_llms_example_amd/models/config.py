@@ -20,7 +20,7 @@ from dataclasses import dataclass, field
 @dataclass
 class Seq2SeqConfig:
     # "t5" | BART family: "bart" | "mbart" | "pegasus" | "marian" | "m2m_100" | "plbart" | "blenderbot" | "led" |
-    # "bigbird_pegasus"
+    # "bigbird_pegasus" | "t5gemma"
     model_type: str = "t5"
     # T5 implementation variants: "t5" / "mt5" (same layers), "umt5" (every self-attention layer owns its
     # relative-position bias table: modeling_umt5.py UMT5LayerSelfAttention, has_relative_attention_bias=True),
@@ -81,6 +81,24 @@ class Seq2SeqConfig:
     block_size: int = 64
     num_random_blocks: int = 3
     use_bias: bool = True
+    # T5Gemma (model_type="t5gemma", modeling_t5gemma.py; models/t5gemma.py): Gemma 2 layers in both stacks.  d_kv is
+    # Gemma's head_dim, d_ff its intermediate_size, layer_norm_epsilon its rms_norm_eps, init_std its
+    # initializer_range, max_position_embeddings the encoder's; decoder_start_token_id is decoder.bos_token_id.
+    # num_kv_heads: K/V heads (None: num_heads), each serving num_heads / num_kv_heads query heads; scores are
+    # attn_logit_softcapping * tanh(q.k * query_pre_attn_scalar**-0.5 / attn_logit_softcapping) (None: no cap) and the
+    # logits final_logit_softcapping * tanh(x / final_logit_softcapping); rotate-half RoPE with rope_theta;
+    # layer_types / decoder_layer_types: per layer "sliding_attention" (keys within sliding_window /
+    # decoder_sliding_window) or "full_attention" (None: alternating, sliding first)
+    num_kv_heads: int | None = None
+    query_pre_attn_scalar: int = 256
+    attn_logit_softcapping: float | None = None
+    final_logit_softcapping: float | None = None
+    rope_theta: float = 10000.0
+    sliding_window: int | None = None
+    decoder_sliding_window: int | None = None
+    layer_types: list | None = None
+    decoder_layer_types: list | None = None
+    decoder_max_position_embeddings: int | None = None
     # special tokens
     pad_token_id: int = 0
     eos_token_id: int = 1
@@ -93,6 +111,28 @@ class Seq2SeqConfig:
     name: str = ""
 
     def __post_init__(self):
+        if self.model_type == "t5gemma":
+            kv = self.num_kv_heads if self.num_kv_heads is not None else self.num_heads
+            if kv < 1 or self.num_heads % kv:
+                raise ValueError(f"T5Gemma: num_heads ({self.num_heads}) must be a multiple of num_kv_heads ({kv})")
+            self.num_kv_heads = kv
+            for attr, n in (("layer_types", self.num_layers), ("decoder_layer_types", self.num_decoder_layers)):
+                lt = getattr(self, attr)
+                if lt is None:  # T5GemmaModuleConfig's default
+                    lt = ["sliding_attention" if (i + 1) % 2 else "full_attention" for i in range(n)]
+                lt = list(lt)
+                if len(lt) != n or any(t not in ("sliding_attention", "full_attention") for t in lt):
+                    raise ValueError(f"T5Gemma: {attr} needs one of 'sliding_attention' / 'full_attention' per layer "
+                                     f"({n}), got {lt}")
+                setattr(self, attr, lt)
+            for attr, lt in (("sliding_window", self.layer_types), ("decoder_sliding_window", self.decoder_layer_types)):
+                w = getattr(self, attr)
+                if "sliding_attention" in lt and (not isinstance(w, int) or w < 1):
+                    raise ValueError(f"T5Gemma: {attr} must be a positive int with sliding_attention layers, got {w}")
+            if self.decoder_max_position_embeddings is None:
+                self.decoder_max_position_embeddings = self.max_position_embeddings
+            if self.d_kv % 2:
+                raise ValueError(f"T5Gemma: head_dim must be even (rotary halves), got {self.d_kv}")
         if self.model_type == "led":
             w = self.attention_window if self.attention_window is not None else 512
             w = [w] * self.num_layers if isinstance(w, int) else list(w)
@@ -150,7 +190,60 @@ class Seq2SeqConfig:
         return c
 
     # ---------------------------------------------------------------- HF config.json I/O
+    def _t5gemma_module(self, decoder: bool) -> dict:
+        """One stack's T5GemmaModuleConfig as config.json holds it."""
+        return {
+            "model_type": "t5_gemma_module",
+            "vocab_size": self.vocab_size,
+            "hidden_size": self.d_model,
+            "intermediate_size": self.d_ff,
+            "num_hidden_layers": self.num_decoder_layers if decoder else self.num_layers,
+            "num_attention_heads": self.num_heads,
+            "num_key_value_heads": self.num_kv_heads,
+            "head_dim": self.d_kv,
+            "hidden_activation": _GEMMA_ACT_OUT[self.feed_forward_proj],
+            "max_position_embeddings": self.decoder_max_position_embeddings if decoder else self.max_position_embeddings,
+            "initializer_range": self.init_std,
+            "rms_norm_eps": self.layer_norm_epsilon,
+            "pad_token_id": self.pad_token_id,
+            "eos_token_id": self.eos_token_id,
+            "bos_token_id": self.bos_token_id,
+            "rope_parameters": {"rope_type": "default", "rope_theta": self.rope_theta},
+            "attention_bias": False,
+            "attention_dropout": self.attention_dropout,
+            "dropout_rate": self.dropout_rate,
+            "query_pre_attn_scalar": self.query_pre_attn_scalar,
+            "sliding_window": self.decoder_sliding_window if decoder else self.sliding_window,
+            "layer_types": list(self.decoder_layer_types if decoder else self.layer_types),
+            "final_logit_softcapping": self.final_logit_softcapping,
+            "attn_logit_softcapping": self.attn_logit_softcapping,
+            "is_decoder": decoder,
+            "tie_word_embeddings": self.tie_word_embeddings,
+        }
+
     def to_hf_dict(self) -> dict:
+        if self.model_type == "t5gemma":
+            return {
+                "architectures": ["T5GemmaForConditionalGeneration"],
+                "model_type": "t5gemma",
+                "encoder": self._t5gemma_module(False),
+                "decoder": self._t5gemma_module(True),
+                "is_encoder_decoder": True,
+                "dropout_rate": self.dropout_rate,
+                "attention_dropout": self.attention_dropout,
+                "tie_word_embeddings": self.tie_word_embeddings,
+                "vocab_size": self.vocab_size,
+                # the width under the name every other family's config.json has.  transformers keeps a key it does not
+                # know as an attribute, so `AutoConfig.for_model(...).d_model` answers for this family as for the
+                # others: tests/test_model_parity.py test_every_preset_round_trips_through_config_json reads it off
+                # every preset's transformers config
+                "d_model": self.d_model,
+                "initializer_range": self.init_std,
+                "pad_token_id": self.pad_token_id,
+                "eos_token_id": self.eos_token_id,
+                "bos_token_id": self.bos_token_id,
+                "torch_dtype": "float32",
+            }
         if self.model_type == "t5":
             d = {
                 "architectures": [{"t5": "T5ForConditionalGeneration", "mt5": "MT5ForConditionalGeneration",
@@ -230,8 +323,60 @@ class Seq2SeqConfig:
         return d
 
     @classmethod
+    def _from_t5gemma(cls, d: dict) -> "Seq2SeqConfig":
+        """config.json of a T5Gemma checkpoint: nested ``encoder`` / ``decoder`` Gemma 2 module configs
+        (configuration_t5gemma.py; a missing key takes T5GemmaModuleConfig's default).  The two stacks share one head
+        geometry here, so they must agree in it; layer counts, layer types, windows and position limits may differ."""
+        enc, dec = dict(d.get("encoder") or {}), dict(d.get("decoder") or {})
+        dflt = {"vocab_size": 256000, "hidden_size": 2304, "intermediate_size": 9216, "num_hidden_layers": 26,
+                "num_attention_heads": 8, "num_key_value_heads": 4, "head_dim": 256,
+                "hidden_activation": "gelu_pytorch_tanh", "max_position_embeddings": 8192, "initializer_range": 0.02,
+                "rms_norm_eps": 1e-6, "pad_token_id": 0, "eos_token_id": 1, "bos_token_id": 2,
+                "query_pre_attn_scalar": 256, "sliding_window": 4096, "layer_types": None,
+                "final_logit_softcapping": 30.0, "attn_logit_softcapping": 50.0, "attention_bias": False}
+        e, c = {**dflt, **enc}, {**dflt, **dec}
+        for k in ("hidden_size", "head_dim", "num_attention_heads", "num_key_value_heads", "intermediate_size",
+                  "vocab_size", "hidden_activation", "rms_norm_eps", "query_pre_attn_scalar",
+                  "attn_logit_softcapping"):
+            if e[k] != c[k]:
+                raise ValueError(f"T5Gemma: encoder and decoder differ in {k} ({e[k]} and {c[k]}): unbalanced "
+                                 "encoder / decoder sizes (such as t5gemma-9b-2b) are not implemented")
+        if e["attention_bias"] or c["attention_bias"]:
+            raise ValueError("T5Gemma: attention_bias is not implemented")
+        if e["hidden_activation"] not in _GEMMA_ACT_IN:
+            raise ValueError(f"T5Gemma: unsupported hidden_activation {e['hidden_activation']!r}")
+
+        def theta(m):
+            rp = m.get("rope_parameters") or {}
+            if rp.get("rope_type", "default") != "default":
+                raise ValueError(f"T5Gemma: rope_type {rp.get('rope_type')!r} is not implemented")
+            return float(rp.get("rope_theta", m.get("rope_theta", 10000.0)))
+
+        if theta(e) != theta(c):
+            raise ValueError(f"T5Gemma: encoder and decoder differ in rope_theta ({theta(e)} and {theta(c)})")
+        return cls(
+            model_type="t5gemma", vocab_size=d.get("vocab_size", c["vocab_size"]), d_model=e["hidden_size"],
+            d_kv=e["head_dim"], d_ff=e["intermediate_size"], num_layers=e["num_hidden_layers"],
+            num_decoder_layers=c["num_hidden_layers"], num_heads=e["num_attention_heads"],
+            num_kv_heads=e["num_key_value_heads"], feed_forward_proj=_GEMMA_ACT_IN[e["hidden_activation"]],
+            dropout_rate=d.get("dropout_rate", 0.0), attention_dropout=d.get("attention_dropout", 0.0),
+            layer_norm_epsilon=e["rms_norm_eps"], init_std=d.get("initializer_range", c["initializer_range"]),
+            tie_word_embeddings=d.get("tie_word_embeddings", True), scale_decoder_outputs=False,
+            max_position_embeddings=e["max_position_embeddings"],
+            decoder_max_position_embeddings=c["max_position_embeddings"],
+            query_pre_attn_scalar=e["query_pre_attn_scalar"], attn_logit_softcapping=e["attn_logit_softcapping"],
+            final_logit_softcapping=c["final_logit_softcapping"], rope_theta=theta(e),
+            sliding_window=e["sliding_window"], decoder_sliding_window=c["sliding_window"],
+            layer_types=e["layer_types"], decoder_layer_types=c["layer_types"],
+            pad_token_id=c["pad_token_id"], eos_token_id=_first(c["eos_token_id"]), bos_token_id=c["bos_token_id"],
+            decoder_start_token_id=c["bos_token_id"],
+        )
+
+    @classmethod
     def from_hf_dict(cls, d: dict) -> "Seq2SeqConfig":
         mt = d.get("model_type", "t5")
+        if mt == "t5gemma":
+            return cls._from_t5gemma(d)
         if mt in ("t5", "mt5", "umt5", "longt5"):
             extra = {}
             if mt == "longt5":
@@ -314,6 +459,11 @@ class Seq2SeqConfig:
 
 def _first(x):
     return x[0] if isinstance(x, (list, tuple)) else x
+
+
+# Gemma's hidden_activation <-> feed_forward_proj (the gated FFN's activation, ops/ffn.py)
+_GEMMA_ACT_IN = {"gelu_pytorch_tanh": "gated-gelu", "gelu_new": "gated-gelu"}
+_GEMMA_ACT_OUT = {"gated-gelu": "gelu_pytorch_tanh"}
 
 
 # structural switches of the BART-family model types (see the Seq2SeqConfig fields)
@@ -442,6 +592,17 @@ for _n in ("pubmed", "bigpatent"):
 PRESETS["bigbird-tiny"] = _bartlike("bigbird_pegasus", "bigbird-tiny", 512, 64, 2, 4, 128, "gelu_new", 256, True, pad=0,
                                     eos=1, bos=2, start=2, attention_type="block_sparse", block_size=8,
                                     num_random_blocks=2, use_bias=False)
+# T5Gemma tiny configs for the tests: head dim 16, encoder window 4 (a 23-token input spans several), caps that bite.
+# No preset for the published sizes: a checkpoint directory's own config.json is read instead
+PRESETS["t5gemma-tiny"] = Seq2SeqConfig(
+    model_type="t5gemma", name="t5gemma-tiny", vocab_size=512, d_model=64, d_kv=16, d_ff=128, num_layers=2,
+    num_decoder_layers=2, num_heads=4, num_kv_heads=4, feed_forward_proj="gated-gelu", dropout_rate=0.0,
+    attention_dropout=0.0, layer_norm_epsilon=1e-6, init_std=0.02, tie_word_embeddings=True,
+    scale_decoder_outputs=False, max_position_embeddings=128, query_pre_attn_scalar=16, attn_logit_softcapping=2.0,
+    final_logit_softcapping=3.0, rope_theta=10000.0, sliding_window=4, decoder_sliding_window=64,
+    layer_types=["sliding_attention", "full_attention"], decoder_layer_types=["sliding_attention", "full_attention"],
+    pad_token_id=0, eos_token_id=1, bos_token_id=2, decoder_start_token_id=2)
+PRESETS["t5gemma-tiny-gqa"] = PRESETS["t5gemma-tiny"].replace(name="t5gemma-tiny-gqa", num_kv_heads=2)
 PRESETS["t5-tiny"] = _t5("t5-tiny", 64, 128, 2, 4, vocab=512, d_kv=16)
 # the policy / reference of the preference-optimisation tests and of a --dpo-beta smoke run
 PRESETS["dpo-tiny"] = PRESETS["t5-tiny"].replace(name="dpo-tiny")

@@ -80,6 +80,8 @@ def _head_geom(model):
     cfg = model.config
     if cfg.model_type == "t5":
         return cfg.num_heads, cfg.d_kv
+    if cfg.model_type == "t5gemma":  # the cache holds the K/V heads; the model repeats them for the query heads
+        return cfg.num_kv_heads, cfg.d_kv
     return cfg.num_heads, cfg.d_model // cfg.num_heads
 
 

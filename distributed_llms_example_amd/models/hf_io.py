@@ -19,6 +19,7 @@ from safetensors.torch import load_file, save_file
 from .bart import BartForConditionalGeneration
 from .config import Seq2SeqConfig, resolve_config
 from .t5 import T5ForConditionalGeneration
+from .t5gemma import T5GemmaForConditionalGeneration
 
 _FUSED_T5 = {".qkv.weight": [".q.weight", ".k.weight", ".v.weight"], ".kv.weight": [".k.weight", ".v.weight"]}
 _FUSED_BART = {".qkv_proj.": [".q_proj.", ".k_proj.", ".v_proj."], ".kv_proj.": [".k_proj.", ".v_proj."]}
@@ -33,6 +34,26 @@ _FUSED_LED = {".self_attn.qkv_proj.": [_LS + "query.", _LS + "key.", _LS + "valu
 _BS = ".self_attn.self."
 _FUSED_BIGBIRD_ENC = {".self_attn.qkv_proj.": [_BS + "query.", _BS + "key.", _BS + "value."],
                       ".self_attn.out_proj.": [".self_attn.output."]}
+
+
+def _t5gemma_names(cfg, name):
+    """T5Gemma (modeling_t5gemma.py): ``(transformers' names, rows of each)`` of our parameter ``name`` — the fused
+    ``qkv_proj`` is q (H D rows), k and v (H_kv D rows each); ``kv_proj`` and the gated ``mlp.wi`` split in halves
+    (None: equal parts); ``mlp.wo`` is ``down_proj``."""
+    if ".self_attn.qkv_proj." in name:
+        hd, kd = cfg.num_heads * cfg.d_kv, cfg.num_kv_heads * cfg.d_kv
+        return [name.replace(".qkv_proj.", p) for p in (".q_proj.", ".k_proj.", ".v_proj.")], [hd, kd, kd]
+    if ".cross_attn.kv_proj." in name:
+        return [name.replace(".kv_proj.", p) for p in (".k_proj.", ".v_proj.")], None
+    if ".mlp.wi." in name:
+        return [name.replace(".mlp.wi.", p) for p in (".mlp.gate_proj.", ".mlp.up_proj.")], None
+    if ".mlp.wo." in name:
+        return [name.replace(".mlp.wo.", ".mlp.down_proj.")], None
+    return [name], None
+
+
+def _split_rows(t, names, sizes):
+    return t.split(sizes, 0) if sizes is not None else t.chunk(len(names), 0)
 
 
 def _hf_names(cfg, name):
@@ -61,7 +82,8 @@ def _hf_names(cfg, name):
 
 def build_model(cfg_or_name, dtype=torch.float32, device="cpu"):
     cfg = cfg_or_name if isinstance(cfg_or_name, Seq2SeqConfig) else resolve_config(cfg_or_name)
-    cls = T5ForConditionalGeneration if cfg.model_type == "t5" else BartForConditionalGeneration
+    cls = (T5ForConditionalGeneration if cfg.model_type == "t5" else
+           T5GemmaForConditionalGeneration if cfg.model_type == "t5gemma" else BartForConditionalGeneration)
     with torch.device(device):
         model = cls(cfg)
     return model.to(dtype=dtype)
@@ -74,7 +96,11 @@ def to_hf_state_dict(model) -> dict[str, torch.Tensor]:
         t = t.detach()
         if _is_adapter_key(name):  # adapters have a checkpoint of their own (save_adapter)
             continue
-        if cfg.model_type == "t5":
+        if cfg.model_type == "t5gemma":
+            names, sizes = _t5gemma_names(cfg, name)
+            for part, piece in zip(names, _split_rows(t, names, sizes)):
+                out[part] = piece
+        elif cfg.model_type == "t5":
             if name.endswith(".wi.weight") and cfg.is_gated:
                 a, b = t.chunk(2, dim=0)
                 out[name.replace(".wi.weight", ".wi_0.weight")] = a
@@ -111,7 +137,15 @@ def from_hf_state_dict(model, sd: dict[str, torch.Tensor], strict: bool = True):
     for name in own:
         if _is_adapter_key(name):
             continue
-        if cfg.model_type == "t5":
+        if cfg.model_type == "t5gemma":
+            names, _ = _t5gemma_names(cfg, name)
+            if all(p in sd for p in names):
+                new[name] = torch.cat([sd[p] for p in names], 0) if len(names) > 1 else sd[names[0]]
+            elif name == "lm_head.out_proj.weight" and "model.decoder.embed_tokens.weight" in sd:
+                new[name] = sd["model.decoder.embed_tokens.weight"]
+            elif name == "model.decoder.embed_tokens.weight" and "lm_head.out_proj.weight" in sd:
+                new[name] = sd["lm_head.out_proj.weight"]  # a tied checkpoint that kept the head's name
+        elif cfg.model_type == "t5":
             if name.endswith(".wi.weight") and cfg.is_gated:
                 new[name] = torch.cat([sd[name.replace(".wi.weight", ".wi_0.weight")],
                                        sd[name.replace(".wi.weight", ".wi_1.weight")]], 0)
@@ -184,6 +218,8 @@ def _is_adapter_key(name: str) -> bool:
 
 def hf_param_names(cfg, name: str) -> list[str]:
     """transformers' names of the parameters our parameter ``name`` is the concatenation of (along dim 0)."""
+    if cfg.model_type == "t5gemma":
+        return _t5gemma_names(cfg, name)[0]
     if cfg.model_type == "t5":
         if name.endswith(".wi.weight") and cfg.is_gated:
             return [name.replace(".wi.weight", ".wi_0.weight"), name.replace(".wi.weight", ".wi_1.weight")]
@@ -193,6 +229,16 @@ def hf_param_names(cfg, name: str) -> list[str]:
         return [name]
     names = _hf_names(cfg, name)
     return [name] if names is None else names
+
+
+def hf_param_parts(cfg, name: str):
+    """How our parameter ``name`` splits along dim 0 into transformers' parameters: their number when the slices are
+    equal, else the list of their dim-0 sizes (T5Gemma's ``qkv_proj`` with grouped K/V heads: q is longer than k and
+    v).  What a per-transformers-parameter rule such as Adafactor's factored moments takes (ops/optim.py)."""
+    if cfg.model_type == "t5gemma":
+        names, sizes = _t5gemma_names(cfg, name)
+        return list(sizes) if sizes is not None and len(set(sizes)) > 1 else len(names)
+    return len(hf_param_names(cfg, name))
 
 
 # leaf module names of transformers' projections -> our logical LoRA targets (models/lora.py)

@@ -80,6 +80,9 @@ def has_lora(model) -> bool:
 def apply_lora(model: nn.Module, cfg: LoraConfig) -> nn.Module:
     """Freeze every parameter of ``model`` and attach trainable adapters to the projections ``cfg.targets`` names.
     Call it before ``TrainEngine`` / ``FlatParams`` are built (they collect the trainable parameters)."""
+    if getattr(getattr(model, "config", None), "model_type", None) == "t5gemma":
+        raise NotImplementedError("T5Gemma: LoRA (--lora-r) is not implemented: its fused qkv projection has unequal "
+                                  "q and k / v parts with grouped K/V heads")
     if has_lora(model):
         raise RuntimeError("apply_lora: the model already carries adapters (merge_lora removes them)")
     if any(getattr(p, "_dllm_fused_wgrad", False) for p in model.parameters()):

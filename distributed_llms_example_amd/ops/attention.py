@@ -51,6 +51,12 @@ bigbird.py).  The same two kernel files follow the lists at 64-block granularity
 multiple of 64 is expanded, any other block size takes the composite on the GPU — and never load an unlisted block.
 Lists compose with the key-padding mask, the bias and dropout, not with ``causal``, ``window``, segments or global
 keys; bf16 at head dim 32 takes the composite.
+
+Soft cap (Gemma 2 / T5Gemma ``attn_logit_softcapping``): with ``softcap=c`` (``c > 0``) the score of (query, key) is
+``c * tanh(scale * q.k / c)``, formed before every mask.  csrc/attn_hd.hip (bf16, head dim 64 included: csrc/attn.hip
+has no cap) and csrc/attn_f32.hip carry it in instantiations of their own; it composes with the key-padding mask,
+``causal``, ``window`` and dropout.  With a bias LUT, segments, global keys or block lists, and bf16 at head dim 32,
+a capped call takes the composite.
 """
 from __future__ import annotations
 
@@ -355,7 +361,18 @@ def _check_segments(q_seg, k_seg, B, Sq, Sk, window) -> None:
             raise ValueError(f"attention: {name} must be [B, S] = [{B}, {S}], got {tuple(sg.ids.shape)}")
 
 
-def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None, q_seg=None, k_seg=None, gk=None, bl=None):
+def _check_softcap(softcap) -> float | None:
+    """A soft cap is a finite positive number, or None (no cap)."""
+    if softcap is None:
+        return None
+    c = float(softcap)
+    if not (c > 0.0 and math.isfinite(c)):
+        raise ValueError(f"attention: softcap must be a finite number > 0 or None, got {softcap}")
+    return c
+
+
+def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None, q_seg=None, k_seg=None, gk=None, bl=None,
+               softcap=None):
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     gk = global_keys(gk)
@@ -364,6 +381,9 @@ def _reference(q, k, v, scale, causal, kpm, lut, p, seed, window=None, q_seg=Non
     kf = k.float().permute(0, 2, 1, 3)
     vf = v.float().permute(0, 2, 1, 3)
     s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
+    softcap = _check_softcap(softcap)
+    if softcap is not None:  # before the bias and every mask
+        s = softcap * torch.tanh(s / softcap)
     if lut is not None:
         rel = torch.arange(Sk, device=q.device)[None, :] - torch.arange(Sq, device=q.device)[:, None] + (Sq - 1)
         s = s + lut.float()[:, rel].unsqueeze(0)
@@ -426,10 +446,16 @@ def _split(mode, a, b, c):
     return a, b, c
 
 
-def _tuned(q, window=None, seg=None, bl=None) -> bool:
-    """csrc/attn.hip serves the call (bf16, head dim 64, no window, no segments, no block lists); else csrc/attn_f32.hip
-    (fp32) or csrc/attn_hd.hip (bf16)."""
-    return q.dtype != torch.float32 and q.shape[-1] == 64 and window is None and seg is None and bl is None
+def _tuned(q, window=None, seg=None, bl=None, softcap=None) -> bool:
+    """csrc/attn.hip serves the call (bf16, head dim 64, no window, no segments, no block lists, no soft cap); else
+    csrc/attn_f32.hip (fp32) or csrc/attn_hd.hip (bf16)."""
+    return (q.dtype != torch.float32 and q.shape[-1] == 64 and window is None and seg is None and bl is None
+            and softcap is None)
+
+
+def _cap_args(softcap) -> dict:
+    """The soft-cap keyword argument of attn_hd_* / attn_f32_* (csrc/bind_attn.cpp), or nothing."""
+    return {} if softcap is None else {"softcap": float(softcap)}
 
 
 def _seg_args(q_seg, k_seg) -> tuple:
@@ -454,13 +480,13 @@ class _AttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mode, a, b, c, lut, kpm, scale, causal, p, seed, window=None, q_seg=None, k_seg=None, gk=None,
-                bl=None):
+                bl=None, softcap=None):
         C = _ext.native()
         q, k, v = _split(mode, a, b, c)
         args = (q, k, v, kpm, lut, float(scale), bool(causal), float(p), int(seed))
         sat_lo = sat_hi = -1
         dmask = None
-        if _tuned(q, window, q_seg, bl):
+        if _tuned(q, window, q_seg, bl, softcap):
             # saturated bias tiles add a scalar instead of reading the LUT (forward -2 %)
             sat = getattr(lut, "_dllm_sat", None) if lut is not None else None
             sat_lo, sat_hi = sat if sat is not None else (-1, -1)
@@ -468,17 +494,18 @@ class _AttnFn(torch.autograd.Function):
         else:
             o, lse = (C.attn_f32_fwd if q.dtype == torch.float32 else C.attn_hd_fwd)(
                 *args, -1 if window is None else int(window), *_seg_args(q_seg, k_seg), **_glob_args(gk),
-                **_list_args(bl, q, k))
+                **_list_args(bl, q, k), **_cap_args(softcap))
         ctx.save_for_backward(a, b, c, o, lse, lut, kpm, dmask)
         ctx.cfg = (mode, scale, causal, p, seed, lut is not None and lut.requires_grad, sat_lo, sat_hi, window)
         ctx.seg = (q_seg, k_seg)  # plain int tensors, no graph: kept as they are
         ctx.gk = gk
         ctx.bl = bl
+        ctx.softcap = softcap
         # packed inputs straight from a biased projection (ops/linear.py marks its output): the backward kernels also
         # sum dQ / dK / dV over tokens for that projection's bias gradient (colsum_record).  csrc/attn.hip only (the
         # partials hard-code H * 64) and bias-LUT-free calls only (its column-sum variants exist for those); everything
         # else takes the separate reduction, as with BIAS_COLSUM = False
-        cs_ok = BIAS_COLSUM and lut is None and _tuned(q, window, q_seg, bl)
+        cs_ok = BIAS_COLSUM and lut is None and _tuned(q, window, q_seg, bl, softcap)
         ctx.cs = (cs_ok and mode != "sep" and _bias_out(a), cs_ok and mode == "q_kv" and _bias_out(b))
         # ops/linear.py stacked_linear: the packed kv is a slice of a multi-layer projection and its
         # gradient has a home in the stacked gradient buffer — write dK/dV there directly
@@ -520,12 +547,12 @@ class _AttnFn(torch.autograd.Function):
                     csk, csv = pkv[:, :HD], pkv[:, HD:]
         args = (do.contiguous(), q, k, v, o, lse, kpm, lut, float(scale), bool(causal), float(p), int(seed),
                 bool(need_dlut), dq, dk, dv)
-        if _tuned(q, window, ctx.seg[0], ctx.bl):
+        if _tuned(q, window, ctx.seg[0], ctx.bl, ctx.softcap):
             rq, rk, rv, dlut = C.attn_bwd(*args, dmask, sat_lo, sat_hi, csq, csk, csv)
         else:
             rq, rk, rv, dlut = (C.attn_f32_bwd if q.dtype == torch.float32 else C.attn_hd_bwd)(
                 *args, -1 if window is None else int(window), *_seg_args(*ctx.seg), **_glob_args(ctx.gk),
-                **_list_args(ctx.bl, q, k))
+                **_list_args(ctx.bl, q, k), **_cap_args(ctx.softcap))
         if part is not None:  # per-block partials, reduced by the consumer into the bias gradient (ops/gemm.py)
             colsum_record(da, part)
         if pq is not None:
@@ -536,7 +563,7 @@ class _AttnFn(torch.autograd.Function):
             da, db, dc = rq, rk, rv
         streams.pair_join()  # side-stream weight gradients paired with these VALU-bound kernels (ops/streams.py)
         return (None, da, db, dc, (dlut if need_dlut else None), None, None, None, None, None, None, None, None, None,
-                None)
+                None, None)
 
 
 # False: the projections' bias gradients from a separate column reduction of dQKV (tests flip the module attribute)
@@ -581,7 +608,7 @@ def _aligned(t) -> bool:
     return t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
 
 
-def _route(t, *rest, window=None, seg=False, glob=False, lists=None):
+def _route(t, *rest, window=None, seg=False, glob=False, lists=None, softcap=None, lut=False):
     """Which kernel family serves a call whose q (or packed qkv) is ``t`` — by ops/routing.py ``attention_route``:
 
     * ``"attn.hip"``: bf16, head dim 64, no ``window`` (csrc/attn.hip, the tuned kernels);
@@ -593,7 +620,11 @@ def _route(t, *rest, window=None, seg=False, glob=False, lists=None):
       sends it to the composite, A/B);
     * ``None``: the composite ``_reference``, the exact-math oracle the kernels are tested against: CPU tensors,
       ``DLLM_REFERENCE_OPS=1``, head dims below 32, above 128 or not a multiple of 8, fp32 at head dims other than 64,
-      other dtypes.  On a GPU tensor that is logged once per reason."""
+      other dtypes.  On a GPU tensor that is logged once per reason.
+
+    ``softcap``: a capped bf16 call at head dim 64 runs csrc/attn_hd.hip (csrc/attn.hip has no cap); the kernels have
+    no cap together with a bias LUT (``lut``), segments, global keys or block lists, nor at bf16 head dim 32: those
+    take the composite."""
     if not _ext.use_native(t):
         return None
     D = t.shape[-1]
@@ -601,6 +632,15 @@ def _route(t, *rest, window=None, seg=False, glob=False, lists=None):
     if not bf16 and t.dtype != torch.float32:
         _warn_composite("this dtype", t)
         return None
+    if softcap is not None:
+        other = ("a bias LUT" if lut else "segments" if seg else "global keys" if glob else
+                 "block lists" if lists is not None else None)
+        if other is not None:
+            _warn_composite(f"a soft cap with {other}", t)
+            return None
+        if bf16 and D == 32:  # csrc/attn_hd.hip keeps its head dim 32 kernels the code they are
+            _warn_composite("a soft cap at head dim 32", t)
+            return None
     if glob and bf16 and D == 32:  # csrc/attn_hd.hip serves no global keys at head dim 32 (its header says why)
         _warn_composite("global keys at head dim 32", t)
         return None
@@ -613,7 +653,7 @@ def _route(t, *rest, window=None, seg=False, glob=False, lists=None):
         if bf16 and D == 32:  # csrc/attn_hd.hip serves no block lists at head dim 32 (its header says why)
             _warn_composite("block lists at head dim 32", t)
             return None
-    r = routing.attention_route(D, bf16, window, segments=seg, lists=lists is not None)
+    r = routing.attention_route(D, bf16, window, segments=seg, lists=lists is not None, softcap=softcap is not None)
     if r == "attn_hd.hip" and not all(_aligned(x) for x in (t,) + rest if x is not None):
         _warn_composite("unaligned rows", t)
         return None
@@ -626,8 +666,8 @@ def _route(t, *rest, window=None, seg=False, glob=False, lists=None):
     return r
 
 
-def _native(t, *rest, window=None, seg=False, glob=False, lists=None) -> bool:
-    return _route(t, *rest, window=window, seg=seg, glob=glob, lists=lists) is not None
+def _native(t, *rest, window=None, seg=False, glob=False, lists=None, softcap=None, lut=False) -> bool:
+    return _route(t, *rest, window=window, seg=seg, glob=glob, lists=lists, softcap=softcap, lut=lut) is not None
 
 
 def _on(sg, t):
@@ -645,7 +685,7 @@ _block_lists = block_lists
 
 def attention(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_mask=None, bias_lut=None,
               dropout_p: float = 0.0, seed: int = 0, window: int | None = None, q_segments=None, k_segments=None,
-              global_keys=None, block_lists=None):
+              global_keys=None, block_lists=None, softcap: float | None = None):
     """Multi-head attention.  q ``[B,Sq,H,D]``, k/v ``[B,Sk,H,D]``; ``key_padding_mask`` bool
     ``[B,Sk]`` (True = attend); ``bias_lut`` from :func:`relative_bias_lut`; ``window``: keys with
     ``|j - i| > window`` are masked (needs ``Sq == Sk`` and ``causal=False``; None: full attention);
@@ -654,7 +694,9 @@ def attention(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_
     (nonzero = global) or :class:`GlobalKeys` (needs ``window``; not with ``causal`` or segments): such a key is
     visible to every query, inside its window or not; ``block_lists``: a :class:`BlockLists` (or what
     :func:`block_lists` takes; not with ``causal``, ``window``, segments or global keys): a key counts once per
-    occurrence of its block in the list of the query's block."""
+    occurrence of its block in the list of the query's block; ``softcap``: ``c > 0`` caps the scaled scores to
+    ``c * tanh(s / c)`` before the bias and every mask (None: no cap)."""
+    softcap = _check_softcap(softcap)
     if window is not None:
         _check_window(window, q.shape[1], k.shape[1], causal)
     qs, ks = segments(q_segments), segments(k_segments)
@@ -663,10 +705,12 @@ def attention(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_
     _check_global(gk, q.shape[0], k.shape[1], window, causal, qs)
     bl = _block_lists(block_lists)
     _check_lists(bl, q.shape[2], q.shape[1], k.shape[1], window, causal, qs, gk)
-    if _native(q, k, v, window=window, seg=qs is not None, glob=gk is not None, lists=bl):
+    if _native(q, k, v, window=window, seg=qs is not None, glob=gk is not None, lists=bl, softcap=softcap,
+               lut=bias_lut is not None):
         return _AttnFn.apply("sep", q, k, v, bias_lut, _prep_kpm(key_padding_mask), scale, causal, dropout_p, seed,
-                             window, _on(qs, q), _on(ks, q), _on(gk, q), bl)
-    return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed, window, qs, ks, gk, bl)
+                             window, _on(qs, q), _on(ks, q), _on(gk, q), bl, softcap)
+    return _reference(q, k, v, scale, causal, key_padding_mask, bias_lut, dropout_p, seed, window, qs, ks, gk, bl,
+                      softcap)
 
 
 def attention_qkv(qkv, **kw):
@@ -683,10 +727,12 @@ def attention_qkv(qkv, **kw):
     _check_global(gk, qkv.shape[0], qkv.shape[1], window, kw.get("causal", False), qs)
     bl = kw["block_lists"] = _block_lists(kw.get("block_lists"))
     _check_lists(bl, qkv.shape[3], qkv.shape[1], qkv.shape[1], window, kw.get("causal", False), qs, gk)
-    if _native(qkv, window=window, seg=qs is not None, glob=gk is not None, lists=bl):
+    cap = kw["softcap"] = _check_softcap(kw.get("softcap"))
+    if _native(qkv, window=window, seg=qs is not None, glob=gk is not None, lists=bl, softcap=cap,
+               lut=kw.get("bias_lut") is not None):
         return _AttnFn.apply("qkv", qkv, None, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
                              kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
-                             window, _on(qs, qkv), _on(ks, qkv), _on(gk, qkv), bl)
+                             window, _on(qs, qkv), _on(ks, qkv), _on(gk, qkv), bl, cap)
     return attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], **kw)
 
 
@@ -705,8 +751,10 @@ def attention_q_kv(q, kv, **kw):
     _check_lists(bl, q.shape[2], q.shape[1], kv.shape[1], window, kw.get("causal", False), qs, gk)
     if bl is not None:
         kw = dict(kw, block_lists=bl)
-    if _native(q, kv, window=window, seg=qs is not None, glob=gk is not None, lists=bl):
+    cap = _check_softcap(kw.get("softcap"))
+    if _native(q, kv, window=window, seg=qs is not None, glob=gk is not None, lists=bl, softcap=cap,
+               lut=kw.get("bias_lut") is not None):
         return _AttnFn.apply("q_kv", q, kv, None, kw.get("bias_lut"), _prep_kpm(kw.get("key_padding_mask")),
                              kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
-                             window, _on(qs, q), _on(ks, q), _on(gk, q), bl)
+                             window, _on(qs, q), _on(ks, q), _on(gk, q), bl, cap)
     return attention(q, kv[:, :, 0], kv[:, :, 1], **kw)

@@ -30,6 +30,10 @@ GEMM-fused variant (``_LMHeadCEFusedFn``, the no-materialised-logits path unless
   never written, not even in bf16 — and csrc/ce.hip ``ce_merge`` folds the ``[N, V/128]`` partials into loss and lse;
 * backward: per vocabulary chunk the GEMM recomputes the logits and its epilogue writes ``g·(softmax - target)`` as
   bf16 dlogits directly (no logits round trip, no separate CE pass), then the input- and weight-gradient GEMMs.
+
+Soft cap (``softcap=c``, Gemma 2 / T5Gemma ``final_logit_softcapping``): the loss of ``c * tanh(logits / c)``.  The
+vocabulary-chunked kernels apply it in their pass (csrc/ce.hip); the GEMM epilogues have no cap, so ``fused_ok`` is
+false with one and the call takes the chunked path.
 """
 from __future__ import annotations
 
@@ -84,10 +88,12 @@ def wants_lm_head_loss(hidden: torch.Tensor, N: int, V: int) -> bool:
             and hidden.shape[-1] % 64 == 0 and _ext.use_native(hidden))
 
 
-def _reference(h, w, labels, bias, smoothing, ignore_index):
+def _reference(h, w, labels, bias, smoothing, ignore_index, softcap=None):
     logits = F.linear(h.float(), w.float())
     if bias is not None:
         logits = logits + bias.float()
+    if softcap is not None:
+        logits = softcap * torch.tanh(logits / softcap)
     return F.cross_entropy(logits, labels, ignore_index=ignore_index, label_smoothing=smoothing)
 
 
@@ -111,8 +117,9 @@ def _dh_accumulate(dh: torch.Tensor, g: torch.Tensor, wc: torch.Tensor) -> None:
 
 class _LMHeadCEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h, w, bias, labels, smoothing, ignore_index, params):
+    def forward(ctx, h, w, bias, labels, smoothing, ignore_index, params, softcap=None):
         C = _ext.native()
+        cap = ctx.cap = {} if softcap is None else {"softcap": float(softcap)}
         N, d = h.shape
         V = w.shape[0]
         vc = _chunk_cols(N, V)
@@ -126,7 +133,7 @@ class _LMHeadCEFn(torch.autograd.Function):
             lg = buf[:N * n].view(N, n)
             _logits(h, w[c0:c0 + n], lg)
             C.ce_chunk_fwd(lg, labels, bias32, state, loss_rows, lse, c0, V, float(smoothing), int(ignore_index),
-                           j == 0, j + 1 == len(chunks), skip)
+                           j == 0, j + 1 == len(chunks), skip, **cap)
         count = (labels != ignore_index).sum().clamp_min(1).to(torch.float32)
         ctx.save_for_backward(h, w, labels, lse, count)
         ctx.bias32 = bias32
@@ -153,7 +160,8 @@ class _LMHeadCEFn(torch.autograd.Function):
             lg = buf[:N * n].view(N, n)
             wc = w[c0:c0 + n]
             _logits(h, wc, lg)
-            C.ce_chunk_bwd(scale, lg, labels, lse, ctx.bias32, c0, V, smoothing, ignore_index, skip)  # skipped -> 0
+            C.ce_chunk_bwd(scale, lg, labels, lse, ctx.bias32, c0, V, smoothing, ignore_index, skip,
+                           **ctx.cap)  # skipped -> 0
             _dh_accumulate(dh, lg, wc)
             with torch.no_grad():
                 if gw is not None:
@@ -162,7 +170,7 @@ class _LMHeadCEFn(torch.autograd.Function):
                     dw[c0:c0 + n] += torch.mm(lg.t(), h)
         if p is not None:
             _fire(p)
-        return dh.to(h.dtype), (dw.to(w.dtype) if dw is not None else None), None, None, None, None, None
+        return dh.to(h.dtype), (dw.to(w.dtype) if dw is not None else None), None, None, None, None, None, None
 
 
 class _LMHeadCEFusedFn(torch.autograd.Function):
@@ -220,30 +228,35 @@ def use_fused() -> bool:
     return routing.get("lmhead") != "logits"
 
 
-def fused_ok(h: torch.Tensor, w: torch.Tensor) -> bool:
-    """Shapes the GEMM-epilogue CE handles (csrc/bind_gemm.cpp lmhead_params): bf16, d % 64 == 0, 16-B rows."""
-    return (use_fused() and h.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and h.shape[-1] % 64 == 0
+def fused_ok(h: torch.Tensor, w: torch.Tensor, softcap=None) -> bool:
+    """Shapes the GEMM-epilogue CE handles (csrc/bind_gemm.cpp lmhead_params): bf16, d % 64 == 0, 16-B rows, no soft
+    cap (the epilogues have none)."""
+    return (softcap is None and use_fused() and h.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and h.shape[-1] % 64 == 0
             and w.stride(-1) == 1 and w.stride(0) % 8 == 0 and w.data_ptr() % 16 == 0 and h.data_ptr() % 16 == 0
             and _ext.use_native(h))
 
 
 def lm_head_loss(hidden: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor, *, scale: float | None = None,
-                 bias: torch.Tensor | None = None, label_smoothing: float = 0.0, ignore_index: int = -100):
+                 bias: torch.Tensor | None = None, label_smoothing: float = 0.0, ignore_index: int = -100,
+                 softcap: float | None = None):
     """Mean (label-smoothed) CE of ``(hidden * scale) @ weightᵀ (+ bias)`` against ``labels`` over non-ignored rows,
-    computed in vocabulary chunks (module docstring).  ``hidden [..., d]``, ``labels [...]``."""
+    computed in vocabulary chunks (module docstring).  ``hidden [..., d]``, ``labels [...]``; ``softcap``: the loss of
+    ``c * tanh(logits / c)`` (None: no cap)."""
+    from .cross_entropy import _check_softcap
+    softcap = _check_softcap(softcap)
     d = hidden.shape[-1]
     h = hidden.reshape(-1, d)
     if scale is not None:
         h = h * scale
     lab = labels.reshape(-1)
     if not _ext.use_native(h) or h.dtype != torch.bfloat16:  # the chunk kernels take bf16 logits; fp32: composite
-        return _reference(h, weight, lab, bias, label_smoothing, ignore_index)
+        return _reference(h, weight, lab, bias, label_smoothing, ignore_index, softcap)
     params = None
     w = weight
     if torch.is_grad_enabled() and _fusable(weight) and weight.requires_grad:
         params = (weight,)
         w = weight.detach()
     h = h.contiguous()
-    if fused_ok(h, w):
+    if fused_ok(h, w, softcap):
         return _LMHeadCEFusedFn.apply(h, w, bias, lab.contiguous(), label_smoothing, ignore_index, params)
-    return _LMHeadCEFn.apply(h, w, bias, lab.contiguous(), label_smoothing, ignore_index, params)
+    return _LMHeadCEFn.apply(h, w, bias, lab.contiguous(), label_smoothing, ignore_index, params, softcap)

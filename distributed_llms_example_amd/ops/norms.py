@@ -7,6 +7,10 @@ BART is post-norm with a biased LayerNorm (modeling_bart.py:280-308):
 ``LN(residual + dropout(sublayer))`` is one kernel.  Backward regenerates the dropout mask from
 the counter-based seed (ops/rng.py), so no mask is stored.
 
+``offset`` (the RMSNorm entry points): the kernels and the reference scale by ``weight + offset`` — Gemma stores its
+norm weights zero-centred and applies ``1 + w`` (``offset=1.0``).  The weight gradient is that of the stored parameter
+either way, so it still accumulates straight into its flat gradient.
+
 Kernels: csrc/norm.hip (``norm_fwd`` / ``norm_bwd``).  On CPU (or with DLLM_REFERENCE_OPS=1)
 the functions below run the plain-torch reference, which is also the test oracle.
 """
@@ -24,7 +28,7 @@ from .rng import keep_mask
 RMS, LAYER = 0, 1
 
 
-def _reference(x, resid, weight, bias, eps, p, seed, kind):
+def _reference(x, resid, weight, bias, eps, p, seed, kind, offset=0.0):
     xf = x.float()
     if p > 0.0:
         xf = xf * keep_mask(seed, p, x.shape, x.device).to(xf.dtype) * (1.0 / (1.0 - p))
@@ -33,7 +37,7 @@ def _reference(x, resid, weight, bias, eps, p, seed, kind):
     sf = s.float()
     if kind == RMS:
         rstd = torch.rsqrt(sf.pow(2).mean(-1, keepdim=True) + eps)
-        out = sf * rstd * weight.float()
+        out = sf * rstd * (weight.float() + offset if offset else weight.float())
     else:
         mean = sf.mean(-1, keepdim=True)
         var = (sf - mean).pow(2).mean(-1, keepdim=True)
@@ -47,7 +51,7 @@ class _NormFn(torch.autograd.Function):
     """out = norm(s) with s = (resid +) dropout(x); returns (out, s)."""
 
     @staticmethod
-    def forward(ctx, x, resid, weight, bias, eps, p, seed, kind, params=None, colsum=False):
+    def forward(ctx, x, resid, weight, bias, eps, p, seed, kind, params=None, colsum=False, offset=0.0):
         C = _ext.native()
         ctx.params = params
         ctx.colsum = colsum
@@ -57,9 +61,11 @@ class _NormFn(torch.autograd.Function):
         d = shape[-1]
         x2 = x.reshape(-1, d)
         r2 = resid.reshape(-1, d) if resid is not None else None
-        out, s, mean, rstd = C.norm_fwd(x2, r2, weight, bias, float(eps), float(p), int(seed), int(kind), True)
+        out, s, mean, rstd = C.norm_fwd(x2, r2, weight, bias, float(eps), float(p), int(seed), int(kind), True,
+                                        *_off_args(offset))
         ctx.save_for_backward(s, weight, bias, mean, rstd)
         ctx.cfg = (p, seed, kind, resid is not None, shape)
+        ctx.offset = offset
         ctx.set_materialize_grads(False)
         return out.view(shape), s.view(shape)
 
@@ -75,7 +81,7 @@ class _NormFn(torch.autograd.Function):
         dfr = gemm.deferring() if ctx.params is not None else None
         dx, dstream, dw, db, dxs = C.norm_bwd(dout2, ds2, s, weight, bias, mean, rstd, float(p), int(seed), int(kind),
                                               want_stream, *_acc_targets(ctx.params), want_colsum=ctx.colsum,
-                                              partials_only=dfr is not None)
+                                              partials_only=dfr is not None, **_off_kw(ctx.offset))
         if dfr is not None:  # deferred window: the weight / bias gradient partials are reduced once per window
             _defer_partials(dfr, ctx.params, dw, db)
             dw = db = None
@@ -89,23 +95,24 @@ class _NormFn(torch.autograd.Function):
         if has_resid:
             dres = dstream.view(shape) if want_stream else dx
         streams.pair_join()  # side-stream weight gradients paired with this memory-bound kernel (ops/streams.py)
-        return (dx, dres) + _param_grads(ctx.params, weight, bias, dw, db) + (None, None, None, None, None, None)
+        return (dx, dres) + _param_grads(ctx.params, weight, bias, dw, db) + (None, None, None, None, None, None, None)
 
 
 class _NormOnlyFn(torch.autograd.Function):
     """out = norm(x) (no residual, no dropout)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps, kind, params=None):
+    def forward(ctx, x, weight, bias, eps, kind, params=None, offset=0.0):
         C = _ext.native()
         ctx.params = params
         for q in params or ():
             _use(q)
         shape = x.shape
         x2 = x.reshape(-1, shape[-1])
-        out, _, mean, rstd = C.norm_fwd(x2, None, weight, bias, float(eps), 0.0, 0, int(kind), False)
+        out, _, mean, rstd = C.norm_fwd(x2, None, weight, bias, float(eps), 0.0, 0, int(kind), False, *_off_args(offset))
         ctx.save_for_backward(x2, weight, bias, mean, rstd)
         ctx.cfg = (kind, shape)
+        ctx.offset = offset
         return out.view(shape)
 
     @staticmethod
@@ -114,9 +121,19 @@ class _NormOnlyFn(torch.autograd.Function):
         x2, weight, bias, mean, rstd = ctx.saved_tensors
         kind, shape = ctx.cfg
         dx, _, dw, db, _ = C.norm_bwd(dout.reshape(-1, shape[-1]), None, x2, weight, bias, mean, rstd, 0.0, 0,
-                                      int(kind), False, *_acc_targets(ctx.params))
+                                      int(kind), False, *_acc_targets(ctx.params), **_off_kw(ctx.offset))
         streams.pair_join()
-        return (dx.view(shape),) + _param_grads(ctx.params, weight, bias, dw, db) + (None, None, None)
+        return (dx.view(shape),) + _param_grads(ctx.params, weight, bias, dw, db) + (None, None, None, None)
+
+
+def _off_args(offset) -> tuple:
+    """The trailing ``w_offset`` argument of ``norm_fwd`` (csrc/bind_rowwise.cpp), or nothing: a call without an offset
+    is the call it was."""
+    return (float(offset),) if offset else ()
+
+
+def _off_kw(offset) -> dict:
+    return {"w_offset": float(offset)} if offset else {}
 
 
 def _defer_partials(dfr, params, dw_part, db_part):
@@ -148,7 +165,7 @@ def _param_grads(params, weight, bias, dw, db):
     return dw.to(weight.dtype), (db.to(bias.dtype) if db is not None else None)
 
 
-def _norm(x, resid, weight, bias, eps, p, seed, kind, colsum=False):
+def _norm(x, resid, weight, bias, eps, p, seed, kind, colsum=False, offset=0.0):
     if _ext.use_native(x):
         params = None
         if torch.is_grad_enabled() and _fusable(weight) and _fusable(bias):
@@ -156,27 +173,27 @@ def _norm(x, resid, weight, bias, eps, p, seed, kind, colsum=False):
             weight = weight.detach()
             bias = bias.detach() if bias is not None else None
         if resid is None and p == 0.0:
-            return _NormOnlyFn.apply(x, weight, bias, eps, kind, params), x
-        return _NormFn.apply(x, resid, weight, bias, eps, p, seed, kind, params, colsum and x.requires_grad)
-    return _reference(x, resid, weight, bias, eps, p, seed, kind)
+            return _NormOnlyFn.apply(x, weight, bias, eps, kind, params, offset), x
+        return _NormFn.apply(x, resid, weight, bias, eps, p, seed, kind, params, colsum and x.requires_grad, offset)
+    return _reference(x, resid, weight, bias, eps, p, seed, kind, offset)
 
 
-def rms_norm(x, weight, eps=1e-6):
-    return _norm(x, None, weight, None, eps, 0.0, 0, RMS)[0]
+def rms_norm(x, weight, eps=1e-6, offset: float = 0.0):
+    return _norm(x, None, weight, None, eps, 0.0, 0, RMS, offset=offset)[0]
 
 
 def layer_norm(x, weight, bias, eps=1e-5):
     return _norm(x, None, weight, bias, eps, 0.0, 0, LAYER)[0]
 
 
-def dropout_rms_norm(x, weight, eps, p, seed):
+def dropout_rms_norm(x, weight, eps, p, seed, offset: float = 0.0):
     """(rms(s)*w, s) with s = dropout(x): T5 embedding dropout fused with block 0's first norm."""
-    return _norm(x, None, weight, None, eps, p, seed, RMS)
+    return _norm(x, None, weight, None, eps, p, seed, RMS, offset=offset)
 
 
-def add_dropout_rms_norm(resid, x, weight, eps, p, seed):
+def add_dropout_rms_norm(resid, x, weight, eps, p, seed, offset: float = 0.0):
     """(rms(s)*w, s) with s = resid + dropout(x): T5 residual update fused with the next norm."""
-    return _norm(x, resid, weight, None, eps, p, seed, RMS)
+    return _norm(x, resid, weight, None, eps, p, seed, RMS, offset=offset)
 
 
 def add_dropout_layer_norm(resid, x, weight, bias, eps, p, seed, x_bias_grad=False):

@@ -148,7 +148,9 @@ class FusedAdafactor:
     Semantics = ``transformers.optimization.Adafactor`` with ``beta1=None``, preceded by the same global-norm clip as
     :class:`FusedAdamW`.  Every formula applies per UNIT: one transformers parameter.  Our parameters are
     concatenations of transformers' along dim 0 (``qkv``, ``kv``, gated ``wi``, BART's fused projections and their 1-D
-    biases), so ``parts(name)`` says into how many equal dim-0 slices a flat segment splits; each slice has its own
+    biases), so ``parts(name)`` says into how many equal dim-0 slices a flat segment splits — or, where the slices
+    differ (T5Gemma's qkv with grouped K/V heads: q, then the shorter k and v), their dim-0 sizes in order; each slice
+    has its own
     ``C``, its own ``mean(R)``, its own ``rms(u)`` clip and its own ``rms(w)``.  State per unit: ``R[rows]`` and
     ``C[cols]`` for matrices, ``V[numel]`` for 1-D tensors, kept in canonical unit order in ``self.rv`` / ``self.c`` —
     not flat-indexed, so a relayout of the flat buffers moves nothing in them; only the device unit table
@@ -189,16 +191,28 @@ class FusedAdafactor:
         self.units: list[dict] = []  # canonical order: segments as constructed, their slices in order
         rv_off = c_off = 0
         for name in flat.canonical:
-            shape, k = shape_of[name], int(parts(name))
+            shape, k = shape_of[name], parts(name)
             if len(shape) > 2 or len(shape) == 0:
                 raise NotImplementedError(f"FusedAdafactor: parameter {name} has {len(shape)} dims (1 or 2 are served)")
-            if k < 1 or shape[0] % k:
-                raise ValueError(f"FusedAdafactor: {name} {tuple(shape)} does not split into {k} equal dim-0 slices")
-            rows, cols = (shape[0] // k, shape[1]) if len(shape) == 2 else (1, shape[0] // k)
+            if isinstance(k, (list, tuple)):  # the slices' dim-0 sizes
+                sizes = [int(x) for x in k]
+                if not sizes or min(sizes) < 1 or sum(sizes) != shape[0]:
+                    raise ValueError(f"FusedAdafactor: {name} {tuple(shape)} does not split into dim-0 slices of "
+                                     f"{sizes}")
+            else:
+                k = int(k)
+                if k < 1 or shape[0] % k:
+                    raise ValueError(f"FusedAdafactor: {name} {tuple(shape)} does not split into {k} equal dim-0 "
+                                     "slices")
+                sizes = [shape[0] // k] * k
             decay = self.weight_decay != 0.0 and not (no_decay is not None and no_decay(name))
-            for j in range(k):
+            first = 0  # the slice's first dim-0 index
+            for j, size in enumerate(sizes):
+                rows, cols = (size, shape[1]) if len(shape) == 2 else (1, size)
                 u = {"name": name, "part": j, "rows": rows, "cols": cols, "factored": len(shape) == 2, "rv": rv_off,
-                     "c": c_off if len(shape) == 2 else -1, "decay": decay}
+                     "c": c_off if len(shape) == 2 else -1, "decay": decay,
+                     "start": first * (shape[1] if len(shape) == 2 else 1)}  # element offset inside the segment
+                first += size
                 self.units.append(u)
                 # 4-element aligned so the kernels may use 16-byte access on the state
                 rv_off += ((rows if u["factored"] else cols) + 3) // 4 * 4
@@ -232,7 +246,7 @@ class FusedAdafactor:
     def _offsets(self) -> list[int]:
         """Flat element offset of every unit under the current layout."""
         seg = {s.name: s.offset for s in self.flat.segments}
-        return [seg[u["name"]] + u["part"] * u["rows"] * u["cols"] for u in self.units]
+        return [seg[u["name"]] + u["start"] for u in self.units]
 
     def _rel(self, t: int, lr: float) -> float:
         if not self.relative_step:

@@ -71,6 +71,11 @@ block-list attention           as the window (same route; bf16 head dim 32 and b
                                follow each query block's list of 64-key blocks, dK / dV
                                its transpose; a block listed n times counts n times; the
                                rest is never loaded (``attn_lists`` = 1; 0: the composite)
+soft-capped attention          as the window (same route; bf16 head dim 32, and a cap with    attn_softcap.txt
+(T5Gemma)                      a bias LUT, segments, global keys or lists: composite):
+                               c·tanh(s / c) per score in instantiations of their own in
+                               csrc/attn_hd.hip and csrc/attn_f32.hip; csrc/attn.hip has
+                               no cap
 segment-masked attention       as the window: bf16 (head dim 64 included) on                 attn_segments_vs_masked.txt
 (sequence packing)             csrc/attn_hd.hip, fp32 at head dim 64 on csrc/attn_f32.hip;
                                blocks of other segments are skipped by per-block (min,
@@ -210,7 +215,7 @@ def get(key: str):
 
 
 def attention_route(head_dim: int, bf16: bool = True, window: int | None = None, *,
-                    segments: bool = False, lists: bool = False) -> str:
+                    segments: bool = False, lists: bool = False, softcap: bool = False) -> str:
     """Kernel family of an attention call on the GPU by head dim and dtype (bf16, else fp32): ``"attn.hip"``,
     ``"attn_hd.hip"``, ``"attn_f32.hip"`` or ``"composite"`` — the rule ops/attention.py ``_route`` applies.
     ``window``: the call's sliding window (None: full attention).  csrc/attn.hip has no window, so a windowed bf16
@@ -219,10 +224,15 @@ def attention_route(head_dim: int, bf16: bool = True, window: int | None = None,
     A windowed call with global keys (LED) routes as the windowed call, except bf16 at head dim 32, where
     csrc/attn_hd.hip serves no global keys and ops/attention.py ``_route`` takes the composite.  ``lists``: the call
     carries block lists (BigBird); it routes as a call with segments, with the same exception at head dim 32 and
-    ``attn_lists`` = 0 sending it to the composite."""
+    ``attn_lists`` = 0 sending it to the composite.  ``softcap``: the call caps its scores (Gemma 2 / T5Gemma);
+    csrc/attn.hip has no cap, so it routes as a windowed call does — bf16 at head dim 32 excepted, where
+    csrc/attn_hd.hip has none either (composite); a cap with a bias LUT, segments, global keys or lists is the
+    composite's (ops/attention.py ``_route``)."""
     if lists and not get("attn_lists"):
         return "composite"
-    if head_dim == 64 and (window is None and not segments and not lists or not bf16):
+    if softcap and (segments or lists or bf16 and head_dim == 32):
+        return "composite"
+    if head_dim == 64 and (window is None and not segments and not lists and not softcap or not bf16):
         return "attn.hip" if bf16 else ("attn_f32.hip" if get("attn_f32") else "composite")
     if bf16 and 32 <= head_dim <= 128 and head_dim % 8 == 0 and get("attn_hd"):
         return "attn_hd.hip"

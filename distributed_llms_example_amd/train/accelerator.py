@@ -214,13 +214,13 @@ class Accelerator:
         no_decay_names = {names[id(p)] for p in flat.params if decay_of.get(id(p), 0.0) == 0.0}
         no_decay = (lambda n: n in no_decay_names) if wd else None
         if type(opt).__name__ == "Adafactor" and "clip_threshold" in g0:  # transformers.optimization.Adafactor
-            from ..models.hf_io import hf_param_names
+            from ..models.hf_io import hf_param_parts
             cfg = getattr(self._model.module, "config", None)
             fused = FusedAdafactor(flat, lr=g0["lr"], eps=g0["eps"], clip_threshold=g0["clip_threshold"],
                                    decay_rate=g0["decay_rate"], beta1=g0["beta1"], weight_decay=wd,
                                    scale_parameter=g0["scale_parameter"], relative_step=g0["relative_step"],
                                    warmup_init=g0["warmup_init"], no_decay=no_decay,
-                                   parts=(lambda n: len(hf_param_names(cfg, n))) if cfg is not None else None)
+                                   parts=(lambda n: hf_param_parts(cfg, n)) if cfg is not None else None)
         else:
             fused = FusedAdamW(flat, lr=g0["lr"], betas=g0.get("betas", (0.9, 0.999)), eps=g0.get("eps", 1e-8),
                                weight_decay=wd, no_decay=no_decay)

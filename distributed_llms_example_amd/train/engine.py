@@ -85,11 +85,11 @@ class TrainEngine:
             self.optimizer = FusedAdamW(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                         no_decay=no_decay)
         elif optim == "adafactor":
-            from ..models.hf_io import hf_param_names
+            from ..models.hf_io import hf_param_parts
             cfg = getattr(self.model, "config", None)
             self.optimizer = FusedAdafactor(self.flat, lr=lr, weight_decay=weight_decay, scale_parameter=False,
                                             relative_step=False, no_decay=no_decay,
-                                            parts=(lambda n: len(hf_param_names(cfg, n))) if cfg is not None else None)
+                                            parts=(lambda n: hf_param_parts(cfg, n)) if cfg is not None else None)
         else:
             raise ValueError(f"optim must be 'adamw' or 'adafactor', got {optim!r}")
         self.max_grad_norm = max_grad_norm
