@@ -4,6 +4,7 @@
 //   AttnParamsT<float>     AttnF32Params   csrc/attn_f32.hip   fp32, head dim 64
 //   AttnParamsT<uint16_t>  AttnHdParams    csrc/attn_hd.hip    bf16, head dims 32 .. 128 other than 64
 //   AttnParams (+ extras)                  csrc/attn.hip       bf16, head dim 64 (the tuned kernels)
+// and AttnWideParams (at the end of this file) for csrc/attn_wide.hip: bf16, head dims 136 .. 256, grouped K/V heads.
 //
 // Tensors: q, o, dout, dq are [B, Sq, H, D] views and k, v, dk, dv [B, Sk, H, D] views of element type T with the head
 // dim contiguous.  x_sb / x_ss / x_sh are the batch / sequence / head strides IN ELEMENTS, each a multiple of
@@ -149,4 +150,44 @@ struct AttnParams : AttnParamsT<uint16_t> {
   int n_tiles;   // fwd: q tiles; bwd: key blocks
   int n_ktiles;  // 64-key tiles (key-mask array length / 64)
   int sq_pad;    // rows of the dropout bit-mask planes (query tiles x 128)
+};
+
+// The fourth family, with a block of its own: csrc/attn_wide.hip, bf16 at head dims 136 .. 256 (D % 8 == 0, one padded
+// instantiation of 256) with grouped K/V heads.  q, o, dout, dq are [B, Sq, H, D] views and k, v, dk, dv
+// [B, Sk, Hkv, D] views, H % Hkv == 0: query head h reads K/V head h / (H / Hkv), and dk / dv are the sums over the
+// H / Hkv query heads of a group (formed in registers, written once).  Strides, alignment, scale, kpm, causal /
+// causal_off, window, softcap, LSE (log2 units) and the rows without a visible key (output 0, LSE +inf, no gradient)
+// are as above.  It has no bias LUT, segments, global keys, block lists or dropout: the binding refuses each by name.
+struct AttnWideParams {
+  typedef uint16_t elem;
+  const uint16_t* q;
+  const uint16_t* k;
+  const uint16_t* v;
+  const uint16_t* o;     // bwd: forward output (checked by the binding; delta is summed from P and dP, not from it)
+  const uint16_t* dout;  // bwd: output gradient
+  uint16_t* o_out;       // fwd output
+  float* lse;            // [B, H, Sq]
+  float* delta;          // [B, H, Sq]
+  uint16_t* dq;
+  uint16_t* dk;          // [B, Sk, Hkv, D]
+  uint16_t* dv;
+  const uint8_t* kpm;    // [B, Sk] 1 = attend; nullptr: none
+  long q_sb, q_ss, q_sh;
+  long k_sb, k_ss, k_sh;
+  long v_sb, v_ss, v_sh;
+  long o_sb, o_ss, o_sh;  // o and o_out
+  long do_sb, do_ss, do_sh;
+  long dq_sb, dq_ss, dq_sh;
+  long dk_sb, dk_ss, dk_sh;
+  long dv_sb, dv_ss, dv_sh;
+  int B, H, Hkv, Sq, Sk;
+  int D;           // head dim, 136 .. 256
+  float scale;
+  int causal;
+  int causal_off;  // Sk - Sq
+  int window;      // -1: none
+  float softcap;   // 0: none
+  // filled by the launchers
+  int G;           // H / Hkv
+  int gw;          // query heads of a group a forward / dQ workgroup serves at once: 4, 2 or 1
 };

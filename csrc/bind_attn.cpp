@@ -1,4 +1,4 @@
-// Attention (csrc/attn.hip, csrc/attn_f32.hip, csrc/attn_hd.hip).
+// Attention (csrc/attn.hip, csrc/attn_f32.hip, csrc/attn_hd.hip, csrc/attn_wide.hip).
 #include "bind_common.h"
 
 #include <cmath>
@@ -346,6 +346,100 @@ std::vector<Tensor> attn_hd_bwd(const Tensor& dout, const Tensor& q, const Tenso
                         ql_ptr, ql_idx, softcap);
 }
 
+// ---- csrc/attn_wide.hip: head dims 136 .. 256, k / v / dk / dv with Hkv heads.  The argument lists are attn_hd's, so
+// what the family does not serve (a bias LUT, segments, global keys, block lists, dropout) arrives and is refused by name.
+const AttnFamily<AttnWideParams> kAttnWide{at::kBFloat16, "attn_wide kernels take bf16", dllm_attn_wide_fwd,
+                                           dllm_attn_wide_bwd, "attn_wide_fwd", "attn_wide_bwd"};
+
+void fill_wide(AttnWideParams& p, const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
+               const optional<Tensor>& lut, double scale, bool causal, double drop, int64_t window, bool segs, bool glob,
+               bool lists, double softcap) {
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "attn_wide: q / k / v must be [B, S, H, D]");
+  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3), Sk = k.size(1), Hkv = k.size(2);
+  TORCH_CHECK(D > 128 && D <= 256 && D % 8 == 0,
+              "attn_wide: head dim must be in 136 .. 256 and a multiple of 8, got ", D);
+  TORCH_CHECK(Hkv > 0 && H % Hkv == 0, "attn_wide: the ", H, " query heads are no multiple of the ", Hkv, " K/V heads");
+  TORCH_CHECK(!has(lut), "attn_wide: a bias LUT is not served (csrc/attn_wide.hip)");
+  TORCH_CHECK(!segs, "attn_wide: segments are not served (csrc/attn_wide.hip)");
+  TORCH_CHECK(!glob, "attn_wide: global keys are not served (csrc/attn_wide.hip)");
+  TORCH_CHECK(!lists, "attn_wide: block lists are not served (csrc/attn_wide.hip)");
+  TORCH_CHECK(drop == 0.0, "attn_wide: dropout (p > 0) is not served (csrc/attn_wide.hip), got p = ", drop);
+  TORCH_CHECK(softcap >= 0.0 && std::isfinite(softcap), "attention: softcap must be finite and >= 0, got ", softcap);
+  check_bshd(q, q, "q", B, Sq, H, D, kAttnWide);
+  check_bshd(k, q, "k", B, Sk, Hkv, D, kAttnWide);
+  check_bshd(v, q, "v", B, Sk, Hkv, D, kAttnWide);
+  TORCH_CHECK(Sq > 0 && Sk > 0, "empty attention");
+  set_view(q, p.q, p.q_sb, p.q_ss, p.q_sh);
+  set_view(k, p.k, p.k_sb, p.k_ss, p.k_sh);
+  set_view(v, p.v, p.v_sb, p.v_ss, p.v_sh);
+  p.B = B; p.H = H; p.Hkv = Hkv; p.Sq = Sq; p.Sk = Sk; p.D = D;
+  p.scale = (float)scale;
+  p.causal = causal ? 1 : 0;
+  p.causal_off = Sk - Sq;
+  p.window = -1;
+  set_window(p, window);
+  p.softcap = (float)softcap;
+  if (has(kpm))
+    TORCH_CHECK(kpm->dim() == 2 && kpm->size(0) == B && kpm->size(1) == Sk,
+                "key_padding_mask must be uint8 [B, Sk] contiguous on GPU");
+  p.kpm = flat_ptr<const uint8_t>(kpm, q, at::kByte, exactly(B * Sk), "key_padding_mask");
+  check_limits_small(p);
+}
+
+std::vector<Tensor> attn_wide_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
+                                  const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
+                                  int64_t window,
+                                  const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
+                                  const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
+                                  const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
+                                  const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
+                                  const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx, double softcap) {
+  (void)seed;
+  AttnWideParams prm{};
+  fill_wide(prm, q, k, v, kpm, lut, scale, causal, p, window, has(q_seg) || has(k_seg) || has(q_blk) || has(k_blk),
+            has(k_glob) || has(k_gblk), has(kl_ptr) || has(kl_idx) || has(ql_ptr) || has(ql_idx), softcap);
+  auto out = fill_fwd(prm, q);
+  check_rc(kAttnWide.fwd(&prm, stream()), kAttnWide.fwd_name);
+  return out;
+}
+
+std::vector<Tensor> attn_wide_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
+                                  const Tensor& o, const Tensor& lse, const optional<Tensor>& kpm,
+                                  const optional<Tensor>& lut, double scale, bool causal, double p, int64_t seed,
+                                  bool need_dlut, const optional<Tensor>& dq_out, const optional<Tensor>& dk_out,
+                                  const optional<Tensor>& dv_out, int64_t window,
+                                  const optional<Tensor>& q_seg, const optional<Tensor>& k_seg,
+                                  const optional<Tensor>& q_blk, const optional<Tensor>& k_blk,
+                                  const optional<Tensor>& k_glob, const optional<Tensor>& k_gblk,
+                                  const optional<Tensor>& kl_ptr, const optional<Tensor>& kl_idx,
+                                  const optional<Tensor>& ql_ptr, const optional<Tensor>& ql_idx, double softcap) {
+  (void)seed; (void)need_dlut;
+  AttnWideParams prm{};
+  fill_wide(prm, q, k, v, kpm, lut, scale, causal, p, window, has(q_seg) || has(k_seg) || has(q_blk) || has(k_blk),
+            has(k_glob) || has(k_gblk), has(kl_ptr) || has(kl_idx) || has(ql_ptr) || has(ql_idx), softcap);
+  check_bshd(o, q, "o", prm.B, prm.Sq, prm.H, prm.D, kAttnWide);
+  check_bshd(dout, q, "dout", prm.B, prm.Sq, prm.H, prm.D, kAttnWide);
+  prm.lse = flat_ptr<float>(lse, q, at::kFloat, exactly((int64_t)prm.B * prm.H * prm.Sq), "attention: lse");
+  auto pick = [&](const optional<Tensor>& t, int64_t S, int64_t heads, const char* n) {
+    if (has(t)) {
+      check_bshd(*t, q, n, prm.B, S, heads, prm.D, kAttnWide);
+      return *t;
+    }
+    return at::empty({prm.B, S, heads, prm.D}, q.options());
+  };
+  Tensor dq = pick(dq_out, prm.Sq, prm.H, "dq_out"), dk = pick(dk_out, prm.Sk, prm.Hkv, "dk_out"),
+         dv = pick(dv_out, prm.Sk, prm.Hkv, "dv_out");
+  Tensor delta = at::empty({prm.B, prm.H, prm.Sq}, q.options().dtype(at::kFloat));
+  set_view(o, prm.o, prm.o_sb, prm.o_ss, prm.o_sh);
+  set_view(dout, prm.dout, prm.do_sb, prm.do_ss, prm.do_sh);
+  prm.delta = delta.data_ptr<float>();
+  set_view(dq, prm.dq, prm.dq_sb, prm.dq_ss, prm.dq_sh);
+  set_view(dk, prm.dk, prm.dk_sb, prm.dk_ss, prm.dk_sh);
+  set_view(dv, prm.dv, prm.dv_sb, prm.dv_ss, prm.dv_sh);
+  check_rc(kAttnWide.bwd(&prm, stream()), kAttnWide.bwd_name);
+  return {dq, dk, dv, Tensor()};
+}
+
 // ---- csrc/attn.hip: the same helpers, plus its extras (dropout bit planes, saturated-bias ranges, rowrec, column sums)
 // its K/V tile rings and key masks live in LDS (sequence length) and its plane / rowrec indices are 64-bit products
 void check_limits_attn(const AttnParams& p) {
@@ -475,6 +569,20 @@ void bind_attn(pybind11::module& m) {
         py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none(),
         py::arg("softcap") = 0.0);
   m.def("attn_hd_bwd", &attn_hd_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
+        py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
+        py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
+        py::arg("dv_out") = py::none(), py::arg("window") = -1, py::arg("q_seg") = py::none(),
+        py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
+        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
+        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none(),
+        py::arg("softcap") = 0.0);
+  m.def("attn_wide_fwd", &attn_wide_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
+        py::arg("scale"), py::arg("causal"), py::arg("p"), py::arg("seed"), py::arg("window") = -1,
+        py::arg("q_seg") = py::none(), py::arg("k_seg") = py::none(), py::arg("q_blk") = py::none(), py::arg("k_blk") = py::none(),
+        py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
+        py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none(),
+        py::arg("softcap") = 0.0);
+  m.def("attn_wide_bwd", &attn_wide_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("kpm"), py::arg("lut"), py::arg("scale"), py::arg("causal"), py::arg("p"),
         py::arg("seed"), py::arg("need_dlut"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(),
         py::arg("dv_out") = py::none(), py::arg("window") = -1, py::arg("q_seg") = py::none(),

@@ -110,6 +110,9 @@ int dllm_attn_f32_fwd(AttnF32Params* pp, hipStream_t st);
 int dllm_attn_f32_bwd(AttnF32Params* pp, hipStream_t st);
 int dllm_attn_hd_fwd(AttnHdParams* pp, hipStream_t st);
 int dllm_attn_hd_bwd(AttnHdParams* pp, hipStream_t st);
+// csrc/attn_wide.hip; < 0: a shape or combination the binding should have refused
+int dllm_attn_wide_fwd(AttnWideParams* pp, hipStream_t st);
+int dllm_attn_wide_bwd(AttnWideParams* pp, hipStream_t st);
 
 // ---- csrc/rope.hip: rotate the `n` listed slots of x [B, S, *, H, D] in place (x_sn: the slot stride; strides in
 // elements); pos [B, S] (pos_sb = S) or [S] (pos_sb = 0); cos / sin fp32 [max_pos, D / 2]; sign -1: the backward

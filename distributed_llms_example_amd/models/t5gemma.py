@@ -32,8 +32,9 @@ encoder-decoder family ``AutoModelForSeq2SeqLM`` gained after 2022 (``google/t5g
 
 Not implemented, each raising ``NotImplementedError`` that names T5Gemma: LoRA, a teacher (distillation), preference
 optimisation, packed inputs and context parallelism; unbalanced encoder / decoder sizes (9b-2b) are refused by the
-config.  Head dims outside 32 .. 128 (the tiny test configs' 16, the 2b / 9b checkpoints' 256) run attention on the
-composite with its one-time warning.
+config.  Head dims 136 .. 256 in bf16 (the 2b / 9b checkpoints' 256) run ``attention_grouped`` on csrc/attn_wide.hip,
+which takes K and V with their ``H_kv`` heads (no repeat); head dims below 32 (the tiny test configs' 16) and, above 128,
+fp32 or attention dropout run attention on the composite with its one-time warning.
 """
 from __future__ import annotations
 
@@ -100,7 +101,9 @@ class T5GemmaAttention(nn.Module):
             kv = kv if kv is not None else self.project_kv(kv_in)
             if kv.shape[0] != B:  # beam search: the nb hypotheses of a batch entry share its encoder K/V (read once)
                 q = q.reshape(kv.shape[0], (B // kv.shape[0]) * S, H, D)
-            if K == H:
+            if attn_ops.grouped_served(q, D, softcap=self.softcap, dropout_p=p):  # csrc/attn_wide.hip: K / V as they are
+                o = attn_ops.attention_grouped(q, kv[:, :, 0], kv[:, :, 1], **kw)
+            elif K == H:
                 o = attn_ops.attention_q_kv(q, kv, **kw)
             else:
                 o = attn_ops.attention(q, self._rep(kv[:, :, 0]), self._rep(kv[:, :, 1]), **kw)
@@ -109,7 +112,9 @@ class T5GemmaAttention(nn.Module):
         if self.window is not None:
             kw["window"] = self.window
         qkv = self.qkv_proj(x)
-        if K == H and cache is None:
+        # head dims 136 .. 256 in bf16: csrc/attn_wide.hip reads the H_kv heads of the packed output (or the cache)
+        wide = attn_ops.grouped_served(qkv, D, window=self.window, softcap=self.softcap, dropout_p=p)
+        if K == H and cache is None and not wide:
             packed = rope(qkv.view(B, S, 3, H, D), pos, cos, sin, slots=2)
             o = attn_ops.attention_qkv(packed, **kw)
         else:
@@ -119,7 +124,10 @@ class T5GemmaAttention(nn.Module):
             v = qkv[..., (H + K) * D:].view(B, S, K, D)
             if cache is not None:
                 k, v = cache.append(k, v)
-            o = attn_ops.attention(q, self._rep(k), self._rep(v), **kw)
+            if wide:
+                o = attn_ops.attention_grouped(q, k, v, **kw)
+            else:
+                o = attn_ops.attention(q, self._rep(k), self._rep(v), **kw)
         return self.o_proj(o.reshape(B, S, H * D))
 
 

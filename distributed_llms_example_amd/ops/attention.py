@@ -758,3 +758,61 @@ def attention_q_kv(q, kv, **kw):
                              kw.get("scale", 1.0), kw.get("causal", False), kw.get("dropout_p", 0.0), kw.get("seed", 0),
                              window, _on(qs, q), _on(ks, q), _on(gk, q), bl, cap)
     return attention(q, kv[:, :, 0], kv[:, :, 1], **kw)
+
+
+# --------------------------------------------------------------------------- grouped K/V heads (csrc/attn_wide.hip)
+
+
+class _GroupedFn(torch.autograd.Function):
+    """csrc/attn_wide.hip: q [B,Sq,H,D], k / v [B,Sk,H_kv,D] as they are (strided views of a fused projection's output
+    included); backward returns dk / dv with H_kv heads, summed over each group in the kernel."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, kpm, scale, causal, window, softcap):
+        win = -1 if window is None else int(window)
+        o, lse = _ext.native().attn_wide_fwd(q, k, v, kpm, None, float(scale), bool(causal), 0.0, 0, win,
+                                             **_cap_args(softcap))
+        ctx.save_for_backward(q, k, v, o, lse, kpm)
+        ctx.cfg = (float(scale), bool(causal), win, softcap)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, kpm = ctx.saved_tensors
+        scale, causal, win, softcap = ctx.cfg
+        dq, dk, dv, _ = _ext.native().attn_wide_bwd(do.contiguous(), q, k, v, o, lse, kpm, None, scale, causal, 0.0, 0,
+                                                    False, None, None, None, win, **_cap_args(softcap))
+        streams.pair_join()
+        return dq, dk, dv, None, None, None, None, None
+
+
+def grouped_served(t, head_dim: int, *, window=None, softcap=None, dropout_p: float = 0.0) -> bool:
+    """csrc/attn_wide.hip serves an :func:`attention_grouped` call on tensors of ``t``'s device and dtype at
+    ``head_dim`` (ops/routing.py ``attention_grouped_route``); models ask before they form the un-repeated views."""
+    return (_ext.use_native(t) and routing.attention_grouped_route(
+        head_dim, t.dtype == torch.bfloat16, window, softcap=softcap is not None,
+        dropout=dropout_p > 0.0) == "attn_wide.hip")
+
+
+def attention_grouped(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_mask=None,
+                      window: int | None = None, softcap: float | None = None, dropout_p: float = 0.0, seed: int = 0):
+    """Grouped-query attention: q ``[B,Sq,H,D]``, k / v ``[B,Sk,H_kv,D]`` with ``H % H_kv == 0``; query head ``h``
+    reads K/V head ``h // (H // H_kv)``.  bf16 on the GPU at head dims 136 .. 256 (``D % 8 == 0``, 16-byte aligned rows,
+    no dropout) runs csrc/attn_wide.hip, which never repeats K / V and sums dk / dv over a group in registers.
+    Everything else — CPU tensors, ``DLLM_REFERENCE_OPS=1``, fp32, other head dims, ``dropout_p > 0``, unaligned rows,
+    ``attn_wide`` = 0 — is :func:`attention` on ``repeat_interleave``d K / V, whatever that routes to (at head dims
+    above 128 the composite, with its one-time warning).  No bias LUT, segments, global keys or block lists here."""
+    softcap = _check_softcap(softcap)
+    H, Hkv = q.shape[2], k.shape[2]
+    if Hkv <= 0 or H % Hkv or v.shape[2] != Hkv:
+        raise ValueError(f"attention_grouped: {H} query heads over k / v with {Hkv} / {v.shape[2]} heads")
+    if window is not None:
+        _check_window(window, q.shape[1], k.shape[1], causal)
+    if (grouped_served(q, q.shape[-1], window=window, softcap=softcap, dropout_p=dropout_p)
+            and k.dtype == q.dtype and v.dtype == q.dtype and all(_aligned(x) for x in (q, k, v))):
+        return _GroupedFn.apply(q, k, v, _prep_kpm(key_padding_mask), scale, causal, window, softcap)
+    G = H // Hkv
+    if G > 1:
+        k, v = k.repeat_interleave(G, 2), v.repeat_interleave(G, 2)
+    return attention(q, k, v, scale=scale, causal=causal, key_padding_mask=key_padding_mask, dropout_p=dropout_p,
+                     seed=seed, window=window, softcap=softcap)

@@ -76,6 +76,13 @@ soft-capped attention          as the window (same route; bf16 head dim 32, and 
                                c·tanh(s / c) per score in instantiations of their own in
                                csrc/attn_hd.hip and csrc/attn_f32.hip; csrc/attn.hip has
                                no cap
+grouped-head attention, head   ``attention_grouped`` (k / v with H_kv heads), bf16 at head    attn_wide.txt
+dims 136 .. 256 (T5Gemma       dims 136 .. 256 (% 8 == 0), no dropout: csrc/attn_wide.hip
+2b-2b / 9b-9b)                 (``attn_wide`` = 1): a staged K/V block serves the query
+                               heads of its group, dK / dV summed over the group in
+                               registers; with or without a window, a cap, causal; 0 and
+                               anything else: ``attention`` on repeated K / V (at these
+                               head dims the composite)
 segment-masked attention       as the window: bf16 (head dim 64 included) on                 attn_segments_vs_masked.txt
 (sequence packing)             csrc/attn_hd.hip, fp32 at head dim 64 on csrc/attn_f32.hip;
                                blocks of other segments are skipped by per-block (min,
@@ -146,6 +153,7 @@ DEFAULTS: dict = {
     "attn_f32": 1,
     "attn_hd": 1,                 # bf16 head dims 32 .. 128 other than 64 on csrc/attn_hd.hip (0: composite)
     "attn_lists": 1,              # block-list calls on csrc/attn_hd.hip / csrc/attn_f32.hip (0: composite)
+    "attn_wide": 1,               # attention_grouped at bf16 head dims 136 .. 256 on csrc/attn_wide.hip (0: fallback)
     "attn_chunk": 0,              # 0: 8192 rows for < 32 rows per head, else 4096
     "attn_chunk_min": 8192,
     # weight-gradient side stream (ops/streams.py)
@@ -237,6 +245,19 @@ def attention_route(head_dim: int, bf16: bool = True, window: int | None = None,
     if bf16 and 32 <= head_dim <= 128 and head_dim % 8 == 0 and get("attn_hd"):
         return "attn_hd.hip"
     return "composite"
+
+
+def attention_grouped_route(head_dim: int, bf16: bool = True, window: int | None = None, *, softcap: bool = False,
+                            dropout: bool = False) -> str:
+    """Route of an ops/attention.py ``attention_grouped`` call (k / v with ``H_kv`` heads) on the GPU:
+    ``"attn_wide.hip"`` for bf16 at head dims 136 .. 256 (% 8 == 0) without dropout — with or without a ``window`` or
+    a ``softcap``, both of which csrc/attn_wide.hip serves — else ``"fallback"``: :func:`attention` on K / V repeated
+    per query head, whose own route :func:`attention_route` gives.  ``attn_wide`` = 0 sends every call to the fallback
+    (A/B).  The decode-shaped call (Sq = 1) is served like any other: no crossover was found (profiles/attn_wide.txt)."""
+    del window, softcap  # served either way; part of the signature so that callers state the call they route
+    if bf16 and not dropout and 128 < head_dim <= 256 and head_dim % 8 == 0 and get("attn_wide"):
+        return "attn_wide.hip"
+    return "fallback"
 
 
 def plan(model: str, tokens_enc: int, tokens_dec: int, d_model: int, d_ff: int, act: str, vocab: int, *,

@@ -37,7 +37,9 @@ CXX = os.environ.get("CXX", "g++")
 # costs more issue cycles than the scalar ops (MI355X_MICROARCH.md, per-instruction constants) and the compiler adds
 # v_mov shuffles to form the register pairs.  attn_hd.hip: the same, for the same reason — its softmax / dS stage is
 # 16 independent f32 element chains per lane that sit between two MFMA groups.
-EXTRA_FLAGS = {"attn.hip": ["-fno-slp-vectorize"], "attn_hd.hip": ["-fno-slp-vectorize"]}
+EXTRA_FLAGS = {"attn.hip": ["-fno-slp-vectorize"], "attn_hd.hip": ["-fno-slp-vectorize"],
+               # attn_wide.hip: the same stage; and no packed fp32 instructions at all (the accumulator rescale)
+               "attn_wide.hip": ["-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # DLLM_HIPFLAGS_EXTRA: extra flags for every HIP source (A/B builds of a kernel variant, e.g. "-DDKDV_PIPE=0"); part
 # of the object key, so switching it back rebuilds the default objects
 _ENV_FLAGS = os.environ.get("DLLM_HIPFLAGS_EXTRA", "").split()
