@@ -31,6 +31,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   dllm::bind_gemm(m);
   dllm::bind_generate(m);
   dllm::bind_lora(m);
+  dllm::bind_nf4(m);
   dllm::bind_reducer(m);
   m.attr("arch") = "gfx950";
 }

@@ -33,6 +33,7 @@ void bind_attn(pybind11::module& m);
 void bind_gemm(pybind11::module& m);     // wgrad, fused, w4, GEGLU, LM-head CE
 void bind_generate(pybind11::module& m); // beam, sample, kv_reorder
 void bind_lora(pybind11::module& m);
+void bind_nf4(pybind11::module& m);
 void bind_reducer(pybind11::module& m);  // csrc/reducer.cpp
 
 inline hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }

@@ -148,4 +148,12 @@ int dllm_lora_up(const void* t, int r, const void* M, int kmajor, void* y, long 
 int dllm_lora_wgrad(const void* Wd, long ldw, int wc, const void* S, int r, float* part, int N, int rows_per_split,
                     int wide_major, void* G, int g_bf16, float alpha, int beta, float p, uint32_t seed, uint32_t row0,
                     hipStream_t st);
+
+// ---- csrc/nf4.hip: W [N][K] as codes uint8 [N][K/2] + absmax fp32 [N][K/64] (N, K % 64 == 0; ops/nf4.py)
+int dllm_nf4_decode_rows();
+int dllm_nf4_quantize(const void* w, int is_bf16, uint8_t* codes, float* absmax, long N, long K, hipStream_t st);
+int dllm_nf4_dequant(const uint8_t* codes, const float* absmax, void* out, long N, long K, hipStream_t st);
+// nn = 0: out [M][N] = x [M][K] . deq(W)^T (+ bias); nn = 1: out [M][K] = x [M][N] . deq(W); bf16, strides in elements
+int dllm_gemm_nf4(const void* x, long ldx, const uint8_t* codes, const float* absmax, const void* bias, void* out,
+                  long ldo, int M, int N, int K, int nn, hipStream_t st);
 }

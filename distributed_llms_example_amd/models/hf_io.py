@@ -16,6 +16,7 @@ import os
 import torch
 from safetensors.torch import load_file, save_file
 
+from ..ops.nf4 import dequantize_nf4, quantize_nf4
 from .bart import BartForConditionalGeneration
 from .config import Seq2SeqConfig, resolve_config
 from .t5 import T5ForConditionalGeneration
@@ -92,10 +93,19 @@ def build_model(cfg_or_name, dtype=torch.float32, device="cpu"):
 def to_hf_state_dict(model) -> dict[str, torch.Tensor]:
     cfg: Seq2SeqConfig = model.config
     out = {}
-    for name, t in model.state_dict().items():
+    own = model.state_dict()
+    for name, t in own.items():
         t = t.detach()
         if _is_adapter_key(name):  # adapters have a checkpoint of their own (save_adapter)
             continue
+        if name.endswith(".weight_absmax"):
+            continue
+        if name.endswith(".weight_nf4"):
+            # an NF4 layer (ops/nf4.py) is written as its dequantised weight under the usual name: the exact fp32
+            # products NF4[code] * absmax, which quantise back to the same codes and scales and whose bf16 roundings
+            # are the values a bf16 model computes with
+            t = dequantize_nf4(t, own[name[: -len("_nf4")] + "_absmax"], torch.float32)
+            name = name[: -len("_nf4")]
         if cfg.model_type == "t5gemma":
             names, sizes = _t5gemma_names(cfg, name)
             for part, piece in zip(names, _split_rows(t, names, sizes)):
@@ -134,9 +144,11 @@ def from_hf_state_dict(model, sd: dict[str, torch.Tensor], strict: bool = True):
     cfg: Seq2SeqConfig = model.config
     own = model.state_dict()
     new = {}
-    for name in own:
-        if _is_adapter_key(name):
+    for own_name in own:
+        if _is_adapter_key(own_name) or own_name.endswith(".weight_absmax"):
             continue
+        # an NF4 layer (ops/nf4.py) is looked up under its weight's name and quantised on the way in (below)
+        name = own_name[: -len("_nf4")] if own_name.endswith(".weight_nf4") else own_name
         if cfg.model_type == "t5gemma":
             names, _ = _t5gemma_names(cfg, name)
             if all(p in sd for p in names):
@@ -174,12 +186,22 @@ def from_hf_state_dict(model, sd: dict[str, torch.Tensor], strict: bool = True):
     # them on save (_keys_to_ignore_on_save) and our module already holds the exact table, so their absence is not an
     # error (Pegasus checkpoints do carry them and they are loaded like any other key)
     derived = {n + ".weight" for n, m in model.named_modules() if getattr(m, "derived_table", False)}
-    missing = [k for k in own if k not in new and k not in derived and not _is_adapter_key(k)]
+    quantized = [k for k in own if k.endswith(".weight_nf4")]
+    for k in quantized:
+        if k[: -len("_nf4")] in new:
+            new[k] = new.pop(k[: -len("_nf4")])
+    missing = [k for k in own if k not in new and k not in derived and not _is_adapter_key(k)
+               and not k.endswith(".weight_absmax")]
     if strict and missing:
         raise KeyError(f"missing keys in checkpoint: {missing[:8]}{'...' if len(missing) > 8 else ''}")
     with torch.no_grad():
         for k, v in new.items():
-            own[k].copy_(v.to(own[k].dtype))
+            if k in quantized:
+                codes, absmax = quantize_nf4(v.to(own[k].device, torch.float32).contiguous())
+                own[k].copy_(codes)
+                own[k[: -len("_nf4")] + "_absmax"].copy_(absmax)
+            else:
+                own[k].copy_(v.to(own[k].dtype))
     return missing
 
 
@@ -272,6 +294,8 @@ def save_adapter(model, output_dir: str) -> list[str]:
     conf = {"peft_type": "LORA", "task_type": "SEQ_2_SEQ_LM", "r": int(cfg.r), "lora_alpha": cfg.alpha,
             "lora_dropout": float(cfg.dropout), "target_modules": leaves, "bias": "none", "fan_in_fan_out": False,
             "inference_mode": True, "base_model_name_or_path": None}
+    if cfg.quantize is not None:
+        conf["quantize"] = cfg.quantize  # not a PEFT field: how the base was held while these adapters were trained
     with open(os.path.join(output_dir, "adapter_config.json"), "w") as f:
         json.dump(conf, f, indent=2, sort_keys=True)
     sd = {k: v.detach().to("cpu").contiguous().clone() for k, v in keys.items()}

@@ -12,17 +12,25 @@ a gated ``wi`` = gate|up.  An adapter therefore lives on an output column slice 
 on a fused ``qkv`` are two adapters on one layer (slices 0 and 2), ``wi`` on a gated FFN adapts both halves.
 Embeddings, the LM head, norms and LED's ``q_global`` / ``kv_global`` are never adapted.  Init as PEFT: ``lora_A``
 Kaiming-uniform (a = √5), ``lora_B`` zeros, so the adapted model starts as the base model.
+
+``LoraConfig(quantize="nf4")`` (QLoRA): after freezing, every projection with one of the names above — adapted or not
+— whose sides are multiples of 64 is held as NF4 codes (ops/nf4.py): ``weight`` None, buffers ``weight_nf4`` /
+``weight_absmax``.  ``merge_lora`` dequantises them again; docs/MODELS.md has the rest.
 """
 from __future__ import annotations
 
+import logging
 import math
 from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
 
+from ..ops import nf4
 from ..ops.linear import Linear
 from ..ops.lora import Adapter
+
+_log = logging.getLogger(__name__)
 
 TARGETS = ("q", "k", "v", "o", "wi", "wo")
 
@@ -40,9 +48,12 @@ class LoraConfig:
     alpha: float = 16
     dropout: float = 0.0
     targets: tuple = ("q", "v")
+    quantize: str | None = None  # "nf4": QLoRA, the frozen projections held as 4-bit codes (ops/nf4.py)
 
     def __post_init__(self):
         object.__setattr__(self, "targets", tuple(self.targets))
+        if self.quantize not in (None, "nf4"):
+            raise ValueError(f"unknown LoRA base quantisation {self.quantize!r}; known: nf4")
         unknown = [t for t in self.targets if t not in TARGETS]
         if unknown:
             raise ValueError(f"unknown LoRA targets {unknown}; known: {', '.join(TARGETS)}")
@@ -115,7 +126,52 @@ def apply_lora(model: nn.Module, cfg: LoraConfig) -> nn.Module:
     if count == 0:
         raise ValueError(f"apply_lora: no projection of this model matches the targets {cfg.targets}")
     model._lora_cfg = cfg
+    if cfg.quantize == "nf4":
+        before = frozen_bytes(model)
+        skipped = quantize_base(model)
+        model._nf4_report = {"frozen_bytes_before": before, "frozen_bytes": frozen_bytes(model),
+                             "nf4_skipped": skipped}
+        _log.info("nf4: frozen bytes %d -> %d; not a multiple of 64 on both sides, kept as they are: %s", before,
+                  model._nf4_report["frozen_bytes"], ", ".join(skipped) or "none")
     return model
+
+
+def quantized_layers(model):
+    """[(module name, Linear)] of the layers whose frozen weight is held as NF4 codes."""
+    return [(n, m) for n, m in model.named_modules() if isinstance(m, Linear) and m._nf4 is not None]
+
+
+@torch.no_grad()
+def quantize_base(model) -> list[str]:
+    """Quantise the frozen weight of every projection whose leaf name is in ``_SLICES`` (attention projections and FFN
+    layers, cross-attention K/V included; adapted or not) to NF4: ``weight`` becomes None, the buffers ``weight_nf4``
+    / ``weight_absmax`` hold it.  Never the LM head, embeddings, norms, bias tables or LED's ``q_global`` /
+    ``kv_global``.  Returns the names of the layers left as they are because a side is no multiple of 64."""
+    skipped = []
+    for name, mod in list(model.named_modules()):
+        if not isinstance(mod, Linear) or _layer_slices(model, name, mod) is None or mod._nf4 is not None:
+            continue
+        if not nf4.quantizable(mod.out_features, mod.in_features):
+            skipped.append(name)
+            continue
+        codes, absmax = nf4.quantize_nf4(mod.weight)
+        mod.weight = None
+        mod.register_buffer("weight_nf4", codes)
+        mod.register_buffer("weight_absmax", absmax)
+        mod._nf4 = True
+    return skipped
+
+
+def frozen_bytes(model) -> int:
+    """Bytes of the parameters that take no gradient plus the NF4 buffers (tied parameters once)."""
+    seen, total = set(), 0
+    for p in model.parameters():
+        if id(p) not in seen and not p.requires_grad:
+            seen.add(id(p))
+            total += p.numel() * p.element_size()
+    for _, m in quantized_layers(model):
+        total += m.weight_nf4.numel() + 4 * m.weight_absmax.numel()
+    return total
 
 
 def adapter_slice_index(ad: Adapter) -> int:
@@ -125,9 +181,17 @@ def adapter_slice_index(ad: Adapter) -> int:
 @torch.no_grad()
 def merge_lora(model: nn.Module) -> nn.Module:
     """Fold every adapter into its base weight — ``W[c0:c0+n] += scale · B A``, computed in fp32 and rounded once —
-    and remove the adapters: a plain model (parameters trainable as before ``apply_lora``)."""
+    and remove the adapters: a plain model (parameters trainable as before ``apply_lora``).  A layer held as NF4 codes
+    is dequantised in fp32 first, so its merged weight is rounded to the model dtype once."""
     if not has_lora(model):
         raise RuntimeError("merge_lora: the model carries no adapters")
+    dtype = next(model.parameters()).dtype
+    dequantized = [mod for _, mod in quantized_layers(model)]
+    for mod in dequantized:  # back to an ordinary weight: fp32 until the adapters are folded in, so ONE rounding
+        w = nf4.dequantize_nf4(mod.weight_nf4, mod.weight_absmax, torch.float32)
+        mod.weight = nn.Parameter(w, requires_grad=False)
+        del mod.weight_nf4, mod.weight_absmax, mod._nf4
+    model.__dict__.pop("_nf4_report", None)
     for _, mod in adapted_layers(model):
         adapters, _ = mod._lora
         for ad in adapters:
@@ -137,6 +201,8 @@ def merge_lora(model: nn.Module) -> nn.Module:
             delattr(mod, f"lora_A_{i}")
             delattr(mod, f"lora_B_{i}")
         del mod._lora  # back to the class default: no adapters
+    for mod in dequantized:
+        mod.weight.data = mod.weight.data.to(dtype)
     trainable = set(model._lora_trainable)
     for n, p in model.named_parameters():
         p.requires_grad_(n in trainable)

@@ -77,6 +77,12 @@ def _kept(params, x2, h, h_for_wgrad_only: bool):
     return None, (None if h_for_wgrad_only else h)
 
 
+def _quantized(lin_in, lin_out) -> bool:
+    """One of the two layers holds an NF4 weight (ops/nf4.py): no ``weight`` to hand to the epilogue kernels, so the FFN
+    runs as ``lin_out(act_dropout(lin_in(x)))``, like an adapted one."""
+    return getattr(lin_in, "_nf4", None) is not None or getattr(lin_out, "_nf4", None) is not None
+
+
 def _frozen_ffn(x: torch.Tensor, lin_in, lin_out) -> bool:
     """A frozen FFN without adapters of its own under a trainable input: the fused kernels run it forward and through
     the input gradient, and skip every weight / bias gradient."""
@@ -265,7 +271,7 @@ def gated_ffn(x: torch.Tensor, lin_in, lin_out, act: str, p: float = 0.0, seed: 
     d_model <= ``gated_max_d``, ops/routing.py)."""
     global gated_calls
     wi, wo = lin_in.weight, lin_out.weight
-    if (act in ("gelu_new", "gelu_fast") and _enabled() and x.dtype == torch.bfloat16 and _ext.use_native(x)
+    if (not _quantized(lin_in, lin_out) and act in ("gelu_new", "gelu_fast") and _enabled() and x.dtype == torch.bfloat16 and _ext.use_native(x)
             and torch.is_grad_enabled() and lin_in.bias is None and lin_out.bias is None
             and ((_fusable(wi) and _fusable(wo)) or _frozen_ffn(x, lin_in, lin_out))):
         C = _ext.native()
@@ -289,7 +295,7 @@ def ffn_res(x: torch.Tensor, lin_in, lin_out, act: str, p: float = 0.0, seed: in
     """``ffn(x)`` and, with ``residual``, ``x`` again for the caller's post-LN residual connection: on the fused path
     that residual's gradient is accumulated by the FFN's input-gradient GEMM instead of an autograd add kernel."""
     global fused_calls
-    if (act in EPILOGUES and _enabled() and x.dtype == torch.bfloat16 and _ext.use_native(x)
+    if (not _quantized(lin_in, lin_out) and act in EPILOGUES and _enabled() and x.dtype == torch.bfloat16 and _ext.use_native(x)
             and torch.is_grad_enabled()
             and (all(_fusable(t) for t in (lin_in.weight, lin_in.bias, lin_out.weight, lin_out.bias))
                  or _frozen_ffn(x, lin_in, lin_out))):

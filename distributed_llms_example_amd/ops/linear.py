@@ -143,7 +143,7 @@ def linear_res(x: torch.Tensor, mod) -> tuple[torch.Tensor, torch.Tensor]:
     """``(mod(x), residual)`` where ``residual`` is ``x`` for the caller's residual connection; on the fused path the
     residual's gradient is accumulated by this linear's input-gradient GEMM (``_LinearResFn``)."""
     w, b = mod.weight, mod.bias
-    if _RES_GEMM and torch.is_grad_enabled() and x.requires_grad and _fusable(w) and _fusable(b):
+    if w is not None and _RES_GEMM and torch.is_grad_enabled() and x.requires_grad and _fusable(w) and _fusable(b):
         y, res = _LinearResFn.apply(x, w.detach(), None if b is None else b.detach(), (w, b))
         _mark_bias_out(y, b is not None)
         return y, res
@@ -201,12 +201,25 @@ class Linear(nn.Linear):
     """Drop-in ``nn.Linear`` (same parameters / state-dict keys / init) with GEMM-fused grad accumulation."""
 
     _lora = None  # (adapters, dropout p) once models/lora.py apply_lora attached low-rank adapters to this layer
+    _nf4 = None   # True once models/lora.py quantised the frozen weight (ops/nf4.py): ``weight`` is None, the buffers
+    #               ``weight_nf4`` (codes) / ``weight_absmax`` (fp32 scales) hold it; the bias stays as it was
 
     def forward(self, x):
         if self._lora is not None:
             from .lora import adapted_forward
             return adapted_forward(self, x)
+        if self._nf4 is not None:
+            from .nf4 import nf4_forward
+            return nf4_forward(self, x)
         return linear(x, self.weight, self.bias)
+
+    def _apply(self, fn, recurse=True):
+        absmax = self._buffers.get("weight_absmax")
+        super()._apply(fn, recurse)
+        if absmax is not None and self._buffers["weight_absmax"].dtype != torch.float32:
+            # the scales stay fp32 under ``model.to(dtype)``: they are part of the storage format, not activations
+            self._buffers["weight_absmax"] = absmax.to(self._buffers["weight_absmax"].device)
+        return self
 
 
 # ------------------------------------------------------------------------------------------------
@@ -302,7 +315,8 @@ def stacked_linear(x, mods, shape):
     backward is one dgrad GEMM with K = Σ n_l (instead of L GEMMs plus L-1 adds of dX) and one wgrad
     GEMM accumulated into the flat gradient buffer; consumers that know how (ops/attention.py) write
     their input gradient straight into the stacked gradient buffer through ``_dllm_grad_into``."""
-    if any(getattr(m, "_lora", None) is not None for m in mods):  # adapters are per layer: one GEMM each
+    if any(getattr(m, "_lora", None) is not None or getattr(m, "_nf4", None) is not None for m in mods):
+        # adapters and quantised weights (ops/nf4.py) are per layer: one GEMM each
         return [m(x).view(shape) for m in mods]
     ws = [m.weight for m in mods]
     bs = [m.bias for m in mods]

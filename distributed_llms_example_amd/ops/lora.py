@@ -24,7 +24,8 @@ on hipBLASLt).  fp32 models, CPU tensors, ``DLLM_REFERENCE_OPS=1`` and shapes of
 slice offsets that are not multiples of 8) run the composite.
 
 The base layer must be frozen (models/lora.py ``apply_lora`` freezes it): its forward runs through ``linear_fwd``, its
-input gradient through ``linear_dgrad`` (ops/gemm.py), and it has no weight gradient.  Adapter gradients accumulate into
+input gradient through ``linear_dgrad`` (ops/gemm.py) — a base held as NF4 codes (``mod._nf4``) through ops/nf4.py's
+forward and input gradient instead — and it has no weight gradient.  Adapter gradients accumulate into
 ``_gbuf(p)`` with ``_use`` / ``_fire`` exactly as ops/linear.py ``_LinearAccumFn`` does, every micro-batch (deferred
 weight gradients do not apply to them); without FlatParams they come back through autograd.
 """
@@ -35,7 +36,7 @@ from dataclasses import dataclass
 import torch
 
 from .. import _ext
-from . import routing
+from . import nf4, routing
 from .gemm import linear_dgrad, linear_fwd
 from .linear import _fire, _fusable, _gbuf, _use
 from .rng import default_rng, rowwise_keep_mask
@@ -124,13 +125,23 @@ def _rows16(t2: torch.Tensor) -> torch.Tensor:
     return t2.contiguous()
 
 
+def _base(mod):
+    """The frozen base weight as the autograd function takes it: ``(weight,)``, or the ``(codes, absmax)`` buffers of
+    a quantised layer (ops/nf4.py)."""
+    if getattr(mod, "_nf4", None) is not None:
+        return (mod.weight_nf4, mod.weight_absmax)
+    return (mod.weight,)
+
+
 def _forward(x, w, b, slices, p, seed, ab):
-    """(x2, y2, [t per adapter], ran on csrc/lora.hip): the frozen base GEMM and the adapters' updates of its output."""
+    """(x2, y2, [t per adapter], ran on csrc/lora.hip): the frozen base GEMM (``w``: :func:`_base`) and the adapters'
+    updates of its output."""
     global fused_calls, lib_calls
     x2 = x.reshape(-1, x.shape[-1])
     if not x2.is_contiguous():
         x2 = x2.contiguous()
-    y = linear_fwd(x2, w, b)  # a fresh [N, out] tensor: the adapters update it in place
+    # a fresh [N, out] tensor: the adapters update it in place
+    y = linear_fwd(x2, w[0], b) if len(w) == 1 else nf4._fwd2(x2, w[0], w[1], b)
     fused = _kernel_ok(x2, y.shape[1], slices)
     if fused:
         C = _ext.native()
@@ -154,8 +165,8 @@ class _LoraLinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, slices, p, seed, params, *ab):
         x2, y, ts, fused = _forward(x, w, b, slices, p, seed, ab)
-        ctx.save_for_backward(x2, w, *ts, *ab)
-        ctx.cfg = (slices, p, seed, fused, x.shape)
+        ctx.save_for_backward(x2, *w, *ts, *ab)  # a quantised base: its code and scale buffers, never a bf16 weight
+        ctx.cfg = (slices, p, seed, fused, x.shape, len(w))
         ctx.params = params
         for q in params or ():
             _use(q)
@@ -164,13 +175,15 @@ class _LoraLinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         saved = ctx.saved_tensors
-        slices, p, seed, fused, shape = ctx.cfg
+        slices, p, seed, fused, shape, nw = ctx.cfg
         na = len(slices)
-        x2, w = saved[0], saved[1]
-        ts, ab = saved[2:2 + na], saved[2 + na:]
+        x2, w = saved[0], saved[1:1 + nw]
+        ts, ab = saved[1 + nw:1 + nw + na], saved[1 + nw + na:]
         params = ctx.params
         dy2 = dy.reshape(-1, dy.shape[-1])
-        dx2 = linear_dgrad(dy2, w) if ctx.needs_input_grad[0] else None
+        dx2 = None
+        if ctx.needs_input_grad[0]:
+            dx2 = linear_dgrad(dy2, w[0]) if nw == 1 else nf4._dgrad2(dy2, w[0], w[1])
         if dx2 is not None and not dx2.is_contiguous():
             dx2 = dx2.contiguous()
         with torch.no_grad():
@@ -203,8 +216,8 @@ class _LoraLinearFn(torch.autograd.Function):
 def lora_linear(x: torch.Tensor, mod, adapters, p: float = 0.0, seed: int = 0) -> torch.Tensor:
     """``mod(x)`` plus every adapter's ``scale · (keep ⊙ x / (1 - p)) Aᵀ Bᵀ`` added into its column slice (module
     docstring).  ``mod``: a linear layer with a frozen ``weight`` / ``bias``; ``adapters``: :class:`Adapter` list."""
-    w, b = mod.weight, mod.bias
-    if w.requires_grad or (b is not None and b.requires_grad):
+    w, b = _base(mod), mod.bias
+    if w[0].requires_grad or (b is not None and b.requires_grad):
         raise NotImplementedError("lora_linear needs a frozen base layer (models/lora.py apply_lora freezes it)")
     slices = tuple((ad.c0, ad.n, float(ad.scale)) for ad in adapters)
     plist = [q for ad in adapters for q in (ad.A, ad.B)]

@@ -101,6 +101,13 @@ low-rank adapters (LoRA)       csrc/lora.hip (``lora`` = fused): mask regenerate
                                once, split reductions summed in order into the flat
                                gradient; ``lib``: the composite on torch matmuls (2-9x
                                slower per adapted projection, 3.3-3.6x per step)
+NF4 frozen base (QLoRA)        csrc/nf4.hip (``nf4`` = fused): the 4-bit codes expanded to      nf4_gemm.txt
+                               bf16 MFMA operands on the way through LDS, forward (NT; a
+                               narrow tile for <= 64 decode rows) and input gradient (NN),
+                               for calls of <= ``nf4_fused_max_rows`` (1024) rows and a
+                               reduction <= ``nf4_fused_max_depth`` (1024); above either,
+                               and under ``dequant``: nf4_dequant into a transient bf16
+                               weight, then the projection routes above
 Adafactor                      csrc/adafactor.hip (``adafactor`` = fused): five launches per   adafactor_step.txt
                                step over a device unit table, three gradient reads, fixed-
                                order partial sums; ``composite``: the per-unit torch ops
@@ -147,6 +154,10 @@ DEFAULTS: dict = {
     "pref": "fused",              # fused | composite
     # low-rank adapters (ops/lora.py): csrc/lora.hip, or the composite on torch matmuls
     "lora": "fused",              # fused | lib
+    # NF4 frozen base weights (ops/nf4.py): the GEMMs of csrc/nf4.hip on the codes, or nf4_dequant + the library GEMM
+    "nf4": "fused",               # fused | dequant
+    "nf4_fused_max_rows": 1024,   # fused serves calls of at most this many rows ...
+    "nf4_fused_max_depth": 1024,  # ... and a reduction at most this deep (K forward, N backward); dequant the rest
     # Adafactor (ops/optim.py FusedAdafactor): csrc/adafactor.hip, or the per-unit torch composite
     "adafactor": "fused",         # fused | composite
     # attention (ops/attention.py, parallel/context.py)
