@@ -28,7 +28,7 @@ using c10::optional;
 // one per family file; csrc/bind.cpp calls them all
 void bind_rowwise(pybind11::module& m);  // norm, activation, dropout, colsum, embedding backward
 void bind_loss(pybind11::module& m);     // cross entropy, distillation
-void bind_optim(pybind11::module& m);    // sq_norm, AdamW, Adafactor
+void bind_optim(pybind11::module& m);    // sq_norm, AdamW, 8-bit AdamW, Adafactor
 void bind_attn(pybind11::module& m);
 void bind_gemm(pybind11::module& m);     // wgrad, fused, w4, GEGLU, LM-head CE
 void bind_generate(pybind11::module& m); // beam, sample, kv_reorder

@@ -1,5 +1,6 @@
-// Optimizer kernels: gradient norm and AdamW (csrc/adamw.hip), Adafactor (csrc/adafactor.hip).  They walk every
-// buffer as one flat array with 16-B (the AdamW decay mask: 8-B) vector accesses.
+// Optimizer kernels: gradient norm and AdamW (csrc/adamw.hip), 8-bit AdamW (csrc/adamw_q8.hip), Adafactor
+// (csrc/adafactor.hip).  They walk every buffer as one flat array with 16-B (the AdamW decay mask: 8-B; the 8-bit
+// step's codes and mask: 4-B) vector accesses.
 #include "bind_common.h"
 
 #include "adafactor_params.h"
@@ -41,6 +42,42 @@ void adamw_step(Tensor param, const optional<Tensor>& master, const Tensor& grad
                       grad.scalar_type() == at::kFloat, hyper_p, stream()),
            "adamw");
 }
+
+// 8-bit AdamW (csrc/adamw_q8.hip; the contract: ops/q8.py).  code_* uint8 [n] (or [n / 64, 64]), absmax_* fp32
+// [n / 64], slots int32 [n / 64], side_* fp32 [64 * slots] (the fp32 moments of the blocks with a slot >= 0), tables
+// fp32 [1024] = signed book | unsigned book | signed midpoints | unsigned midpoints.
+void adamw_q8_step(Tensor param, const optional<Tensor>& master, const Tensor& grad, Tensor code_m, Tensor code_v,
+                   Tensor absmax_m, Tensor absmax_v, const Tensor& slots, Tensor side_m, Tensor side_v,
+                   const optional<Tensor>& wd_mask, const Tensor& tables, const Tensor& coef, double lr, double b1,
+                   double b2, double eps, double wd, double bc1, double bc2, const optional<Tensor>& hyper) {
+  const bool bf16 = is_bf16(param);
+  void* param_p = flat_ptr<void>(param, param, kParamDtypes, at_least(64, bf16 ? 8 : 16), "adamw_q8: param");
+  const int64_t n = param.numel();
+  TORCH_CHECK(n % 64 == 0, "adamw_q8: the flat buffers are whole 64-element blocks, got numel ", n);
+  TORCH_CHECK(bf16 == has(master), "adamw_q8: bf16 parameters need an fp32 master, fp32 parameters take none");
+  const int64_t nb = n / 64;
+  const float* grad_p = flat_ptr<const float>(grad, param, at::kFloat, exactly(n, 16), "adamw_q8: grad");
+  float* master_p = flat_ptr<float>(master, param, at::kFloat, exactly(n, 16), "adamw_q8: master");
+  uint8_t* cm_p = flat_ptr<uint8_t>(code_m, param, at::kByte, exactly(n, 4), "adamw_q8: code_m");
+  uint8_t* cv_p = flat_ptr<uint8_t>(code_v, param, at::kByte, exactly(n, 4), "adamw_q8: code_v");
+  float* am_p = flat_ptr<float>(absmax_m, param, at::kFloat, exactly(nb, 4), "adamw_q8: absmax_m");
+  float* av_p = flat_ptr<float>(absmax_v, param, at::kFloat, exactly(nb, 4), "adamw_q8: absmax_v");
+  const int* slots_p = flat_ptr<const int>(slots, param, at::kInt, exactly(nb, 4), "adamw_q8: slots");
+  TORCH_CHECK(side_m.numel() >= 64 && side_m.numel() % 64 == 0 && side_m.numel() / 64 < INT_MAX,
+              "adamw_q8: the side stores hold whole 64-element blocks (at least one)");
+  float* sm_p = flat_ptr<float>(side_m, param, at::kFloat, at_least(64, 16), "adamw_q8: side_m");
+  float* sv_p = flat_ptr<float>(side_v, param, at::kFloat, exactly(side_m.numel(), 16), "adamw_q8: side_v");
+  const uint8_t* mask_p = flat_ptr<const uint8_t>(wd_mask, param, at::kByte, exactly(n, 4), "adamw_q8: wd_mask");
+  const float* tab_p = flat_ptr<const float>(tables, param, at::kFloat, exactly(1024, 4), "adamw_q8: tables");
+  const float* coef_p = flat_ptr<const float>(coef, param, at::kFloat, kAnyScalar, "adamw_q8: coef");
+  const float* hyper_p = flat_ptr<const float>(hyper, param, at::kFloat, at_least(3), "adamw_q8: hyper");
+  check_rc(dllm_adamw_q8(param_p, master_p, grad_p, cm_p, cv_p, am_p, av_p, slots_p, sm_p, sv_p,
+                         (int)(side_m.numel() / 64), mask_p, tab_p, coef_p, n, (float)lr, (float)b1, (float)b2,
+                         (float)eps, (float)wd, (float)bc1, (float)bc2, bf16 ? 1 : 0, hyper_p, stream()),
+           "adamw_q8");
+}
+
+std::vector<int64_t> adamw_q8_geometry() { return {dllm_adamw_q8_wg_elems(), dllm_adamw_q8_grid_cap()}; }
 
 // Adafactor (csrc/adafactor.hip).  adafactor_plan lays out the unit table the kernels walk: `units` is a CPU int64
 // [U, 6] of (flat offset, rows, cols, R|V offset, C offset or -1, decay flag) per unit; the result is the [U + 1,
@@ -140,6 +177,11 @@ void bind_optim(pybind11::module& m) {
   m.def("adamw_step", &adamw_step, py::arg("param"), py::arg("master"), py::arg("grad"), py::arg("m"), py::arg("v"),
         py::arg("wd_mask"), py::arg("coef"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
         py::arg("bc1"), py::arg("bc2"), py::arg("hyper") = py::none());
+  m.def("adamw_q8_step", &adamw_q8_step, py::arg("param"), py::arg("master"), py::arg("grad"), py::arg("code_m"),
+        py::arg("code_v"), py::arg("absmax_m"), py::arg("absmax_v"), py::arg("slots"), py::arg("side_m"),
+        py::arg("side_v"), py::arg("wd_mask"), py::arg("tables"), py::arg("coef"), py::arg("lr"), py::arg("b1"),
+        py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2"), py::arg("hyper") = py::none());
+  m.def("adamw_q8_geometry", &adamw_q8_geometry, "[elements per workgroup and iteration, grid cap]");
   m.def("adafactor_plan", &adafactor_plan, "unit table, tile count and scratch sizes of csrc/adafactor.hip");
   m.def("adafactor_geometry", &adafactor_geometry, "[rows per tile, cols per wave, cols per tile, grid cap, ...]");
   m.def("adafactor_step", &adafactor_step, py::arg("param"), py::arg("master"), py::arg("grad"), py::arg("rv"),

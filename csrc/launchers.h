@@ -102,6 +102,15 @@ int dllm_adafactor_step(void* param, float* master, const float* grad, float* rv
                         float rel, float b2t, float eps1, float eps2, float clip_thr, float wd, int scale_param,
                         int is_bf16, const float* hyper, hipStream_t st);
 
+// ---- csrc/adamw_q8.hip: AdamW on 8-bit block-quantised moments (codes uint8 [n], absmax fp32 [n / 64] per state;
+// slots int [n / 64]: -1 or the block's place in the fp32 side stores; tables: 1024 floats, ops/q8.py)
+int dllm_adamw_q8_wg_elems();
+int dllm_adamw_q8_grid_cap();
+int dllm_adamw_q8(void* param, float* master, const float* grad, uint8_t* code_m, uint8_t* code_v, float* absmax_m,
+                  float* absmax_v, const int* slots, float* side_m, float* side_v, int nslots, const uint8_t* wd_mask,
+                  const float* tables, const float* coef, long n, float lr, float b1, float b2, float eps, float wd,
+                  float bc1, float bc2, int is_bf16, const float* hyper, hipStream_t st);
+
 // ---- csrc/attn.hip, csrc/attn_f32.hip, csrc/attn_hd.hip
 int dllm_attn_fwd(AttnParams* pp, hipStream_t st);
 int dllm_attn_bwd(AttnParams* pp, hipStream_t st);

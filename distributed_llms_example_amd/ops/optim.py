@@ -138,6 +138,205 @@ class FusedAdamW:
         self.param_groups[0]["lr"] = d.get("lr", self.param_groups[0]["lr"])
 
 
+# ------------------------------------------------------------------------------------------------ 8-bit AdamW
+_warned_q8_composite = [False]
+MIN_8BIT_SIZE = 4096  # the HF Trainer's rule for adamw_bnb_8bit: smaller parameters keep fp32 moments
+
+
+def embedding_parameters(module: torch.nn.Module) -> set[str]:
+    """Names (as ``named_parameters`` gives them) of the parameters owned by ``nn.Embedding`` modules: token embeddings
+    (and with them a tied LM head), learned position tables, relative-position bias tables."""
+    ids = {id(p) for m in module.modules() if isinstance(m, torch.nn.Embedding) for p in m.parameters(recurse=False)}
+    return {n for n, p in module.named_parameters() if id(p) in ids}
+
+
+class FusedAdamW8bit(FusedAdamW):
+    """AdamW with block-wise 8-bit moments (Dettmers et al. 2022) over the flat parameter space: ``FusedAdamW``'s clip,
+    recurrence, decay mask, master weights and ``device_hyper``, with ``exp_avg`` / ``exp_avg_sq`` kept as one uint8
+    code per element and one fp32 scale per 64-element block (the contract: ops/q8.py).  Per block, a step dequantises
+    both moments, runs the fp32 recurrence, updates master and parameter from the UNQUANTISED new moments, then takes
+    each new block maximum and stores new codes and scales.
+
+    Parameters with fewer than ``min_8bit_size`` (4096) elements and those ``keep_fp32(name)`` selects (the engine
+    passes the parameters owned by embedding modules) keep fp32 moments, as the HF Trainer arranges for
+    ``adamw_bnb_8bit``.  They live in ``side_m`` / ``side_v``, 64 floats per block in canonical segment order — not
+    flat-indexed, so a relayout moves nothing in them; the flat companion ``slots`` (one int32 per block) holds the
+    block's place there, or -1 for a quantised block.  ``code_*`` ([blocks, 64]), ``absmax_*`` and ``slots`` are
+    companions of granule 64: a block never straddles two parameters (parallel/flat.py ALIGN), so a relayout moves
+    whole blocks and loses nothing.
+
+    On the GPU one launch of csrc/adamw_q8.hip runs the step (route ``adamw_q8`` = fused) for fp32 gradients with
+    bf16 parameters + fp32 master or fp32 parameters without one; ``_reference_step`` is the torch composite: the CPU
+    path, the oracle, and what ``adamw_q8=composite`` / ``DLLM_REFERENCE_OPS=1`` / other dtypes select.
+    """
+
+    def __init__(self, flat: FlatParams, lr: float = 5e-5, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, no_decay=None, master_weights: bool | None = None, keep_fp32=None,
+                 min_8bit_size: int = MIN_8BIT_SIZE):
+        from . import q8
+        from ..utils.logging import get_logger
+        self.flat = flat
+        self.lr = lr
+        self.betas = betas
+        self.eps = eps
+        self.weight_decay = weight_decay
+        self.step_count = 0
+        if master_weights is None:
+            master_weights = flat.dtype != torch.float32
+        self.master = flat.param_buf.float().clone() if master_weights else None
+        self.wd_mask = flat.decay_mask(no_decay) if (no_decay is not None and weight_decay != 0.0) else None
+        if no_decay is not None and weight_decay != 0.0 and self.wd_mask is None:
+            if all(no_decay(s.name) for s in flat.segments):
+                self.weight_decay = 0.0
+        dev, nblk = flat.device, flat.numel // q8.BLOCK
+        zero_s, _ = q8.quantize(torch.zeros(q8.BLOCK), True)   # the codes of 0.0
+        zero_u, _ = q8.quantize(torch.zeros(q8.BLOCK), False)
+        self.code_m = zero_s.to(dev).repeat(nblk, 1)
+        self.code_v = zero_u.to(dev).repeat(nblk, 1)
+        self.absmax_m = torch.zeros(nblk, dtype=torch.float32, device=dev)
+        self.absmax_v = torch.zeros(nblk, dtype=torch.float32, device=dev)
+        # fp32 segments, in canonical order: name -> (first slot, blocks)
+        by_name = {s.name: s for s in flat.segments}
+        self.fp32_slots: dict[str, tuple[int, int]] = {}
+        at = kept = 0
+        for name in flat.canonical:
+            seg = by_name[name]
+            if seg.numel < min_8bit_size or (keep_fp32 is not None and keep_fp32(name)):
+                k = (seg.numel + q8.BLOCK - 1) // q8.BLOCK
+                self.fp32_slots[name] = (at, k)
+                at += k
+                kept += seg.numel
+        self.slots = torch.full((nblk,), -1, dtype=torch.int32, device=dev)
+        for seg in flat.segments:
+            if seg.name in self.fp32_slots:
+                s0, k = self.fp32_slots[seg.name]
+                b0 = seg.offset // q8.BLOCK
+                self.slots[b0:b0 + k] = torch.arange(s0, s0 + k, dtype=torch.int32, device=dev)
+        self.side_m = torch.zeros(max(at, 1) * q8.BLOCK, dtype=torch.float32, device=dev)
+        self.side_v = torch.zeros_like(self.side_m)
+        for attr in ("master", "wd_mask"):
+            flat.register_companion(self, attr)
+        for attr in ("code_m", "code_v", "absmax_m", "absmax_v", "slots"):
+            flat.register_companion(self, attr, granule=q8.BLOCK)
+        self._one = torch.ones((), dtype=torch.float32, device=dev)
+        self.param_groups = [{"lr": lr, "initial_lr": lr, "weight_decay": weight_decay, "betas": betas, "eps": eps}]
+        get_logger().info("8-bit AdamW: %d of %d parameters (%d of %d elements) keep fp32 moments, %d bytes in the "
+                          "side store; optimizer state %d bytes", len(self.fp32_slots), len(flat.segments), kept,
+                          sum(s.numel for s in flat.segments), 2 * self.side_m.numel() * 4, self.state_bytes())
+
+    # ------------------------------------------------------------------------------------------
+    def grad_norm(self) -> torch.Tensor:
+        from . import routing
+        g = self.flat.grad_buf
+        if _ext.use_native(g) and routing.get("adamw_q8") == "fused":  # the composite route runs no native call
+            return _ext.native().sq_norm(g).sqrt()
+        return torch.linalg.vector_norm(g.float())
+
+    def state_bytes(self) -> int:
+        """Bytes of optimizer state: master, two code bytes per element, two scales and a slot per block, the fp32
+        side store and the decay mask."""
+        return sum(t.numel() * t.element_size() for t in (self.master, self.code_m, self.code_v, self.absmax_m,
+                                                          self.absmax_v, self.slots, self.side_m, self.side_v,
+                                                          self.wd_mask) if t is not None)
+
+    def _fused(self, p: torch.Tensor, g: torch.Tensor) -> bool:
+        from . import routing
+        if not _ext.use_native(p) or routing.get("adamw_q8") != "fused":
+            if p.is_cuda and not _warned_q8_composite[0]:
+                _warned_q8_composite[0] = True
+                import warnings
+                warnings.warn("FusedAdamW8bit: adamw_q8=composite / DLLM_REFERENCE_OPS=1: the torch composite runs")
+            return False
+        served = g.dtype == torch.float32 and ((p.dtype == torch.bfloat16 and self.master is not None) or
+                                               (p.dtype == torch.float32 and self.master is None))
+        if not served and not _warned_q8_composite[0]:
+            _warned_q8_composite[0] = True
+            import warnings
+            warnings.warn("FusedAdamW8bit: the fused kernel serves fp32 gradients with bf16 parameters + fp32 master or "
+                          f"fp32 parameters; {g.dtype} gradients / {p.dtype} parameters take the torch composite")
+        return served
+
+    @torch.no_grad()
+    def step(self, max_grad_norm: float | None = None, hyper: torch.Tensor | None = None) -> torch.Tensor | None:
+        """One clip + 8-bit AdamW update.  ``hyper`` (device_hyper) replaces the host lr / bias corrections."""
+        from . import q8
+        lr = self.param_groups[0]["lr"]
+        self.step_count += 1
+        norm = None
+        coef = self._one
+        if max_grad_norm is not None and max_grad_norm > 0:
+            norm = self.grad_norm()
+            coef = torch.clamp(max_grad_norm / (norm + 1e-6), max=1.0)
+        b1, b2 = self.betas
+        bc1 = 1.0 - b1 ** self.step_count
+        bc2 = 1.0 - b2 ** self.step_count
+        p, g = self.flat.param_buf, self.flat.grad_buf
+        if self._fused(p, g):
+            _ext.native().adamw_q8_step(p, self.master, g, self.code_m, self.code_v, self.absmax_m, self.absmax_v,
+                                        self.slots, self.side_m, self.side_v, self.wd_mask, q8.tables(str(p.device)),
+                                        coef, float(lr), float(b1), float(b2), float(self.eps),
+                                        float(self.weight_decay), float(bc1), float(bc2), hyper)
+        else:
+            if hyper is not None:
+                lr, bc1, bc2 = float(hyper[0]), float(hyper[0] / hyper[1]), float(1.0 / hyper[2] ** 2)
+            self._reference_step(p, g, coef, lr, b1, b2, bc1, bc2)
+        return norm
+
+    def _reference_step(self, p, g, coef, lr, b1, b2, bc1, bc2):
+        """The contract as a torch composite: dequantise (side-store blocks: read), FusedAdamW's recurrence on the
+        fp32 moments, requantise (side-store blocks: write back)."""
+        from . import q8
+        fp32 = self.slots >= 0
+        idx = self.slots[fp32].long()
+        self.exp_avg = q8.dequantize(self.code_m, self.absmax_m, True).view(-1, q8.BLOCK)
+        self.exp_avg_sq = q8.dequantize(self.code_v, self.absmax_v, False).view(-1, q8.BLOCK)
+        self.exp_avg[fp32] = self.side_m.view(-1, q8.BLOCK)[idx]
+        self.exp_avg_sq[fp32] = self.side_v.view(-1, q8.BLOCK)[idx]
+        self.exp_avg, self.exp_avg_sq = self.exp_avg.view(-1), self.exp_avg_sq.view(-1)
+        FusedAdamW._reference_step(self, p, g, coef, lr, b1, b2, bc1, bc2)
+        m, v = self.exp_avg.view(-1, q8.BLOCK), self.exp_avg_sq.view(-1, q8.BLOCK)
+        del self.exp_avg, self.exp_avg_sq
+        self.side_m.view(-1, q8.BLOCK)[idx] = m[fp32]
+        self.side_v.view(-1, q8.BLOCK)[idx] = v[fp32]
+        q = ~fp32  # the kernel leaves the codes and scales of side-store blocks alone
+        (cm, am), (cv, av) = q8.quantize(m[q].reshape(-1), True), q8.quantize(v[q].reshape(-1), False)
+        self.code_m[q], self.absmax_m[q], self.code_v[q], self.absmax_v[q] = cm, am, cv, av
+
+    # ------------------------------------------------------------------------------------------
+    def _layout(self) -> list[dict]:
+        f = self.flat
+        numel = {s.name: s.numel for s in f.segments}
+        return [{"name": n, "numel": numel[n], "fp32": n in self.fp32_slots} for n in f.canonical]
+
+    def state_dict(self) -> dict:
+        """State in the model's canonical segment order, whatever the current layout (the side store always is)."""
+        from . import q8
+        can = self.flat.to_canonical
+        blk = lambda t: can(t, q8.BLOCK)
+        return {"kind": "adamw_8bit", "step": self.step_count, "code_m": blk(self.code_m), "code_v": blk(self.code_v),
+                "absmax_m": blk(self.absmax_m), "absmax_v": blk(self.absmax_v), "side_m": self.side_m,
+                "side_v": self.side_v, "master": can(self.master) if self.master is not None else None,
+                "lr": self.param_groups[0]["lr"], "betas": list(self.betas), "eps": self.eps,
+                "weight_decay": self.weight_decay, "layout": self._layout()}
+
+    def load_state_dict(self, d: dict) -> None:
+        from . import q8
+        if d.get("kind", "adamw") != "adamw_8bit":
+            raise ValueError(f"optimizer state of kind {d.get('kind', 'adamw')!r} cannot be loaded into FusedAdamW8bit")
+        if list(d["layout"]) != self._layout():
+            raise ValueError("optimizer state layout does not match the model")
+        f = self.flat
+        self.step_count = int(d["step"])
+        for k in ("code_m", "code_v", "absmax_m", "absmax_v"):
+            getattr(self, k).copy_(f.from_canonical(d[k].to(f.device), q8.BLOCK))
+        self.side_m.copy_(d["side_m"].to(f.device))
+        self.side_v.copy_(d["side_v"].to(f.device))
+        if self.master is not None and d.get("master") is not None:
+            self.master.copy_(f.from_canonical(d["master"].to(self.master.device)))
+            self.flat.param_buf.copy_(self.master)
+        self.param_groups[0]["lr"] = d.get("lr", self.param_groups[0]["lr"])
+
+
 # ------------------------------------------------------------------------------------------------ Adafactor
 _warned_composite = [False]
 

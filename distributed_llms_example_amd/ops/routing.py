@@ -111,6 +111,10 @@ NF4 frozen base (QLoRA)        csrc/nf4.hip (``nf4`` = fused): the 4-bit codes e
 Adafactor                      csrc/adafactor.hip (``adafactor`` = fused): five launches per   adafactor_step.txt
                                step over a device unit table, three gradient reads, fixed-
                                order partial sums; ``composite``: the per-unit torch ops
+8-bit AdamW                    csrc/adamw_q8.hip (``adamw_q8`` = fused): one launch per step,   adamw_q8_step.txt
+                               16 lanes per 64-block, code books and midpoints in LDS,
+                               block maxima by row-local DPP; ``composite``: the torch ops
+                               of ops/q8.py (also bf16 gradients, CPU tensors)
 gradient reducer               native C++ engine (``reducer`` = native | python), buckets     r5_gloo2_gpu.txt
                                re-laid in gradient-ready order (``rebuild_buckets``)
 HIP-graph DP schedule          overlap: backward segments cut at bucket readiness            r5_gloo2_gpu_final.txt
@@ -160,6 +164,8 @@ DEFAULTS: dict = {
     "nf4_fused_max_depth": 1024,  # ... and a reduction at most this deep (K forward, N backward); dequant the rest
     # Adafactor (ops/optim.py FusedAdafactor): csrc/adafactor.hip, or the per-unit torch composite
     "adafactor": "fused",         # fused | composite
+    # 8-bit AdamW (ops/optim.py FusedAdamW8bit): csrc/adamw_q8.hip, or the torch composite of ops/q8.py
+    "adamw_q8": "fused",          # fused | composite
     # attention (ops/attention.py, parallel/context.py)
     "attn_f32": 1,
     "attn_hd": 1,                 # bf16 head dims 32 .. 128 other than 64 on csrc/attn_hd.hip (0: composite)

@@ -82,7 +82,7 @@ class FlatParams:
             self.params.append(p)
             off += (p.numel() + ALIGN - 1) // ALIGN * ALIGN
         self.numel = off
-        self._companions: list[tuple[object, str]] = []  # flat-indexed tensors kept in step with relayout()
+        self._companions: list[tuple[object, str, int]] = []  # flat-indexed tensors kept in step with relayout()
         self.canonical = [s.name for s in self.segments]  # construction order (optimizer state is saved in it)
         self.layout_version = 0  # bumped by relayout(): whoever caches segment offsets (ops/optim.py unit table) compares it
         self.param_buf = torch.zeros(off, dtype=self.dtype, device=self.device)
@@ -149,10 +149,13 @@ class FlatParams:
                 p.grad = self.grad_view(i)
 
     # ------------------------------------------------------------------------------------------- layout
-    def register_companion(self, obj, attr: str) -> None:
+    def register_companion(self, obj, attr: str, granule: int = 1) -> None:
         """``getattr(obj, attr)`` is indexed like the flat buffers (optimizer master weights / moments, weight-decay
-        mask): relayout() permutes it together with the parameters."""
-        self._companions.append((obj, attr))
+        mask): relayout() permutes it together with the parameters.  ``granule`` (a divisor of ``ALIGN``): the tensor
+        has one entry along dim 0 per ``granule`` flat elements (per-block optimizer state, ops/optim.py
+        FusedAdamW8bit) and is permuted at ``offset / granule``, a segment's last, partial granule included."""
+        assert granule >= 1 and ALIGN % granule == 0, "a companion's granule must divide the segment alignment"
+        self._companions.append((obj, attr, granule))
 
     def _offsets(self, order: list[int]) -> tuple[list[int], int]:
         offs, off = [0] * len(self.segments), 0
@@ -161,10 +164,13 @@ class FlatParams:
             off += (self.segments[i].numel + ALIGN - 1) // ALIGN * ALIGN
         return offs, off
 
-    def _permute(self, t: torch.Tensor, src_offs: list[int], dst_offs: list[int], n: int) -> torch.Tensor:
-        out = torch.zeros(n, dtype=t.dtype, device=t.device)
+    def _permute(self, t: torch.Tensor, src_offs: list[int], dst_offs: list[int], n: int,
+                 granule: int = 1) -> torch.Tensor:
+        out = torch.zeros((n // granule,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
         for i, seg in enumerate(self.segments):
-            out[dst_offs[i]:dst_offs[i] + seg.numel] = t[src_offs[i]:src_offs[i] + seg.numel]
+            k = (seg.numel + granule - 1) // granule
+            s, d = src_offs[i] // granule, dst_offs[i] // granule
+            out[d:d + k] = t[s:s + k]
         return out
 
     @torch.no_grad()
@@ -178,10 +184,10 @@ class FlatParams:
         dst, n = self._offsets(order)
         self.param_buf = self._permute(self.param_buf, src, dst, n)
         self.grad_buf = self._permute(self.grad_buf, src, dst, n)
-        for obj, attr in self._companions:
+        for obj, attr, granule in self._companions:
             t = getattr(obj, attr)
             if t is not None:
-                setattr(obj, attr, self._permute(t, src, dst, n))
+                setattr(obj, attr, self._permute(t, src, dst, n, granule))
         segs = [Segment(self.segments[i].name, dst[i], self.segments[i].numel, self.segments[i].shape) for i in order]
         params = [self.params[i] for i in order]
         self.segments, self.params, self.numel = segs, params, n
@@ -224,13 +230,13 @@ class FlatParams:
         can, n = self._offsets(order)
         return [seg.offset for seg in self.segments], can, n
 
-    def to_canonical(self, t: torch.Tensor) -> torch.Tensor:
+    def to_canonical(self, t: torch.Tensor, granule: int = 1) -> torch.Tensor:
         cur, can, n = self.canonical_offsets()
-        return t if cur == can else self._permute(t, cur, can, n)
+        return t if cur == can else self._permute(t, cur, can, n, granule)
 
-    def from_canonical(self, t: torch.Tensor) -> torch.Tensor:
+    def from_canonical(self, t: torch.Tensor, granule: int = 1) -> torch.Tensor:
         cur, can, n = self.canonical_offsets()
-        return t if cur == can else self._permute(t, can, cur, self.numel)
+        return t if cur == can else self._permute(t, can, cur, self.numel, granule)
 
     def grads(self) -> list[torch.Tensor]:
         """Per-parameter gradient views of the flat buffer (fp32 or param dtype), in ``params`` order."""

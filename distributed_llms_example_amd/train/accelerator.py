@@ -25,7 +25,7 @@ import contextlib
 
 import torch
 
-from ..ops.optim import FusedAdafactor, FusedAdamW
+from ..ops.optim import FusedAdafactor, FusedAdamW, FusedAdamW8bit, embedding_parameters
 from ..parallel import collectives
 from ..parallel.env import init_distributed
 from ..parallel.flat import FlatParams
@@ -78,6 +78,12 @@ class DeviceDataLoader:
         nb = self.device.type == "cuda"
         for batch in self.loader:
             yield {k: (v.to(self.device, non_blocking=nb) if torch.is_tensor(v) else v) for k, v in batch.items()}
+
+
+class AdamW8bit(torch.optim.AdamW):
+    """A ``torch.optim.AdamW`` that ``Accelerator.prepare`` turns into :class:`~..ops.optim.FusedAdamW8bit` (AdamW on
+    block-quantised 8-bit moments) instead of ``FusedAdamW``: what a script that would build ``bnb.optim.AdamW8bit``
+    builds here (a bitsandbytes object itself is not mapped)."""
 
 
 class PreparedOptimizer:
@@ -221,6 +227,10 @@ class Accelerator:
                                    scale_parameter=g0["scale_parameter"], relative_step=g0["relative_step"],
                                    warmup_init=g0["warmup_init"], no_decay=no_decay,
                                    parts=(lambda n: hf_param_parts(cfg, n)) if cfg is not None else None)
+        elif isinstance(opt, AdamW8bit):
+            emb = embedding_parameters(self._model.module)
+            fused = FusedAdamW8bit(flat, lr=g0["lr"], betas=g0.get("betas", (0.9, 0.999)), eps=g0.get("eps", 1e-8),
+                                   weight_decay=wd, no_decay=no_decay, keep_fp32=emb.__contains__)
         else:
             fused = FusedAdamW(flat, lr=g0["lr"], betas=g0.get("betas", (0.9, 0.999)), eps=g0.get("eps", 1e-8),
                                weight_decay=wd, no_decay=no_decay)

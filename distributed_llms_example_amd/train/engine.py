@@ -20,7 +20,7 @@ from ..ops import rng as rng_mod
 from ..ops import streams
 from ..ops.distill import check_weights
 from ..ops.preference import check_config as check_preference
-from ..ops.optim import FusedAdafactor, FusedAdamW
+from ..ops.optim import FusedAdafactor, FusedAdamW, FusedAdamW8bit, embedding_parameters
 from ..utils import profiling
 from ..parallel.env import DistEnv
 from ..parallel.flat import FlatParams
@@ -64,8 +64,10 @@ class TrainEngine:
         """``bucket_mb``: MiB per all-reduce bucket, or "auto" (parallel/reducer.py choose_bucket_mb: probed on the
         job's process group, recorded in ``reducer.bucket_choice``).  ``grad_reduce_dtype``: "bf16" compresses each bucket
         for the wire only (fp32 accumulation kept), None / "fp32" reduces the gradient buffer as it is.  ``optim``:
-        "adamw", or "adafactor" as the HF Trainer builds it (scale_parameter=False, relative_step=False, the learning
-        rate from ``lr``; ``betas`` / ``eps`` are AdamW's and unused).  ``teacher``: a frozen model to distil from
+        "adamw", "adamw_8bit" (HF's spelling "adamw_bnb_8bit" too: AdamW on block-quantised 8-bit moments,
+        ops/optim.py FusedAdamW8bit; small parameters and embeddings keep fp32 moments), or "adafactor" as the HF
+        Trainer builds it (scale_parameter=False, relative_step=False, the learning rate from ``lr``; ``betas`` /
+        ``eps`` are AdamW's and unused).  ``teacher``: a frozen model to distil from
         (``set_teacher``): training steps then minimise (1 - kd_alpha) CE + kd_alpha T^2 KL(teacher || student) at
         temperature ``kd_temperature`` (ops/distill.py).  ``reference``: a frozen reference policy (``set_reference``):
         training steps then minimise the preference loss (ops/preference.py) of batches of (prompt, chosen, rejected)
@@ -90,8 +92,12 @@ class TrainEngine:
             self.optimizer = FusedAdafactor(self.flat, lr=lr, weight_decay=weight_decay, scale_parameter=False,
                                             relative_step=False, no_decay=no_decay,
                                             parts=(lambda n: hf_param_parts(cfg, n)) if cfg is not None else None)
+        elif optim in ("adamw_8bit", "adamw_bnb_8bit"):
+            emb = embedding_parameters(self.model)
+            self.optimizer = FusedAdamW8bit(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                            no_decay=no_decay, keep_fp32=emb.__contains__)
         else:
-            raise ValueError(f"optim must be 'adamw' or 'adafactor', got {optim!r}")
+            raise ValueError(f"optim must be 'adamw', 'adamw_8bit' or 'adafactor', got {optim!r}")
         self.max_grad_norm = max_grad_norm
         self.label_smoothing = label_smoothing
         self.step_seed: rng_mod.StepSeed | None = None

@@ -54,7 +54,8 @@ class TrainingArguments:
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
     adam_epsilon: float = 1e-8
-    optim: str = "adamw_torch"  # any of HF's AdamW names (one fused AdamW here), or "adafactor"
+    # any of HF's AdamW names (one fused AdamW here), "adamw_8bit" / "adamw_bnb_8bit" (8-bit moments), or "adafactor"
+    optim: str = "adamw_torch"
     max_grad_norm: float = 1.0
     lr_scheduler_type: str = "linear"
     warmup_steps: int = 0
@@ -142,7 +143,8 @@ class Trainer:
                                   bucket_mb=args.ddp_bucket_cap_mb or "auto", overlap=args.overlap_comm,
                                   grad_reduce_dtype=args.grad_reduce_dtype,
                                   no_decay=default_no_decay, label_smoothing=args.label_smoothing_factor,
-                                  optim="adafactor" if args.optim == "adafactor" else "adamw",
+                                  optim=(args.optim if args.optim in ("adafactor", "adamw_8bit", "adamw_bnb_8bit")
+                                         else "adamw"),
                                   teacher=teacher, kd_alpha=args.kd_alpha, kd_temperature=args.kd_temperature,
                                   reference=reference, dpo_beta=args.dpo_beta, dpo_loss=args.dpo_loss,
                                   dpo_label_smoothing=args.dpo_label_smoothing, dpo_sft_alpha=args.dpo_sft_alpha)

@@ -78,6 +78,9 @@ class ModelTrainer:
         if a.optim == "adafactor":  # as the HF Trainer builds it (transformers trainer.py: optim="adafactor")
             from transformers.optimization import Adafactor
             optimizer = Adafactor(groups, lr=a.learning_rate, scale_parameter=False, relative_step=False)
+        elif a.optim in ("adamw_8bit", "adamw_bnb_8bit"):  # AdamW on 8-bit moments (ops/optim.py FusedAdamW8bit)
+            from distributed_llms_example_amd.train.accelerator import AdamW8bit
+            optimizer = AdamW8bit(groups, lr=a.learning_rate)
         else:
             optimizer = torch.optim.AdamW(groups, lr=a.learning_rate)
         model, optimizer, train_dl, eval_dl = acc.prepare(self.model, optimizer, train_dl, eval_dl)
