@@ -191,3 +191,37 @@ struct AttnWideParams {
   int G;           // H / Hkv
   int gw;          // query heads of a group a forward / dQ workgroup serves at once: 4, 2 or 1
 };
+
+// Decode-step attention, csrc/attn_decode.hip: bf16 forward only, for the few query rows of a generation step against
+// a long K/V (the self-attention cache, the encoder's K/V shared by a batch entry's beams).  q and o are
+// [B, Sq, H, D] views and k, v [B, Sk, Hkv, D] views, H % Hkv == 0, G = H / Hkv; head dim contiguous, strides in
+// elements, every row start 16-byte aligned; D % 8 == 0, 32 <= D <= 256 (instantiations for the padded dims 64, 128,
+// 256).  The R = Sq * G <= 16 query rows that share one K/V head are packed as r = i * G + g into one 16-row MFMA tile.
+// Key j is visible to query i iff kpm[b][j] != 0 (when given): no causal mask, window, segments, lists or dropout.
+// The score is scale * q.k, with softcap = c > 0 c * tanh(scale * q.k / c) (before the mask), plus
+// lut[h][(j - i) + Sq - 1] when given (never with a cap).  A row without a visible key is an output row of zeros.
+// The key axis is cut into `splits` ranges of L keys (L % 128 == 0), one workgroup each; with splits > 1 they write
+// unnormalised fp32 partials that a second kernel merges in split order (no atomics).
+struct AttnDecodeParams {
+  typedef uint16_t elem;
+  const uint16_t* q;
+  const uint16_t* k;
+  const uint16_t* v;
+  uint16_t* o;
+  const uint8_t* kpm;  // [B, Sk] 1 = attend; nullptr: none
+  const float* lut;    // [H, Sq + Sk - 1]; nullptr: none
+  float* part_o;       // [B * Hkv, splits, R, D] fp32: sum_j exp2(x_j - m) v_j of the split; splits > 1 only
+  float* part_ml;      // [B * Hkv, splits, 2, 16] fp32: the split's (m, l) per row, log2 units; (-inf, 0): no visible key
+  long q_sb, q_ss, q_sh;
+  long k_sb, k_ss, k_sh;
+  long v_sb, v_ss, v_sh;
+  long o_sb, o_ss, o_sh;
+  int B, H, Hkv, Sq, Sk;
+  int D;
+  float scale;
+  float softcap;       // 0: none
+  int splits;          // in: 0 = let the launcher choose, n > 0 = asked for; out (dllm_attn_decode_plan): the count used
+  // filled by dllm_attn_decode_plan
+  int L;               // keys per split, a multiple of 128
+  int G;               // H / Hkv
+};

@@ -1,4 +1,4 @@
-// Attention (csrc/attn.hip, csrc/attn_f32.hip, csrc/attn_hd.hip, csrc/attn_wide.hip).
+// Attention (csrc/attn.hip, csrc/attn_f32.hip, csrc/attn_hd.hip, csrc/attn_wide.hip, csrc/attn_decode.hip).
 #include "bind_common.h"
 
 #include <cmath>
@@ -440,6 +440,62 @@ std::vector<Tensor> attn_wide_bwd(const Tensor& dout, const Tensor& q, const Ten
   return {dq, dk, dv, Tensor()};
 }
 
+// ---- csrc/attn_decode.hip: the decode-step forward (csrc/attn_params.h AttnDecodeParams).  Every clause of the
+// contract is checked here and refused by name; the partials of a split call are allocated here.
+const AttnFamily<AttnDecodeParams> kAttnDecode{at::kBFloat16, "attn_decode takes bf16", nullptr, nullptr,
+                                               "attn_decode", nullptr};  // forward only, one launcher pair of its own
+
+Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
+                   const optional<Tensor>& lut, double scale, double softcap, int64_t splits, bool causal) {
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "attn_decode: q / k / v must be [B, S, H, D]");
+  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3), Sk = k.size(1), Hkv = k.size(2);
+  TORCH_CHECK(D >= 32 && D <= 256 && D % 8 == 0,
+              "attn_decode: head dim must be in 32 .. 256 and a multiple of 8, got ", D);
+  TORCH_CHECK(Hkv > 0 && H % Hkv == 0, "attn_decode: the ", H, " query heads are no multiple of the ", Hkv,
+              " K/V heads");
+  TORCH_CHECK(Sq * (H / Hkv) <= 16, "attn_decode: R = Sq * (H / Hkv) = ", Sq * (H / Hkv),
+              " query rows per K/V head, at most 16 are served");
+  TORCH_CHECK(!causal || Sq == 1, "attn_decode: causal with Sq > 1 is not served (Sq = ", Sq, ")");
+  TORCH_CHECK(softcap >= 0.0 && std::isfinite(softcap), "attn_decode: softcap must be finite and >= 0, got ", softcap);
+  TORCH_CHECK(!(softcap > 0.0 && has(lut)), "attn_decode: a soft cap with a bias LUT is unsupported");
+  TORCH_CHECK(splits >= 0 && splits <= 65535, "attn_decode: splits must be 0 (auto) or a count up to 65535, got ",
+              splits);
+  TORCH_CHECK(B > 0 && Sq > 0 && Sk > 0, "attn_decode: empty attention");
+  TORCH_CHECK(B <= 65535 && Hkv <= 65535 && Sk < (1 << 30), "attn_decode: B or Hkv > 65535 or Sk >= 2^30 unsupported");
+  check_bshd(q, q, "q", B, Sq, H, D, kAttnDecode);
+  check_bshd(k, q, "k", B, Sk, Hkv, D, kAttnDecode);
+  check_bshd(v, q, "v", B, Sk, Hkv, D, kAttnDecode);
+  AttnDecodeParams p{};
+  set_view(q, p.q, p.q_sb, p.q_ss, p.q_sh);
+  set_view(k, p.k, p.k_sb, p.k_ss, p.k_sh);
+  set_view(v, p.v, p.v_sb, p.v_ss, p.v_sh);
+  p.B = B; p.H = H; p.Hkv = Hkv; p.Sq = Sq; p.Sk = Sk; p.D = D;
+  p.scale = (float)scale;
+  p.softcap = (float)softcap;
+  if (has(kpm))
+    TORCH_CHECK(kpm->dim() == 2 && kpm->size(0) == B && kpm->size(1) == Sk,
+                "key_padding_mask must be uint8 [B, Sk] contiguous on GPU");
+  p.kpm = flat_ptr<const uint8_t>(kpm, q, at::kByte, exactly(B * Sk), "key_padding_mask");
+  if (has(lut))
+    TORCH_CHECK(lut->dim() == 2 && lut->size(0) == H && lut->size(1) == Sq + Sk - 1,
+                "bias_lut must be fp32 [H, Sq + Sk - 1] contiguous on GPU");
+  p.lut = flat_ptr<const float>(lut, q, at::kFloat, exactly(H * (Sq + Sk - 1)), "bias_lut");
+  p.splits = (int)splits;
+  check_rc(dllm_attn_decode_plan(&p), "attn_decode_plan");
+  Tensor o = at::empty({B, Sq, H, D}, q.options());
+  set_view(o, p.o, p.o_sb, p.o_ss, p.o_sh);
+  Tensor part_o, part_ml;
+  if (p.splits > 1) {
+    auto f32 = q.options().dtype(at::kFloat);
+    part_o = at::empty({B * Hkv, p.splits, Sq * (H / Hkv), D}, f32);
+    part_ml = at::empty({B * Hkv, p.splits, 2, 16}, f32);
+    p.part_o = part_o.data_ptr<float>();
+    p.part_ml = part_ml.data_ptr<float>();
+  }
+  check_rc(dllm_attn_decode(&p, stream()), "attn_decode");
+  return o;
+}
+
 // ---- csrc/attn.hip: the same helpers, plus its extras (dropout bit planes, saturated-bias ranges, rowrec, column sums)
 // its K/V tile rings and key masks live in LDS (sequence length) and its plane / rowrec indices are 64-bit products
 void check_limits_attn(const AttnParams& p) {
@@ -590,6 +646,8 @@ void bind_attn(pybind11::module& m) {
         py::arg("k_glob") = py::none(), py::arg("k_gblk") = py::none(), py::arg("kl_ptr") = py::none(),
         py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none(),
         py::arg("softcap") = 0.0);
+  m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
+        py::arg("scale"), py::arg("softcap"), py::arg("splits") = 0, py::arg("causal") = false);
 }
 
 }  // namespace dllm

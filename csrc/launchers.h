@@ -122,6 +122,11 @@ int dllm_attn_hd_bwd(AttnHdParams* pp, hipStream_t st);
 // csrc/attn_wide.hip; < 0: a shape or combination the binding should have refused
 int dllm_attn_wide_fwd(AttnWideParams* pp, hipStream_t st);
 int dllm_attn_wide_bwd(AttnWideParams* pp, hipStream_t st);
+// csrc/attn_decode.hip.  plan: checks the shapes (< 0: one the binding should have refused) and sets splits (from the
+// count asked for, or for 0 from B * Hkv, Sk and the device's CU count), L and G; the binding then allocates the
+// partials for splits > 1 and calls dllm_attn_decode with the planned block
+int dllm_attn_decode_plan(AttnDecodeParams* pp);
+int dllm_attn_decode(const AttnDecodeParams* pp, hipStream_t st);
 
 // ---- csrc/rope.hip: rotate the `n` listed slots of x [B, S, *, H, D] in place (x_sn: the slot stride; strides in
 // elements); pos [B, S] (pos_sb = S) or [S] (pos_sb = 0); cos / sin fp32 [max_pos, D / 2]; sign -1: the backward

@@ -93,7 +93,7 @@ class BartAttention(nn.Module):
         return self.kv_proj(kv_in).view(B, S, 2, self.n_heads, self.head_dim)
 
     def forward(self, x, kv_in=None, mask=None, causal=False, p=0.0, cache=None, kv=None, residual=False, seg=None,
-                lists=None):
+                lists=None, decode=False):
         """Attention block output; with ``residual`` also ``x`` for the post-LN residual, its gradient accumulated by
         the input projection's dgrad GEMM (ops/linear.py linear_res).  ``lists``: the ops/attention.py BlockLists of a
         block-sparse self-attention (BigBird-Pegasus encoder)."""
@@ -117,7 +117,10 @@ class BartAttention(nn.Module):
             kv = kv if kv is not None else self.project_kv(kv_in)
             if kv.shape[0] != B:  # beam search: the nb hypotheses of a batch entry share its encoder K/V (read once)
                 q = q.reshape(kv.shape[0], (B // kv.shape[0]) * S, H, D)
-            o = attn_ops.attention_q_kv(q, kv, **kw)
+            if decode and seg is None and attn_ops.decode_step(q, kv[:, :, 0], p):  # a cached generation step
+                o = attn_ops.attention_decode(q, kv[:, :, 0], kv[:, :, 1], scale=self.scaling, key_padding_mask=mask)
+            else:
+                o = attn_ops.attention_q_kv(q, kv, **kw)
         else:
             if residual:
                 qkv, res = linear_res(x, self.qkv_proj)
@@ -126,7 +129,11 @@ class BartAttention(nn.Module):
                 qkv = self.qkv_proj(x).view(B, S, 3, H, D)
             if cache is not None:
                 k, v = cache.append(qkv[:, :, 1], qkv[:, :, 2])
-                o = attn_ops.attention(qkv[:, :, 0], k, v, **kw)
+                if lists is None and attn_ops.decode_step(qkv[:, :, 0], k, p, causal=causal):
+                    o = attn_ops.attention_decode(qkv[:, :, 0], k, v, scale=self.scaling, causal=causal,
+                                                  key_padding_mask=mask)
+                else:
+                    o = attn_ops.attention(qkv[:, :, 0], k, v, **kw)
             else:
                 o = attn_ops.attention_qkv(qkv, **kw)
         out = self.out_proj(o.reshape(B, S, H * D))
@@ -218,7 +225,7 @@ class BartLayer(nn.Module):
                                          p, rng.next_seed() if p > 0 else 0, xb)
         if self.is_decoder:
             c, h = self.encoder_attn(h, kv_in=enc_out, mask=enc_mask, p=pa, kv=cross_kv, residual=True,
-                                     seg=cross_seg)
+                                     seg=cross_seg, decode=cache is not None)
             h = norms.add_dropout_layer_norm(h, c, self.encoder_attn_layer_norm.weight,
                                              self.encoder_attn_layer_norm.bias, eps, p,
                                              rng.next_seed() if p > 0 else 0, xb)
@@ -246,7 +253,8 @@ class BartLayer(nn.Module):
             normed, h = norms.add_dropout_layer_norm_pre(h, a, self.encoder_attn_layer_norm.weight,
                                                          self.encoder_attn_layer_norm.bias, eps, p,
                                                          rng.next_seed() if p > 0 else 0, xb)
-            a = self.encoder_attn(normed, kv_in=enc_out, mask=enc_mask, p=pa, kv=cross_kv, seg=cross_seg)
+            a = self.encoder_attn(normed, kv_in=enc_out, mask=enc_mask, p=pa, kv=cross_kv, seg=cross_seg,
+                                  decode=cache is not None)
         normed, h = norms.add_dropout_layer_norm_pre(h, a, self.final_layer_norm.weight, self.final_layer_norm.bias,
                                                      eps, p, rng.next_seed() if p > 0 else 0, xb)
         f = ffn(normed, self.fc1, self.fc2, cfg.act, pact, rng.next_seed() if pact > 0 else 0)

@@ -11,8 +11,9 @@ generation_config uses all of them).
 
 MI355X specifics: the decoder self-attention cache is preallocated ``[B, max_len, H, D]`` (no
 per-step concatenation; the attention kernel reads the strided prefix view), cross-attention K/V are
-projected once per generate call, and every decode step runs the same fused kernels as training
-(attention with the bias LUT offset by the cache length).
+projected once per generate call, and every decode step's attention (the bias LUT offset by the cache
+length) is one split-key flash-decoding launch (csrc/attn_decode.hip, ops/attention.py attention_decode);
+the rest of the step runs the same fused kernels as training.
 """
 from __future__ import annotations
 

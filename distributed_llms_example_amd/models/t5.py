@@ -82,7 +82,8 @@ class T5Attention(nn.Module):
         B, S, _ = kv_in.shape
         return self.kv(kv_in).view(B, S, 2, self.n_heads, self.d_kv)
 
-    def forward(self, x, kv_in=None, mask=None, lut=None, causal=False, p=0.0, cache=None, kv=None, seg=None):
+    def forward(self, x, kv_in=None, mask=None, lut=None, causal=False, p=0.0, cache=None, kv=None, seg=None,
+                decode=False):
         B, S, _ = x.shape
         H, D = self.n_heads, self.d_kv
         seed = default_rng().next_seed() if p > 0 else 0
@@ -101,7 +102,10 @@ class T5Attention(nn.Module):
                 q = q.reshape(kv.shape[0], (B // kv.shape[0]) * S, H, D)
             # segment-masked kernels keep nothing length-bound in LDS: a packed call is never chunked
             chunk = long_sequence_chunk(kv.shape[1], cross=True) if seg is None else None
-            if chunk is not None:  # long encoder output: key-chunked blocks merged by LSE
+            if decode and seg is None and attn_ops.decode_step(q, kv[:, :, 0], p):
+                # a cached generation step: one pass over the encoder K/V at any length (csrc/attn_decode.hip)
+                o = attn_ops.attention_decode(q, kv[:, :, 0], kv[:, :, 1], scale=1.0, key_padding_mask=mask)
+            elif chunk is not None:  # long encoder output: key-chunked blocks merged by LSE
                 o = chunked_cross_attention(q, kv[:, :, 0], kv[:, :, 1], chunk=chunk, scale=1.0,
                                             key_padding_mask=mask, dropout_p=p, seed=seed)
             else:
@@ -119,7 +123,11 @@ class T5Attention(nn.Module):
             qkv = self.qkv(x).view(B, S, 3, H, D)
             if cache is not None:
                 k, v = cache.append(qkv[:, :, 1], qkv[:, :, 2])
-                o = attn_ops.attention(qkv[:, :, 0], k, v, **kw)
+                if self.window is None and attn_ops.decode_step(qkv[:, :, 0], k, p, causal=causal, bias_lut=lut):
+                    o = attn_ops.attention_decode(qkv[:, :, 0], k, v, scale=1.0, causal=causal, key_padding_mask=mask,
+                                                  bias_lut=lut)
+                else:
+                    o = attn_ops.attention(qkv[:, :, 0], k, v, **kw)
             else:
                 o = attn_ops.attention_qkv(qkv, **kw)
         return self.o(o.reshape(B, S, H * D))
@@ -278,7 +286,7 @@ class T5Stack(nn.Module):
         j = 1
         if self.is_decoder:
             c = subs[1].EncDecAttention(normed, kv_in=enc_out, mask=enc_mask, lut=None, causal=False, p=pa, kv=ckv,
-                                        seg=cross_seg)
+                                        seg=cross_seg, decode=cache is not None)
             normed, h = norms.add_dropout_rms_norm(h, c, norms_w[1], eps, p, rng.next_seed() if p > 0 else 0)
             j = 2
         f = subs[j].DenseReluDense(normed, p)

@@ -91,7 +91,7 @@ class T5GemmaAttention(nn.Module):
         """K or V ``[B, S, H_kv, D]`` with every head repeated for the query heads it serves."""
         return t if self.n_kv == self.n_heads else t.repeat_interleave(self.n_heads // self.n_kv, 2)
 
-    def forward(self, x, kv_in=None, mask=None, causal=False, p=0.0, cache=None, kv=None, rot=None):
+    def forward(self, x, kv_in=None, mask=None, causal=False, p=0.0, cache=None, kv=None, rot=None, decode=False):
         B, S, _ = x.shape
         H, K, D = self.n_heads, self.n_kv, self.d_kv
         seed = default_rng().next_seed() if p > 0 else 0
@@ -101,7 +101,13 @@ class T5GemmaAttention(nn.Module):
             kv = kv if kv is not None else self.project_kv(kv_in)
             if kv.shape[0] != B:  # beam search: the nb hypotheses of a batch entry share its encoder K/V (read once)
                 q = q.reshape(kv.shape[0], (B // kv.shape[0]) * S, H, D)
-            if attn_ops.grouped_served(q, D, softcap=self.softcap, dropout_p=p):  # csrc/attn_wide.hip: K / V as they are
+            # head dims 136 .. 256 stay on csrc/attn_wide.hip in cached steps too (tests/test_t5gemma_wide_gpu.py holds
+            # generate() to it); below that a cached step is csrc/attn_decode.hip on the H_kv heads as they are
+            wide = attn_ops.grouped_served(q, D, softcap=self.softcap, dropout_p=p)
+            if decode and not wide and attn_ops.decode_step(q, kv[:, :, 0], p, softcap=self.softcap):
+                o = attn_ops.attention_decode(q, kv[:, :, 0], kv[:, :, 1], scale=self.scale, key_padding_mask=mask,
+                                              softcap=self.softcap)
+            elif wide:  # K / V as they are
                 o = attn_ops.attention_grouped(q, kv[:, :, 0], kv[:, :, 1], **kw)
             elif K == H:
                 o = attn_ops.attention_q_kv(q, kv, **kw)
@@ -124,7 +130,11 @@ class T5GemmaAttention(nn.Module):
             v = qkv[..., (H + K) * D:].view(B, S, K, D)
             if cache is not None:
                 k, v = cache.append(k, v)
-            if wide:
+            if (cache is not None and not wide and self.window is None
+                    and attn_ops.decode_step(q, k, p, causal=causal, softcap=self.softcap)):
+                o = attn_ops.attention_decode(q, k, v, scale=self.scale, causal=causal, key_padding_mask=mask,
+                                              softcap=self.softcap)
+            elif wide:
                 o = attn_ops.attention_grouped(q, k, v, **kw)
             else:
                 o = attn_ops.attention(q, self._rep(k), self._rep(v), **kw)
@@ -241,7 +251,7 @@ class T5GemmaStack(nn.Module):
         if self.is_decoder:
             normed, h = norms.add_dropout_rms_norm(h, a, lyr.pre_cross_attn_layernorm.weight, eps, p, seed(),
                                                    offset=_OFF)
-            c = lyr.cross_attn(normed, kv_in=enc_out, mask=enc_mask, p=pa, kv=ckv)
+            c = lyr.cross_attn(normed, kv_in=enc_out, mask=enc_mask, p=pa, kv=ckv, decode=cache is not None)
             a = norms.rms_norm(c, lyr.post_cross_attn_layernorm.weight, eps, offset=_OFF)
         normed, h = norms.add_dropout_rms_norm(h, a, lyr.pre_feedforward_layernorm.weight, eps, p, seed(), offset=_OFF)
         f = lyr.mlp(normed, p)

@@ -816,3 +816,57 @@ def attention_grouped(q, k, v, *, scale: float = 1.0, causal: bool = False, key_
         k, v = k.repeat_interleave(G, 2), v.repeat_interleave(G, 2)
     return attention(q, k, v, scale=scale, causal=causal, key_padding_mask=key_padding_mask, dropout_p=dropout_p,
                      seed=seed, window=window, softcap=softcap)
+
+
+# --------------------------------------------------------------------------- decode steps (csrc/attn_decode.hip)
+
+
+def decode_served(q, k, *, causal: bool = False, bias_lut=None, softcap=None) -> bool:
+    """csrc/attn_decode.hip serves an :func:`attention_decode` call with this ``q`` ``[B,Sq,H,D]`` and ``k``
+    ``[B,Sk,H_kv,D]``: bf16 on the GPU, ``attn_decode`` = 1 (ops/routing.py), ``D % 8 == 0`` in 32 .. 256, at most 16
+    query rows per K/V head (``Sq * H / H_kv``), no causal mask over more than one query row (with one row and ``Sk``
+    the cache length it hides nothing) and no soft cap together with a bias LUT."""
+    if q.dim() != 4 or k.dim() != 4 or not _ext.use_native(q) or not routing.get("attn_decode"):
+        return False
+    Sq, H, D = q.shape[1:]
+    Hkv = k.shape[2]
+    return (q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 and 32 <= D <= 256 and D % 8 == 0 and Hkv > 0
+            and H % Hkv == 0 and Sq * (H // Hkv) <= 16 and not (causal and Sq > 1)
+            and not (softcap is not None and bias_lut is not None) and q.shape[0] <= 65535)
+
+
+def decode_step(q, k, p: float = 0.0, **kw) -> bool:
+    """What a model asks before a cached generation step: the call has no dropout, needs no gradient and
+    :func:`decode_served` holds (``kw``: its ``causal`` / ``bias_lut`` / ``softcap``).  False: the model's other path."""
+    return (p == 0.0 and not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad))
+            and decode_served(q, k, **kw))
+
+
+def attention_decode(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_mask=None, bias_lut=None,
+                     softcap: float | None = None):
+    """Attention of a generation step, forward only: q ``[B,Sq,H,D]`` (``Sq`` = 1, or the beams of a batch entry
+    against its shared encoder K/V), k / v ``[B,Sk,H_kv,D]`` as they are — views of the KV cache, slices of a fused
+    projection — with ``H % H_kv == 0`` (query head ``h`` reads K/V head ``h // (H // H_kv)``).  Where
+    :func:`decode_served` holds it is one split-key flash-decoding launch (csrc/attn_decode.hip; a second small one
+    merges the splits): K/V are read once per K/V head for all its query heads and beams.  Anything else — CPU
+    tensors, ``DLLM_REFERENCE_OPS=1``, ``attn_decode`` = 0, fp32, more than 16 rows per K/V head, unaligned rows —
+    computes what :func:`attention` / :func:`attention_grouped` compute for the call, K / V repeat included.
+    No autograd: an input that requires grad while grad is enabled raises."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, bias_lut)):
+        raise RuntimeError("attention_decode is forward only: call it under torch.no_grad() (generate does), or "
+                           "attention / attention_grouped for a call that needs gradients")
+    softcap = _check_softcap(softcap)
+    H, Hkv = q.shape[2], k.shape[2]
+    if Hkv <= 0 or H % Hkv or v.shape[2] != Hkv:
+        raise ValueError(f"attention_decode: {H} query heads over k / v with {Hkv} / {v.shape[2]} heads")
+    if (decode_served(q, k, causal=causal, bias_lut=bias_lut, softcap=softcap) and v.dtype == q.dtype
+            and all(_aligned(x) for x in (q, k, v))):
+        return _ext.native().attn_decode(q, k, v, _prep_kpm(key_padding_mask), bias_lut, float(scale),
+                                         softcap or 0.0, 0, bool(causal))
+    if Hkv != H and bias_lut is not None:  # attention_grouped takes no bias
+        k, v = k.repeat_interleave(H // Hkv, 2), v.repeat_interleave(H // Hkv, 2)
+    elif Hkv != H:
+        return attention_grouped(q, k, v, scale=scale, causal=causal, key_padding_mask=key_padding_mask,
+                                 softcap=softcap)
+    return attention(q, k, v, scale=scale, causal=causal, key_padding_mask=key_padding_mask, bias_lut=bias_lut,
+                     softcap=softcap)

@@ -83,6 +83,13 @@ dims 136 .. 256 (T5Gemma       dims 136 .. 256 (% 8 == 0), no dropout: csrc/attn
                                registers; with or without a window, a cap, causal; 0 and
                                anything else: ``attention`` on repeated K / V (at these
                                head dims the composite)
+decode-step attention          ``attention_decode`` (cached self-attention, cross-attention    attn_decode.txt
+(generate())                   of a step; k / v with H_kv heads as they are), bf16 at head
+                               dims 32 .. 256 (% 8 == 0), at most 16 query rows (beams x
+                               group heads) per K/V head: csrc/attn_decode.hip
+                               (``attn_decode`` = 1), the rows in one MFMA tile, the key
+                               axis split over workgroups, splits merged in fixed order;
+                               0 and anything else: ``attention`` / ``attention_grouped``
 segment-masked attention       as the window: bf16 (head dim 64 included) on                 attn_segments_vs_masked.txt
 (sequence packing)             csrc/attn_hd.hip, fp32 at head dim 64 on csrc/attn_f32.hip;
                                blocks of other segments are skipped by per-block (min,
@@ -171,6 +178,7 @@ DEFAULTS: dict = {
     "attn_hd": 1,                 # bf16 head dims 32 .. 128 other than 64 on csrc/attn_hd.hip (0: composite)
     "attn_lists": 1,              # block-list calls on csrc/attn_hd.hip / csrc/attn_f32.hip (0: composite)
     "attn_wide": 1,               # attention_grouped at bf16 head dims 136 .. 256 on csrc/attn_wide.hip (0: fallback)
+    "attn_decode": 1,             # cached generation steps on csrc/attn_decode.hip (0: the training forward kernels)
     "attn_chunk": 0,              # 0: 8192 rows for < 32 rows per head, else 4096
     "attn_chunk_min": 8192,
     # weight-gradient side stream (ops/streams.py)

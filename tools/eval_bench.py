@@ -1,7 +1,8 @@
 """Eval-generation throughput: ``generate(num_beams=2, max_length=128)`` over 818 SAMSum-test-shaped samples
 (ref/train-accelerator.py:239-249).  Modes: ``fused`` = device-side beam bookkeeping with the one-kernel beam step
 (csrc/beam.hip), ``device`` = the same with the torch composite step (DLLM_ROUTE gen_fused_beam=0), ``host`` = the
-per-step host loop (gen_host=1).
+per-step host loop (gen_host=1), ``nodecode`` = ``fused`` with the decode steps' attention on the training forward
+kernels (attn_decode=0; ``fused`` runs csrc/attn_decode.hip).  ``--repeat N`` runs the mode list N times, interleaved.
 
     python tools/eval_bench.py [--model t5-base] [--batch 64] [--src-len 512] [--n 818] [--modes fused,device,host]
 Synthetic prompts (random ids, ragged attention masks) and random-init weights; prints one JSON line per mode.
@@ -27,6 +28,7 @@ def main():
     ap.add_argument("--beams", type=int, default=2)
     ap.add_argument("--max-length", type=int, default=128)
     ap.add_argument("--modes", default="fused,device,host")
+    ap.add_argument("--repeat", type=int, default=1)
     a = ap.parse_args()
     torch.manual_seed(0)
     cfg = resolve_config(a.model)
@@ -35,9 +37,10 @@ def main():
     ids = torch.randint(3, cfg.vocab_size, (a.n, a.src_len), generator=g)
     lens = torch.randint(a.src_len // 4, a.src_len + 1, (a.n,), generator=g)
     am = (torch.arange(a.src_len)[None, :] < lens[:, None]).long()
-    for mode in a.modes.split(","):
+    for mode in a.modes.split(",") * a.repeat:
         os.environ["DLLM_ROUTE"] = (f"gen_host={1 if mode == 'host' else 0},"
-                                    f"gen_fused_beam={1 if mode == 'fused' else 0}")
+                                    f"gen_fused_beam={1 if mode in ('fused', 'nodecode') else 0},"
+                                    f"attn_decode={0 if mode == 'nodecode' else 1}")
         m.generate(ids[:a.batch].cuda(), attention_mask=am[:a.batch].cuda(), max_length=8, num_beams=a.beams)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
