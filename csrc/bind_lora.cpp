@@ -37,9 +37,10 @@ Tensor lora_down(const Tensor& x, const Tensor& A, double alpha, double p, int64
   return t;
 }
 
-// y[:, c0:c0+n] += alpha * (keep .) (t M): t [N, r]; M [n, r], or [r, n] with kmajor; y [N, ld] in place
+// y[:, c0:c0+n] += alpha * (keep .) (t M): t [N, r]; M [n, r], or [r, n] with kmajor; y [N, ld] in place.
+// With c (fp32 [n], DoRA): y[:, c0:c0+n] = c . ((y[:, c0:c0+n] - bias) + the update) + bias, bias bf16 [n] or none.
 void lora_up(const Tensor& t, const Tensor& M, bool kmajor, double alpha, Tensor& y, int64_t c0, int64_t n, double p,
-             int64_t seed, int64_t row0) {
+             int64_t seed, int64_t row0, const optional<Tensor>& c, const optional<Tensor>& bias) {
   const auto yr = lora_wide<void>(y, y, "lora_up", "y");
   const void* tp = lora_small(t, y, t.dim() == 2 ? t.size(1) : 0, "lora_up", "t");
   const int64_t r = t.size(1);
@@ -51,8 +52,11 @@ void lora_up(const Tensor& t, const Tensor& M, bool kmajor, double alpha, Tensor
   TORCH_CHECK(kmajor ? (M.size(0) == r && M.size(1) == n) : (M.size(0) == n && M.size(1) == r),
               "lora_up: M must be ", kmajor ? "[r, n]" : "[n, r]", ", got ", M.sizes());
   TORCH_CHECK(p >= 0.0 && p < 1.0, "lora_up: p must be in [0, 1)");
+  TORCH_CHECK(has(c) || !has(bias), "lora_up: a bias is taken only with the DoRA scale c");
+  const float* cp = flat_ptr<const float>(c, y, at::kFloat, exactly(n), "lora_up: c");
+  const void* bp = flat_ptr<const void>(bias, y, at::kBFloat16, exactly(n), "lora_up: bias");
   check_rc(dllm_lora_up(tp, (int)r, Mp, kmajor ? 1 : 0, yr.ptr, yr.ld, (int)c0, (int)n, (int)y.size(0), (float)alpha,
-                        (float)p, (uint32_t)seed, (uint32_t)row0, stream()),
+                        (float)p, (uint32_t)seed, (uint32_t)row0, cp, bp, stream()),
            "lora_up");
 }
 
@@ -83,6 +87,65 @@ void lora_wgrad(const Tensor& W, const Tensor& S, double alpha, Tensor& G, bool 
            "lora_wgrad");
 }
 
+// ---- DoRA
+// norm [n] (fp32) of the rows of W[c0:c0+n] + s B A: W [out, K] bf16 (rows may be strided), A [r, K], B [n, r].  With m
+// [n] (bf16 or fp32) and c (fp32 [n], e.g. a slice of the layer's scale vector): c = m / norm is written too.
+Tensor dora_norm(const Tensor& W, int64_t c0, const Tensor& A, const Tensor& B, double s, const optional<Tensor>& m,
+                 optional<Tensor> c) {
+  const auto Wr = lora_wide<const void>(W, W, "dora_norm", "W");
+  const int64_t r = A.dim() == 2 ? A.size(0) : 0;
+  const void* Ap = lora_small(A, W, r, "dora_norm", "A");
+  const void* Bp = lora_small(B, W, r, "dora_norm", "B");
+  const int64_t n = B.size(0), K = W.size(1);
+  TORCH_CHECK(A.size(1) == K && B.size(1) == r, "dora_norm: A must be [r, K] and B [n, r], got ", A.sizes(), " and ",
+              B.sizes(), " for W ", W.sizes());
+  TORCH_CHECK(c0 >= 0 && n > 0 && c0 + n <= W.size(0), "dora_norm: the rows [c0, c0 + n) must lie inside W, got c0 ",
+              c0, " n ", n, " of ", W.size(0));
+  TORCH_CHECK(has(m) || !has(c), "dora_norm: c = m / norm needs m");
+  const void* mp = flat_ptr<const void>(m, W, {at::kFloat, at::kBFloat16}, exactly(n), "dora_norm: m");
+  float* cp = has(c) ? flat_ptr<float>(*c, W, at::kFloat, exactly(n), "dora_norm: c") : nullptr;
+  auto norm = at::empty({n}, W.options().dtype(at::kFloat));
+  const uint16_t* w0 = static_cast<const uint16_t*>(Wr.ptr) + c0 * Wr.ld;
+  check_rc(dllm_dora_norm(w0, Wr.ld, Ap, Bp, (int)n, (int)K, (int)r, (float)s, mp,
+                          has(m) && m->scalar_type() == at::kBFloat16 ? 1 : 0, norm.data_ptr<float>(), cp, stream()),
+           "dora_norm");
+  return norm;
+}
+
+// (dY' = c_full . dY [N, C] bf16, partials [splits, C] fp32 of dY . (y - bias) over lora_wgrad's token splits, zero on
+// the columns whose live8 byte is 0): c_full fp32 [C], live8 uint8 [C / 8], bias bf16 [C] or none
+std::tuple<Tensor, Tensor> dora_bwd(const Tensor& dy, const Tensor& y, const Tensor& c_full, const Tensor& live8,
+                                    const optional<Tensor>& bias) {
+  const auto dr = lora_wide<const void>(dy, dy, "dora_bwd", "dy");
+  const auto yr = lora_wide<const void>(y, dy, "dora_bwd", "y");
+  const int64_t N = dy.size(0), C = dy.size(1);
+  TORCH_CHECK(y.size(0) == N && y.size(1) == C, "dora_bwd: dy and y need the same shape");
+  const float* cp = flat_ptr<const float>(c_full, dy, at::kFloat, exactly(C), "dora_bwd: c_full");
+  const uint8_t* lp = flat_ptr<const uint8_t>(live8, dy, at::kByte, exactly(C / 8), "dora_bwd: live8");
+  const void* bp = flat_ptr<const void>(bias, dy, at::kBFloat16, exactly(C), "dora_bwd: bias");
+  const auto sp = lora_wgrad_splits(N);
+  auto out = at::empty({N, C}, dy.options());
+  auto part = at::empty({sp[0], C}, dy.options().dtype(at::kFloat));
+  if (N == 0) return {out, part};
+  check_rc(dllm_dora_bwd(dr.ptr, dr.ld, yr.ptr, yr.ld, cp, lp, bp, out.data_ptr(), C, part.data_ptr<float>(), (int)N,
+                         (int)C, (int)sp[1], stream()),
+           "dora_bwd");
+  return {out, part};
+}
+
+// sink [n] (fp32 or bf16) += (sum of part[:, c0:c0+n] over the splits, in order) / m
+void dora_dm(const Tensor& part, int64_t c0, const Tensor& m, Tensor& sink) {
+  const float* pp = flat_ptr<const float>(part, part, at::kFloat, at_least(0), "dora_dm: part");
+  TORCH_CHECK(part.dim() == 2, "dora_dm: part must be [splits, C]");
+  const int64_t n = m.numel(), C = part.size(1);
+  TORCH_CHECK(c0 >= 0 && n > 0 && c0 + n <= C, "dora_dm: the columns [c0, c0 + n) must lie inside part");
+  const void* mp = flat_ptr<const void>(m, part, {at::kFloat, at::kBFloat16}, exactly(n), "dora_dm: m");
+  void* sp = flat_ptr<void>(sink, part, {at::kFloat, at::kBFloat16}, exactly(n), "dora_dm: sink");
+  check_rc(dllm_dora_dm(pp, (int)part.size(0), (int)C, (int)c0, (int)n, mp, m.scalar_type() == at::kBFloat16 ? 1 : 0,
+                        sp, sink.scalar_type() == at::kBFloat16 ? 1 : 0, stream()),
+           "dora_dm");
+}
+
 }  // namespace
 
 void bind_lora(pybind11::module& m) {
@@ -90,7 +153,13 @@ void bind_lora(pybind11::module& m) {
         py::arg("alpha") = 1.0, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("row0") = 0);
   m.def("lora_up", &lora_up, "y[:, c0:c0+n] += alpha * (keep .) (t M), in place", py::arg("t"), py::arg("M"),
         py::arg("kmajor"), py::arg("alpha"), py::arg("y"), py::arg("c0"), py::arg("n"), py::arg("p") = 0.0,
-        py::arg("seed") = 0, py::arg("row0") = 0);
+        py::arg("seed") = 0, py::arg("row0") = 0, py::arg("c") = py::none(), py::arg("bias") = py::none());
+  m.def("dora_norm", &dora_norm, "row norms of W[c0:c0+n] + s B A (and c = m / norm)", py::arg("W"), py::arg("c0"),
+        py::arg("A"), py::arg("B"), py::arg("s"), py::arg("m") = py::none(), py::arg("c") = py::none());
+  m.def("dora_bwd", &dora_bwd, "(c_full . dY, split partials of dY . (y - bias)) in one pass", py::arg("dy"),
+        py::arg("y"), py::arg("c_full"), py::arg("live8"), py::arg("bias") = py::none());
+  m.def("dora_dm", &dora_dm, "sink += (partials summed in split order) / m", py::arg("part"), py::arg("c0"),
+        py::arg("m"), py::arg("sink"));
   m.def("lora_wgrad", &lora_wgrad, "G (+)= alpha * (keep . W)^T S over tokens, fixed splits summed in order",
         py::arg("W"), py::arg("S"), py::arg("alpha"), py::arg("G"), py::arg("wide_major"), py::arg("beta") = true,
         py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("row0") = 0);

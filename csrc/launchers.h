@@ -157,11 +157,19 @@ int dllm_lora_wgrad_max_splits();
 int dllm_lora_wgrad_split_rows(long N);
 int dllm_lora_down(const void* x, long ldx, const void* A, void* t, int N, int K, int r, float alpha, float p,
                    uint32_t seed, uint32_t row0, hipStream_t st);
+// cvec / bias: the DoRA scale (fp32 [n]) and bias (bf16 [n] or null) of the slice; cvec null: the plain update
 int dllm_lora_up(const void* t, int r, const void* M, int kmajor, void* y, long ld, int c0, int n, int N, float alpha,
-                 float p, uint32_t seed, uint32_t row0, hipStream_t st);
+                 float p, uint32_t seed, uint32_t row0, const float* cvec, const void* bias, hipStream_t st);
 int dllm_lora_wgrad(const void* Wd, long ldw, int wc, const void* S, int r, float* part, int N, int rows_per_split,
                     int wide_major, void* G, int g_bf16, float alpha, int beta, float p, uint32_t seed, uint32_t row0,
                     hipStream_t st);
+// DoRA: row norms of W_s + s B A (W: the slice's first row), the layer's gradient pass and the magnitude gradient
+int dllm_dora_norm(const void* W, long ldw, const void* A, const void* B, int n, int K, int r, float s, const void* m,
+                   int m_bf16, float* norm, float* cvec, hipStream_t st);
+int dllm_dora_bwd(const void* dy, long lddy, const void* y, long ldy, const float* cfull, const uint8_t* live8,
+                  const void* bias, void* out, long ldo, float* part, int N, int C, int rows_per_split, hipStream_t st);
+int dllm_dora_dm(const float* part, int splits, int C, int c0, int n, const void* m, int m_bf16, void* sink,
+                 int sink_bf16, hipStream_t st);
 
 // ---- csrc/nf4.hip: W [N][K] as codes uint8 [N][K/2] + absmax fp32 [N][K/64] (N, K % 64 == 0; ops/nf4.py)
 int dllm_nf4_decode_rows();

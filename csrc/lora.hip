@@ -18,6 +18,20 @@
 //           sums the splits in ascending order into G (fp32 or bf16, beta = 1).  No atomics: bitwise reproducible.
 //           Both operands are token-major, so the 64-token chunks are staged row-major in LDS and read through the
 //           hardware-transposed ds_read_b64_tr_b16 (the key order of csrc/attn_hd.hip ld_tr2, the same for both).
+//
+// DoRA (weight-decomposed adapters, ops/lora.py): the slice's output is c . (x W_s^T + s t B^T) + b with
+// c = m / ||W_s + s B A|| per output row.
+//   norm    norm[j] = ||W_s[j, :] + s (B A)[j, :]||, c[j] = m[j] / norm[j].  A workgroup owns 16 rows of the slice and
+//           walks K in 256-column chunks, 64 columns per wave.  Its B rows are the stationary MFMA operand (registers);
+//           the A chunk is staged row-major in LDS, its columns permuted in groups of 4 so that the transposed reads
+//           hand every lane the B A values of 8 CONSECUTIVE columns of one row: the matching W values are one 16-B
+//           load, added in fp32, squared and summed per lane.  One cross-lane and one cross-wave sum at the end.  W is
+//           read once and nothing of size [n, K] is written.
+//   up      the DORA arm of lora_up_k: y = c . ((y - b) + alpha t B^T) + b in the same read and write of the slice.
+//   bwd     dY' = c_full . dY for the whole layer (c_full = 1 on columns without a DoRA adapter) and, on the DoRA
+//           columns, per-column partials of dY . (y - b) over the token splits of wgrad: a lane owns 8 columns and
+//           walks rows, the 16 row walkers of a workgroup are summed by shuffles and through LDS.  dora_dm_k sums the
+//           splits in ascending order, divides by m and adds into m's gradient sink.  No atomics.
 #include "common.h"
 
 using namespace dllm;
@@ -115,10 +129,12 @@ __global__ __launch_bounds__(256) void lora_down_k(const uint16_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------- up
-template <int KS>  // 32-wide steps over the padded rank
+// DORA: cvec [n] (fp32) and bias [n] (bf16, or null) of the slice; y = cvec . ((y - bias) + update) + bias
+template <int KS, bool DORA>  // 32-wide steps over the padded rank
 __global__ __launch_bounds__(256) void lora_up_k(const uint16_t* __restrict__ t, int r, const uint16_t* __restrict__ M,
                                                  int kmajor, uint16_t* __restrict__ y, long ld, int c0, int n, int N,
-                                                 float alpha, uint32_t seed, uint32_t t2, int drop, uint32_t row0) {
+                                                 float alpha, uint32_t seed, uint32_t t2, int drop, uint32_t row0,
+                                                 const float* __restrict__ cvec, const uint16_t* __restrict__ bias) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int j0 = blockIdx.y * 64;
   const long wtok0 = (long)blockIdx.x * 512 + w * 128;
@@ -145,6 +161,17 @@ __global__ __launch_bounds__(256) void lora_up_k(const uint16_t* __restrict__ t,
       }
       mf[tl][ks] = as_op(v);
     }
+  }
+  float cr[2][8], br[2][8];  // DORA: the scale and bias of this lane's 2 x 8 columns
+  if constexpr (DORA) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int j = j0 + 32 * u + 8 * g + q;
+        cr[u][q] = j < n ? cvec[j] : 0.f;
+        br[u][q] = (j < n && bias != nullptr) ? bf2f(bias[j]) : 0.f;
+      }
   }
   const bool vecT = (r & 7) == 0;
   const uint32_t es = drop ? eff_seed(seed) : 0u;
@@ -187,6 +214,18 @@ __global__ __launch_bounds__(256) void lora_up_k(const uint16_t* __restrict__ t,
           if (d3 >> 16) hi.w = 0.f;
         }
         u32x4 out;
+        if constexpr (DORA) {
+          float o[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q)
+            o[q] = cr[u][q] * ((bf2f(old[q]) - br[u][q]) + (q < 4 ? lo[q] : hi[q - 4])) + br[u][q];
+          out.x = pack_bf16x2(o[0], o[1]);
+          out.y = pack_bf16x2(o[2], o[3]);
+          out.z = pack_bf16x2(o[4], o[5]);
+          out.w = pack_bf16x2(o[6], o[7]);
+          *reinterpret_cast<u32x4*>(yp) = out;
+          continue;
+        }
         out.x = pack_bf16x2(bf2f(old[0]) + lo.x, bf2f(old[1]) + lo.y);
         out.y = pack_bf16x2(bf2f(old[2]) + lo.z, bf2f(old[3]) + lo.w);
         out.z = pack_bf16x2(bf2f(old[4]) + hi.x, bf2f(old[5]) + hi.y);
@@ -300,6 +339,148 @@ __global__ __launch_bounds__(256) void lora_wgrad_reduce_k(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------------- dora
+DLLM_DEVICE float ld_m(const void* m, int m_bf16, long j) {
+  return m_bf16 ? bf2f(reinterpret_cast<const uint16_t*>(m)[j]) : reinterpret_cast<const float*>(m)[j];
+}
+
+template <int KS>  // 32-wide steps over the padded rank
+__global__ __launch_bounds__(256) void dora_norm_k(const uint16_t* __restrict__ W, long ldw,
+                                                   const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, int n,
+                                                   int K, int r, float s, const void* __restrict__ m, int m_bf16,
+                                                   float* __restrict__ norm, float* __restrict__ cvec) {
+  constexpr int CH = 256, LD = CH + 8, RP = 32 * KS;  // chunk columns, image row stride (16-B pad), padded rank
+  __shared__ __attribute__((aligned(16))) uint16_t img[RP * LD];
+  __shared__ float red[4][16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
+  const int j0 = blockIdx.x * 16, row = j0 + c;
+  const bool live = row < n;
+  // the stationary operand: row `row` of B in ld_tr's key order (elements 0..3: rank 32 ks + 4g + {0..3}, elements
+  // 4..7: 16 further on), zeros past r and past n
+  bf16x8v bfr[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int rho = 32 * ks + 16 * (q >> 2) + 4 * g + (q & 3);
+      if (live && rho < r) v[q] = B[(long)row * r + rho];
+    }
+    bfr[ks] = as_op(v);
+  }
+  const uint16_t* wrow = W + (long)(live ? row : 0) * ldw;
+  float ss = 0.f;
+  for (int k0 = 0; k0 < K; k0 += CH) {  // block-uniform bounds: the barriers stay matched, EXEC stays full
+    u16x8 wv[2];  // W[row][k0 + 64 w + 32 u + 8 g .. + 7], in flight under the staging
+#pragma unroll
+    for (int u = 0; u < 2; ++u) wv[u] = ld8(wrow, k0 + 64 * w + 32 * u + 8 * g, live ? K : 0, true);
+    __syncthreads();
+    // A[:, k0 .. k0 + 255] row-major; inside every 32 columns the 4-column group 2a + e sits at group 4e + a, so that
+    // operand row c' of the 16-column tile e is column 8 (c' >> 2) + 4e + (c' & 3)
+    for (int idx = tid; idx < RP * 32; idx += 256) {
+      const int rho = idx >> 5, ch = idx & 31;
+      const u16x8 v = ld8(A + (long)(rho < r ? rho : 0) * K, k0 + 8 * ch, rho < r ? K : 0, true);
+      uint16_t* dst = img + rho * LD + 32 * (ch >> 2) + 4 * (ch & 3);
+      *reinterpret_cast<u16x4*>(dst) = u16x4{v[0], v[1], v[2], v[3]};
+      *reinterpret_cast<u16x4*>(dst + 16) = u16x4{v[4], v[5], v[6], v[7]};
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        d0 = mma(ld_tr(img, LD, 32 * ks, 64 * w + 32 * u, c, g), bfr[ks], d0);
+        d1 = mma(ld_tr(img, LD, 32 * ks, 64 * w + 32 * u + 16, c, g), bfr[ks], d1);
+      }
+      // d0[i] / d1[i] = (B A)[row][k0 + 64 w + 32 u + 8 g + i / + 4 + i]
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float v0 = bf2f(wv[u][i]) + s * d0[i], v1 = bf2f(wv[u][4 + i]) + s * d1[i];
+        ss += v0 * v0;
+        ss += v1 * v1;
+      }
+    }
+  }
+  ss += __shfl_xor(ss, 16);
+  ss += __shfl_xor(ss, 32);
+  if (g == 0) red[w][c] = ss;
+  __syncthreads();
+  if (tid < 16 && j0 + tid < n) {
+    const float nm = sqrtf(((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid]);
+    norm[j0 + tid] = nm;
+    if (cvec != nullptr) cvec[j0 + tid] = ld_m(m, m_bf16, j0 + tid) / nm;
+  }
+}
+
+// grid (128-column strips, token splits); live8[C / 8]: the 8-column group carries a DoRA adapter
+__global__ __launch_bounds__(256) void dora_bwd_k(const uint16_t* __restrict__ dy, long lddy,
+                                                  const uint16_t* __restrict__ y, long ldy,
+                                                  const float* __restrict__ cfull, const uint8_t* __restrict__ live8,
+                                                  const uint16_t* __restrict__ bias, uint16_t* __restrict__ out,
+                                                  long ldo, float* __restrict__ part, int N, int C,
+                                                  int rows_per_split) {
+  __shared__ float red[4][128];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
+  const int col = blockIdx.x * 128 + 8 * c;
+  const bool colok = col < C;  // C % 8 == 0: all 8 columns or none
+  const bool dora = colok && live8[col >> 3] != 0;
+  const long t_begin = (long)blockIdx.y * rows_per_split;
+  const long t_end = t_begin + rows_per_split < N ? t_begin + rows_per_split : N;
+  float cr[8], br[8], acc[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    cr[q] = colok ? cfull[col + q] : 0.f;
+    br[q] = (dora && bias != nullptr) ? bf2f(bias[col + q]) : 0.f;
+    acc[q] = 0.f;
+  }
+  if (colok) {
+    for (long tok = t_begin + 4 * w + g; tok < t_end; tok += 16) {
+      const u16x8 d = *reinterpret_cast<const u16x8*>(dy + tok * lddy + col);
+      u32x4 o;
+      o.x = pack_bf16x2(cr[0] * bf2f(d[0]), cr[1] * bf2f(d[1]));
+      o.y = pack_bf16x2(cr[2] * bf2f(d[2]), cr[3] * bf2f(d[3]));
+      o.z = pack_bf16x2(cr[4] * bf2f(d[4]), cr[5] * bf2f(d[5]));
+      o.w = pack_bf16x2(cr[6] * bf2f(d[6]), cr[7] * bf2f(d[7]));
+      *reinterpret_cast<u32x4*>(out + tok * ldo + col) = o;
+      if (dora) {
+        const u16x8 yv = *reinterpret_cast<const u16x8*>(y + tok * ldy + col);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[q] += bf2f(d[q]) * (bf2f(yv[q]) - br[q]);
+      }
+    }
+  }
+  // the 4 row walkers of the wave, then the 4 waves in order
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    acc[q] += __shfl_xor(acc[q], 16);
+    acc[q] += __shfl_xor(acc[q], 32);
+  }
+  if (g == 0) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) red[w][8 * c + q] = acc[q];
+  }
+  __syncthreads();
+  if (tid < 128 && blockIdx.x * 128 + tid < C)
+    part[(long)blockIdx.y * C + blockIdx.x * 128 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// sink[j] += (sum over splits, ascending, of part[split][c0 + j]) / m[j]
+__global__ __launch_bounds__(256) void dora_dm_k(const float* __restrict__ part, int splits, int C, int c0, int n,
+                                                 const void* __restrict__ m, int m_bf16, void* sink, int sink_bf16) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  float s = 0.f;
+  for (int sp = 0; sp < splits; ++sp) s += part[(long)sp * C + c0 + j];
+  s /= ld_m(m, m_bf16, j);
+  if (sink_bf16) {
+    uint16_t* p = reinterpret_cast<uint16_t*>(sink) + j;
+    *p = f2bf(bf2f(*p) + s);
+  } else {
+    reinterpret_cast<float*>(sink)[j] += s;
+  }
+}
+
 }  // namespace
 
 extern "C" int dllm_lora_wgrad_rows() { return kWgradRows; }
@@ -334,19 +515,26 @@ extern "C" int dllm_lora_down(const void* x, long ldx, const void* A, void* t, i
   return 0;
 }
 
+// cvec: null (the plain update), or the DoRA scale [n] of the slice with its bias [n] (bf16, may be null)
 extern "C" int dllm_lora_up(const void* t, int r, const void* M, int kmajor, void* y, long ld, int c0, int n, int N,
-                            float alpha, float p, uint32_t seed, uint32_t row0, hipStream_t st) {
+                            float alpha, float p, uint32_t seed, uint32_t row0, const float* cvec, const void* bias,
+                            hipStream_t st) {
   if (N <= 0 || n <= 0) return 0;
   const int drop = p > 0.f;
   const uint32_t t2 = rw_t2(drop_threshold(p));
   const dim3 grid((N + 511) / 512, (n + 63) / 64), block(256);
   if (r < 1 || r > 64 || grid.y > 65535) return -1;
-  if (r <= 32)
-    lora_up_k<1><<<grid, block, 0, st>>>((const uint16_t*)t, r, (const uint16_t*)M, kmajor, (uint16_t*)y, ld, c0, n, N,
-                                         alpha, seed, t2, drop, row0);
-  else
-    lora_up_k<2><<<grid, block, 0, st>>>((const uint16_t*)t, r, (const uint16_t*)M, kmajor, (uint16_t*)y, ld, c0, n, N,
-                                         alpha, seed, t2, drop, row0);
+#define DLLM_LORA_UP(KS, D)                                                                                         \
+  lora_up_k<KS, D><<<grid, block, 0, st>>>((const uint16_t*)t, r, (const uint16_t*)M, kmajor, (uint16_t*)y, ld, c0, n, \
+                                           N, alpha, seed, t2, drop, row0, cvec, (const uint16_t*)bias)
+  if (cvec == nullptr) {
+    if (r <= 32) DLLM_LORA_UP(1, false);
+    else DLLM_LORA_UP(2, false);
+  } else {
+    if (r <= 32) DLLM_LORA_UP(1, true);
+    else DLLM_LORA_UP(2, true);
+  }
+#undef DLLM_LORA_UP
   DLLM_CHECK_LAUNCH();
   return 0;
 }
@@ -377,6 +565,46 @@ extern "C" int dllm_lora_wgrad(const void* Wd, long ldw, int wc, const void* S, 
   const long numel = (long)wc * r;
   lora_wgrad_reduce_k<<<dim3((unsigned)((numel + 255) / 256)), block, 0, st>>>(part, splits, numel, G, g_bf16, alpha,
                                                                               beta);
+  DLLM_CHECK_LAUNCH();
+  return 0;
+}
+
+// W: the first row of the slice (row stride ldw); norm [n] fp32; cvec [n] fp32 = m / norm, or null (then m is unused)
+extern "C" int dllm_dora_norm(const void* W, long ldw, const void* A, const void* B, int n, int K, int r, float s,
+                              const void* m, int m_bf16, float* norm, float* cvec, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (r < 1 || r > 64 || K <= 0 || (K & 7) || (ldw & 7) || (cvec != nullptr && m == nullptr)) return -1;
+  const dim3 grid((n + 15) / 16), block(256);
+  if (r <= 32)
+    dora_norm_k<1><<<grid, block, 0, st>>>((const uint16_t*)W, ldw, (const uint16_t*)A, (const uint16_t*)B, n, K, r, s,
+                                           m, m_bf16, norm, cvec);
+  else
+    dora_norm_k<2><<<grid, block, 0, st>>>((const uint16_t*)W, ldw, (const uint16_t*)A, (const uint16_t*)B, n, K, r, s,
+                                           m, m_bf16, norm, cvec);
+  DLLM_CHECK_LAUNCH();
+  return 0;
+}
+
+// out [N, C] = cfull . dy; part: fp32 [splits, C], splits = ceil(N / rows_per_split), every element written
+extern "C" int dllm_dora_bwd(const void* dy, long lddy, const void* y, long ldy, const float* cfull,
+                             const uint8_t* live8, const void* bias, void* out, long ldo, float* part, int N, int C,
+                             int rows_per_split, hipStream_t st) {
+  if (N <= 0 || C <= 0) return 0;
+  if ((C & 7) || (lddy & 7) || (ldy & 7) || (ldo & 7) || rows_per_split <= 0) return -1;
+  const int splits = (N + rows_per_split - 1) / rows_per_split;
+  if (splits > 65535) return -1;
+  dora_bwd_k<<<dim3((C + 127) / 128, splits), dim3(256), 0, st>>>(
+      (const uint16_t*)dy, lddy, (const uint16_t*)y, ldy, cfull, live8, (const uint16_t*)bias, (uint16_t*)out, ldo,
+      part, N, C, rows_per_split);
+  DLLM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dllm_dora_dm(const float* part, int splits, int C, int c0, int n, const void* m, int m_bf16, void* sink,
+                            int sink_bf16, hipStream_t st) {
+  if (n <= 0 || splits <= 0) return 0;
+  if (c0 < 0 || c0 + n > C) return -1;
+  dora_dm_k<<<dim3((n + 255) / 256), dim3(256), 0, st>>>(part, splits, C, c0, n, m, m_bf16, sink, sink_bf16);
   DLLM_CHECK_LAUNCH();
   return 0;
 }

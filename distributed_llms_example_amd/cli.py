@@ -91,6 +91,9 @@ def base_parser(description: str, defaults: dict | None = None) -> argparse.Argu
                    help="comma list of adapted projections out of q,k,v,o,wi,wo")
     g.add_argument("--lora-quant", type=str, default=None,
                    help="nf4: QLoRA, hold the frozen attention and FFN projections as 4-bit NF4 codes (needs --lora-r)")
+    g.add_argument("--lora-dora", action="store_true",
+                   help="DoRA: every adapter also trains a magnitude per output row, the slice's output is rescaled by "
+                        "magnitude / row norm of the adapted weight (needs --lora-r; not with --lora-quant)")
     g.add_argument("--teacher-ckpt", type=str, default=None,
                    help="distil from this frozen teacher (anything --model-ckpt takes): the training loss becomes "
                         "(1 - kd-alpha) CE + kd-alpha T^2 KL(teacher || student); evaluation and the saved model are "
@@ -274,21 +277,26 @@ def maybe_apply_lora(model, args, log_fn=None):
     """``--lora-r N``: freeze ``model`` and attach adapters (models/lora.py) — before the engine is built — and log the
     trainable / total parameter counts once.  Without the flag the model is returned untouched."""
     quant = getattr(args, "lora_quant", None)
+    dora = bool(getattr(args, "lora_dora", False))
     if not getattr(args, "lora_r", 0):
         if quant:
             raise ValueError("--lora-quant needs --lora-r: only a frozen base under adapters is quantised")
+        if dora:
+            raise ValueError("--lora-dora needs --lora-r: it adds a magnitude to low-rank adapters")
         return model
+    if dora and quant:
+        raise ValueError("--lora-dora and --lora-quant cannot be combined: DoRA on an NF4 base is not implemented")
     import json
 
     from .models.lora import LoraConfig, apply_lora, param_counts
     targets = tuple(t.strip() for t in args.lora_targets.split(",") if t.strip())
     total = param_counts(model)[1]  # before quantisation: an NF4 weight is a buffer, not a parameter
     apply_lora(model, LoraConfig(r=args.lora_r, alpha=args.lora_alpha, dropout=args.lora_dropout, targets=targets,
-                                 quantize=quant))
+                                 quantize=quant, dora=dora))
     train = param_counts(model)[0]
     if log_fn is not None:
         log_fn(json.dumps({"trainable_params": train, "total_params": total + train, "lora_r": args.lora_r,
-                           "lora_targets": list(targets)}))
+                           "lora_targets": list(targets), "lora_dora": dora}))
         if quant:  # frozen bytes before / after, and the layers left in the model dtype
             log_fn(json.dumps(dict(model._nf4_report, lora_quant=quant)))
     return model

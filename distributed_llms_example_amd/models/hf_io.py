@@ -230,12 +230,14 @@ def from_pretrained(name_or_path: str, dtype=torch.float32, device="cpu"):
 # PEFT's checkpoint layout, written from its documented format (peft is not installed where this was developed):
 # adapter_config.json (peft_type LORA, task_type SEQ_2_SEQ_LM, r, lora_alpha, lora_dropout, target_modules) and
 # adapter_model.safetensors with keys base_model.model.<HF module path>.lora_A.weight [r, in] / .lora_B.weight [out, r],
-# where the module path is transformers' name of the UNFUSED projection (the mapping of to_hf_state_dict).
+# where the module path is transformers' name of the UNFUSED projection (the mapping of to_hf_state_dict).  DoRA:
+# "use_dora": true and .lora_magnitude_vector.weight [out] per module (PEFT >= 0.10 writes the magnitude as a module with
+# a "weight"; the first releases wrote the bare key .lora_magnitude_vector, which load_adapter takes too).
 
 
 def _is_adapter_key(name: str) -> bool:
     leaf = name.rsplit(".", 1)[-1]
-    return leaf.startswith("lora_A_") or leaf.startswith("lora_B_")
+    return leaf.startswith("lora_A_") or leaf.startswith("lora_B_") or leaf.startswith("lora_m_")
 
 
 def hf_param_names(cfg, name: str) -> list[str]:
@@ -279,6 +281,8 @@ def adapter_keys(model) -> dict:
             path = paths[adapter_slice_index(ad)]
             out[f"base_model.model.{path}.lora_A.weight"] = ad.A
             out[f"base_model.model.{path}.lora_B.weight"] = ad.B
+            if ad.m is not None:
+                out[f"base_model.model.{path}.lora_magnitude_vector.weight"] = ad.m
     return out
 
 
@@ -294,6 +298,8 @@ def save_adapter(model, output_dir: str) -> list[str]:
     conf = {"peft_type": "LORA", "task_type": "SEQ_2_SEQ_LM", "r": int(cfg.r), "lora_alpha": cfg.alpha,
             "lora_dropout": float(cfg.dropout), "target_modules": leaves, "bias": "none", "fan_in_fan_out": False,
             "inference_mode": True, "base_model_name_or_path": None}
+    if cfg.dora:
+        conf["use_dora"] = True
     if cfg.quantize is not None:
         conf["quantize"] = cfg.quantize  # not a PEFT field: how the base was held while these adapters were trained
     with open(os.path.join(output_dir, "adapter_config.json"), "w") as f:
@@ -311,6 +317,17 @@ def load_adapter(model, adapter_dir: str):
         conf = json.load(f)
     if conf.get("peft_type") != "LORA":
         raise ValueError(f"load_adapter: peft_type {conf.get('peft_type')!r} is not LORA")
+    use_dora = bool(conf.get("use_dora", False))
+    sd = load_file(os.path.join(adapter_dir, "adapter_model.safetensors"))
+    # the older spelling of the magnitude key
+    sd = {(k + ".weight" if k.endswith(".lora_magnitude_vector") else k): v for k, v in sd.items()}
+    has_m = any(k.endswith(".lora_magnitude_vector.weight") for k in sd)
+    if use_dora != has_m:
+        raise ValueError("load_adapter: adapter_config.json says use_dora = " + str(use_dora).lower() + " but the "
+                         "checkpoint holds " + ("" if has_m else "no ") + "lora_magnitude_vector tensors")
+    if has_lora(model) and bool(model._lora_cfg.dora) != use_dora:
+        raise ValueError(f"load_adapter: the checkpoint has use_dora = {use_dora}, the model's adapters have dora = "
+                         f"{model._lora_cfg.dora}")
     if not has_lora(model):
         unknown = [m for m in conf["target_modules"] if m not in _LEAF_TARGET]
         if unknown:
@@ -318,8 +335,7 @@ def load_adapter(model, adapter_dir: str):
         named = {_LEAF_TARGET[m] for m in conf["target_modules"]}
         targets = tuple(t for t in TARGETS if t in named)
         apply_lora(model, LoraConfig(r=int(conf["r"]), alpha=conf["lora_alpha"], dropout=float(conf["lora_dropout"]),
-                                     targets=targets))
-    sd = load_file(os.path.join(adapter_dir, "adapter_model.safetensors"))
+                                     targets=targets, dora=use_dora))
     keys = adapter_keys(model)
     missing = [k for k in keys if k not in sd]
     extra = [k for k in sd if k not in keys]

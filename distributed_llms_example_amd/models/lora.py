@@ -16,6 +16,10 @@ Kaiming-uniform (a = √5), ``lora_B`` zeros, so the adapted model starts as the
 ``LoraConfig(quantize="nf4")`` (QLoRA): after freezing, every projection with one of the names above — adapted or not
 — whose sides are multiples of 64 is held as NF4 codes (ops/nf4.py): ``weight`` None, buffers ``weight_nf4`` /
 ``weight_absmax``.  ``merge_lora`` dequantises them again; docs/MODELS.md has the rest.
+
+``LoraConfig(dora=True)`` (DoRA): every adapter also carries a trainable magnitude ``lora_m_{i}`` [n], initialised to
+the row norms of its weight slice, and the slice's output is ``m / ‖W_s + s B A‖ ⊙ (x W_sᵀ + s t Bᵀ) + b_s``
+(ops/lora.py).  Not together with ``quantize``.
 """
 from __future__ import annotations
 
@@ -28,7 +32,7 @@ import torch.nn as nn
 
 from ..ops import nf4
 from ..ops.linear import Linear
-from ..ops.lora import Adapter
+from ..ops.lora import Adapter, dora_norm
 
 _log = logging.getLogger(__name__)
 
@@ -49,9 +53,14 @@ class LoraConfig:
     dropout: float = 0.0
     targets: tuple = ("q", "v")
     quantize: str | None = None  # "nf4": QLoRA, the frozen projections held as 4-bit codes (ops/nf4.py)
+    dora: bool = False           # weight-decomposed adapters: a trainable magnitude per output row (ops/lora.py)
 
     def __post_init__(self):
         object.__setattr__(self, "targets", tuple(self.targets))
+        object.__setattr__(self, "dora", bool(self.dora))
+        if self.dora and self.quantize is not None:
+            raise NotImplementedError(f"dora=True with quantize={self.quantize!r} is not implemented: the row norms "
+                                      "would need the dequantised weight every step")
         if self.quantize not in (None, "nf4"):
             raise ValueError(f"unknown LoRA base quantisation {self.quantize!r}; known: nf4")
         unknown = [t for t in self.targets if t not in TARGETS]
@@ -120,7 +129,12 @@ def apply_lora(model: nn.Module, cfg: LoraConfig) -> nn.Module:
             nn.init.kaiming_uniform_(A, a=math.sqrt(5))
             mod.register_parameter(f"lora_A_{i}", A)
             mod.register_parameter(f"lora_B_{i}", B)
-            adapters.append(Adapter(target, i * n, n, A, B, cfg.scale))
+            m = None
+            if cfg.dora:  # B = 0: the norm of the weight rows themselves, so c = 1 at the start
+                with torch.no_grad():
+                    m = nn.Parameter(dora_norm(mod.weight[i * n:(i + 1) * n], A, B, cfg.scale).to(mod.weight.dtype))
+                mod.register_parameter(f"lora_m_{i}", m)
+            adapters.append(Adapter(target, i * n, n, A, B, cfg.scale, m))
             count += 1
         mod._lora = (adapters, float(cfg.dropout))
     if count == 0:
@@ -180,7 +194,8 @@ def adapter_slice_index(ad: Adapter) -> int:
 
 @torch.no_grad()
 def merge_lora(model: nn.Module) -> nn.Module:
-    """Fold every adapter into its base weight — ``W[c0:c0+n] += scale · B A``, computed in fp32 and rounded once —
+    """Fold every adapter into its base weight — ``W[c0:c0+n] += scale · B A``, with a DoRA magnitude
+    ``W[c0:c0+n] = (m / ‖W[c0:c0+n] + scale · B A‖) ⊙ (W[c0:c0+n] + scale · B A)``, computed in fp32 and rounded once —
     and remove the adapters: a plain model (parameters trainable as before ``apply_lora``).  A layer held as NF4 codes
     is dequantised in fp32 first, so its merged weight is rounded to the model dtype once."""
     if not has_lora(model):
@@ -196,11 +211,17 @@ def merge_lora(model: nn.Module) -> nn.Module:
         adapters, _ = mod._lora
         for ad in adapters:
             rows = mod.weight[ad.c0:ad.c0 + ad.n]
-            rows.copy_((rows.float() + ad.scale * (ad.B.float() @ ad.A.float())).to(rows.dtype))
+            merged = rows.float() + ad.scale * (ad.B.float() @ ad.A.float())
+            if ad.m is not None:
+                merged = merged * (ad.m.float() / torch.linalg.vector_norm(merged, dim=1)).unsqueeze(1)
+            rows.copy_(merged.to(rows.dtype))
             i = adapter_slice_index(ad)
             delattr(mod, f"lora_A_{i}")
             delattr(mod, f"lora_B_{i}")
+            if ad.m is not None:
+                delattr(mod, f"lora_m_{i}")
         del mod._lora  # back to the class default: no adapters
+        mod.__dict__.pop("_dora_c", None)
     for mod in dequantized:
         mod.weight.data = mod.weight.data.to(dtype)
     trainable = set(model._lora_trainable)

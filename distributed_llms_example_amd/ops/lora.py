@@ -23,6 +23,23 @@ fixed splits summed in order, straight into the flat gradient buffer); ``lib`` =
 on hipBLASLt).  fp32 models, CPU tensors, ``DLLM_REFERENCE_OPS=1`` and shapes off the kernels' grid (feature counts or
 slice offsets that are not multiples of 8) run the composite.
 
+DoRA (an adapter with a magnitude ``m`` [n]; Liu et al. 2024, PEFT ``use_dora``).  With ``W_s = W[c0:c0+n]`` and
+``b_s`` the slice's bias:
+
+* ``norm_j = ‖W_s[j] + s · (B A)[j]‖`` in fp32 from the 16-bit operands (``B A`` is never rounded), DETACHED as in the
+  paper and in PEFT; ``c = m / norm`` in fp32;
+* forward: ``y_s = c ⊙ ((y_s − b_s) + s · t Bᵀ) + b_s`` on the base output ``y_s = x W_sᵀ + b_s``, one rounding; ``t``
+  is the ``t`` above, so dropout acts on the adapter branch only (PEFT also feeds the dropped ``x`` to the base term
+  when p > 0; at p = 0 and in eval the two agree);
+* backward: ``dm = (Σ_rows dY_s ⊙ (y_s − b_s)) / m`` from the SAVED (rounded) output — no recompute GEMM —, and
+  ``dY' = c ⊙ dY_s`` (``dY`` itself on the other columns) replaces ``dY`` in everything above and in the base layer's
+  input gradient (:func:`composite_dora_backward`, then :func:`composite_backward` on its result).
+
+Kernels: ``dora_norm`` (one read of ``W_s``, nothing of size [n, K] written), the rescaling arm of ``lora_up`` (no
+extra pass over the output) and ``dora_bwd`` / ``dora_dm`` (one pass over ``dY`` and ``y`` for the whole layer, split
+partials summed in order).  Under ``no_grad`` the layer's ``c`` is cached on the module, keyed by the ``_version`` of
+every ``A``, ``B`` and ``m`` (a decode step does not read ``W`` again); a forward with gradients drops the cache.
+
 The base layer must be frozen (models/lora.py ``apply_lora`` freezes it): its forward runs through ``linear_fwd``, its
 input gradient through ``linear_dgrad`` (ops/gemm.py) — a base held as NF4 codes (``mod._nf4``) through ops/nf4.py's
 forward and input gradient instead — and it has no weight gradient.  Adapter gradients accumulate into
@@ -54,6 +71,7 @@ class Adapter:
     A: torch.nn.Parameter
     B: torch.nn.Parameter
     scale: float
+    m: torch.nn.Parameter | None = None  # DoRA magnitude [n]; None: plain LoRA
 
 
 def _wide(t: torch.Tensor) -> torch.Tensor:
@@ -75,8 +93,14 @@ def _dropped(x2: torch.Tensor, p: float, seed: int) -> torch.Tensor:
     return x2 * rowwise_keep_mask(seed, p, x2.shape[0], x2.shape[1], x2.device).to(x2.dtype)
 
 
-def composite_forward(x2, y2, slices, ab, p, seed):
-    """The adapters' forward on the base output ``y2`` (updated in place); returns the ``t`` of every adapter."""
+def dora_norm(W_s, A, B, s):
+    """``‖W_s + s · B A‖`` per row, in the accumulation type (module docstring)."""
+    return torch.linalg.vector_norm(_wide(W_s) + s * (_wide(B) @ _wide(A)), dim=1)
+
+
+def composite_forward(x2, y2, slices, ab, p, seed, cs=None, b=None):
+    """The adapters' forward on the base output ``y2`` (updated in place); returns the ``t`` of every adapter.
+    ``cs[i]``: the DoRA scale ``m / norm`` of adapter i (None: plain LoRA); ``b``: the layer's bias."""
     inv = 1.0 / (1.0 - p)
     xd = _dropped(x2, p, seed)
     ts = []
@@ -84,9 +108,29 @@ def composite_forward(x2, y2, slices, ab, p, seed):
         A, B = ab[2 * i], ab[2 * i + 1]
         t = (_mm32(xd, A.t()) * inv).to(x2.dtype)
         ys = y2[:, c0:c0 + n]
-        ys.copy_((_wide(ys) + _mm32(t, B.t()) * s).to(y2.dtype))
+        upd = _mm32(t, B.t()) * s
+        if cs is None or cs[i] is None:
+            ys.copy_((_wide(ys) + upd).to(y2.dtype))
+        else:
+            bs = 0.0 if b is None else _wide(b[c0:c0 + n])
+            ys.copy_((cs[i] * ((_wide(ys) - bs) + upd) + bs).to(y2.dtype))
         ts.append(t)
     return ts
+
+
+def composite_dora_backward(dy2, y2, b, slices, ms, cs, msinks):
+    """DoRA's part of the backward: returns ``dY'`` (``c ⊙ dY`` on the DoRA slices, ``dY`` elsewhere) and accumulates
+    ``dm = Σ_rows dY_s ⊙ (y_s − b_s) / m`` into ``msinks[i]`` for every adapter with a magnitude ``ms[i]``."""
+    out = dy2.clone()
+    for i, (c0, n, _) in enumerate(slices):
+        if ms[i] is None:
+            continue
+        dys = _wide(dy2[:, c0:c0 + n])
+        bs = 0.0 if b is None else _wide(b[c0:c0 + n])
+        dm = (dys * (_wide(y2[:, c0:c0 + n]) - bs)).sum(0) / _wide(ms[i])
+        msinks[i].add_(dm.to(msinks[i].dtype))
+        out[:, c0:c0 + n] = (cs[i] * dys).to(dy2.dtype)
+    return out
 
 
 def composite_backward(x2, dy2, dx2, slices, ab, ts, p, seed, sinks):
@@ -133,9 +177,46 @@ def _base(mod):
     return (mod.weight,)
 
 
-def _forward(x, w, b, slices, p, seed, ab):
-    """(x2, y2, [t per adapter], ran on csrc/lora.hip): the frozen base GEMM (``w``: :func:`_base`) and the adapters'
-    updates of its output."""
+def _dora_scales(W, slices, ab, ms, fused, cache):
+    """``c_full`` [out]: ``m / norm`` on the DoRA slices, 1 elsewhere (fp32 for 16-bit weights).  ``cache``: the module
+    to keep it on between ``no_grad`` forwards (None: compute), valid while no ``A``, ``B`` or ``m`` changed."""
+    key = None
+    if cache is not None:
+        key = (fused, W.data_ptr(), W._version) + tuple(t._version for t in ab) + tuple(
+            q._version for q in ms if q is not None)
+        hit = cache.__dict__.get("_dora_c")
+        if hit is not None and hit[0] == key:
+            return hit[1]
+    c_full = torch.ones(W.shape[0], dtype=_wide(W).dtype, device=W.device)
+    for i, (c0, n, s) in enumerate(slices):
+        if ms[i] is None:
+            continue
+        if fused:
+            _ext.native().dora_norm(W, c0, ab[2 * i], ab[2 * i + 1], s, ms[i], c_full[c0:c0 + n])
+        else:
+            c_full[c0:c0 + n] = _wide(ms[i]) / dora_norm(W[c0:c0 + n], ab[2 * i], ab[2 * i + 1], s)
+    if cache is not None:
+        cache.__dict__["_dora_c"] = (key, c_full)
+    return c_full
+
+
+_live8 = {}
+
+
+def _dora_live8(out_features, slices, ms, device):
+    """uint8 [out / 8]: 1 where the 8-column group lies in a DoRA slice (dora_bwd reads ``y`` only there)."""
+    key = (out_features, tuple((c0, n) for (c0, n, _), q in zip(slices, ms) if q is not None), str(device))
+    if key not in _live8:
+        v = torch.zeros(out_features // 8, dtype=torch.uint8)
+        for c0, n in key[1]:
+            v[c0 // 8:(c0 + n) // 8] = 1
+        _live8[key] = v.to(device)
+    return _live8[key]
+
+
+def _forward(x, w, b, slices, p, seed, ab, ms=None, cache=None):
+    """(x2, y2, [t per adapter], ran on csrc/lora.hip, c_full or None): the frozen base GEMM (``w``: :func:`_base`) and
+    the adapters' updates of its output.  ``ms``: the DoRA magnitude of every adapter (None: plain LoRA)."""
     global fused_calls, lib_calls
     x2 = x.reshape(-1, x.shape[-1])
     if not x2.is_contiguous():
@@ -143,6 +224,11 @@ def _forward(x, w, b, slices, p, seed, ab):
     # a fresh [N, out] tensor: the adapters update it in place
     y = linear_fwd(x2, w[0], b) if len(w) == 1 else nf4._fwd2(x2, w[0], w[1], b)
     fused = _kernel_ok(x2, y.shape[1], slices)
+    dora = ms is not None and any(q is not None for q in ms)
+    c_full = _dora_scales(w[0], slices, ab, ms, fused, cache) if dora else None
+    cs = [None] * len(slices)
+    if dora:
+        cs = [None if q is None else c_full[c0:c0 + n] for (c0, n, _), q in zip(slices, ms)]
     if fused:
         C = _ext.native()
         fused_calls += 1
@@ -150,23 +236,32 @@ def _forward(x, w, b, slices, p, seed, ab):
         ts = []
         for i, (c0, n, s) in enumerate(slices):
             t = C.lora_down(x2, ab[2 * i], inv, p, seed, 0)
-            C.lora_up(t, ab[2 * i + 1], False, s, y, c0, n, 0.0, 0, 0)
+            if cs[i] is None:
+                C.lora_up(t, ab[2 * i + 1], False, s, y, c0, n, 0.0, 0, 0)
+            else:
+                C.lora_up(t, ab[2 * i + 1], False, s, y, c0, n, 0.0, 0, 0, cs[i],
+                          None if b is None else b[c0:c0 + n])
             ts.append(t)
     else:
         lib_calls += 1
-        ts = composite_forward(x2, y, slices, ab, p, seed)
-    return x2, y, ts, fused
+        ts = composite_forward(x2, y, slices, ab, p, seed, cs, b)
+    return x2, y, ts, fused, c_full
 
 
 class _LoraLinearFn(torch.autograd.Function):
-    """Frozen base linear + its adapters.  ``ab`` = (A0, B0, A1, B1, ...): detached when their gradients accumulate
-    into the flat buffer (``params`` then carries the Parameters), else the Parameters themselves (autograd)."""
+    """Frozen base linear + its adapters.  ``ab`` = (A0, B0, A1, B1, ..., then the magnitude of every adapter whose
+    ``dora`` flag is set): detached when their gradients accumulate into the flat buffer (``params`` then carries the
+    Parameters in the same order), else the Parameters themselves (autograd)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, slices, p, seed, params, *ab):
-        x2, y, ts, fused = _forward(x, w, b, slices, p, seed, ab)
-        ctx.save_for_backward(x2, *w, *ts, *ab)  # a quantised base: its code and scale buffers, never a bf16 weight
-        ctx.cfg = (slices, p, seed, fused, x.shape, len(w))
+    def forward(ctx, x, w, b, slices, p, seed, params, dora, *ab):
+        mi = iter(ab[2 * len(slices):])
+        ms = [next(mi) if d else None for d in dora]
+        x2, y, ts, fused, c_full = _forward(x, w, b, slices, p, seed, ab, ms)
+        # a quantised base: its code and scale buffers, never a bf16 weight; DoRA: the output, the scales, the bias
+        extra = () if c_full is None else (y, c_full) + (() if b is None else (b,))
+        ctx.save_for_backward(x2, *w, *ts, *ab, *extra)
+        ctx.cfg = (slices, p, seed, fused, x.shape, len(w), dora, len(extra))
         ctx.params = params
         for q in params or ():
             _use(q)
@@ -175,26 +270,43 @@ class _LoraLinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         saved = ctx.saved_tensors
-        slices, p, seed, fused, shape, nw = ctx.cfg
+        slices, p, seed, fused, shape, nw, dora, nx = ctx.cfg
         na = len(slices)
         x2, w = saved[0], saved[1:1 + nw]
-        ts, ab = saved[1 + nw:1 + nw + na], saved[1 + nw + na:]
+        ts, ab = saved[1 + nw:1 + nw + na], saved[1 + nw + na:len(saved) - nx]
         params = ctx.params
         dy2 = dy.reshape(-1, dy.shape[-1])
+        with torch.no_grad():
+            if params is not None:
+                sinks = [_gbuf(q) for q in params]
+            else:
+                sinks = [torch.zeros(t.shape, dtype=_wide(t).dtype, device=t.device) for t in ab]
+            dyk = _rows16(dy2) if fused else dy2
+            if nx:  # DoRA: dm from the saved output, then everything below runs on dY' = c_full . dY
+                y, c_full, b = saved[len(saved) - nx], saved[len(saved) - nx + 1], saved[-1] if nx == 3 else None
+                mi = iter(range(2 * na, len(ab)))
+                mk = [next(mi) if d else None for d in dora]
+                ms = [None if k is None else ab[k] for k in mk]
+                if fused:
+                    C = _ext.native()
+                    dyk, part = C.dora_bwd(dyk, y, c_full, _dora_live8(y.shape[1], slices, ms, y.device), b)
+                    dy2 = dyk
+                    for (c0, n, _), k in zip(slices, mk):
+                        if k is not None:
+                            C.dora_dm(part, c0, ab[k], sinks[k])
+                else:
+                    cs = [None if k is None else c_full[c0:c0 + n] for (c0, n, _), k in zip(slices, mk)]
+                    dy2 = composite_dora_backward(dy2, y, b, slices, ms, cs,
+                                                  [None if k is None else sinks[k] for k in mk])
         dx2 = None
         if ctx.needs_input_grad[0]:
             dx2 = linear_dgrad(dy2, w[0]) if nw == 1 else nf4._dgrad2(dy2, w[0], w[1])
         if dx2 is not None and not dx2.is_contiguous():
             dx2 = dx2.contiguous()
         with torch.no_grad():
-            if params is not None:
-                sinks = [_gbuf(q) for q in params]
-            else:
-                sinks = [torch.zeros(t.shape, dtype=_wide(t).dtype, device=t.device) for t in ab]
             if fused:
                 C = _ext.native()
                 inv = 1.0 / (1.0 - p)
-                dyk = _rows16(dy2)
                 for i, (c0, n, s) in enumerate(slices):
                     A, B = ab[2 * i], ab[2 * i + 1]
                     dys = dyk[:, c0:c0 + n]
@@ -209,8 +321,8 @@ class _LoraLinearFn(torch.autograd.Function):
         if params is not None:
             for q in params:
                 _fire(q)
-            return (dx, None, None, None, None, None, None) + (None,) * len(ab)
-        return (dx, None, None, None, None, None, None) + tuple(g.to(t.dtype) for g, t in zip(sinks, ab))
+            return (dx, None, None, None, None, None, None, None) + (None,) * len(ab)
+        return (dx, None, None, None, None, None, None, None) + tuple(g.to(t.dtype) for g, t in zip(sinks, ab))
 
 
 def lora_linear(x: torch.Tensor, mod, adapters, p: float = 0.0, seed: int = 0) -> torch.Tensor:
@@ -220,16 +332,21 @@ def lora_linear(x: torch.Tensor, mod, adapters, p: float = 0.0, seed: int = 0) -
     if w[0].requires_grad or (b is not None and b.requires_grad):
         raise NotImplementedError("lora_linear needs a frozen base layer (models/lora.py apply_lora freezes it)")
     slices = tuple((ad.c0, ad.n, float(ad.scale)) for ad in adapters)
-    plist = [q for ad in adapters for q in (ad.A, ad.B)]
+    dora = tuple(ad.m is not None for ad in adapters)
+    if any(dora) and len(w) != 1:
+        raise NotImplementedError("lora_linear: DoRA on an NF4 base is not implemented")
+    plist = [q for ad in adapters for q in (ad.A, ad.B)] + [ad.m for ad in adapters if ad.m is not None]
     if not torch.is_grad_enabled():
-        _, y, _, _ = _forward(x, w, b, slices, float(p), int(seed), [q.detach() for q in plist])
+        ms = [None if ad.m is None else ad.m.detach() for ad in adapters]
+        y = _forward(x, w, b, slices, float(p), int(seed), [q.detach() for q in plist], ms, mod)[1]
         return y.view(*x.shape[:-1], y.shape[1])
+    mod.__dict__.pop("_dora_c", None)  # a training step follows: the cached scales go stale
     if all(_fusable(q) for q in plist):
         # fresh leaves over the adapters' storage give the output a grad_fn even when x carries no gradient (the first
         # adapted layer of a frozen model) without an edge to the Parameters' AccumulateGrad (ops/embedding.py)
-        return _LoraLinearFn.apply(x, w, b, slices, float(p), int(seed), tuple(plist),
+        return _LoraLinearFn.apply(x, w, b, slices, float(p), int(seed), tuple(plist), dora,
                                    *[q.detach().requires_grad_(True) for q in plist])
-    return _LoraLinearFn.apply(x, w, b, slices, float(p), int(seed), None, *plist)
+    return _LoraLinearFn.apply(x, w, b, slices, float(p), int(seed), None, dora, *plist)
 
 
 def adapted_forward(mod, x: torch.Tensor) -> torch.Tensor:

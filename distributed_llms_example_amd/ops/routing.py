@@ -108,6 +108,10 @@ low-rank adapters (LoRA)       csrc/lora.hip (``lora`` = fused): mask regenerate
                                once, split reductions summed in order into the flat
                                gradient; ``lib``: the composite on torch matmuls (2-9x
                                slower per adapted projection, 3.3-3.6x per step)
+DoRA magnitudes                csrc/lora.hip under the same ``lora`` key: dora_norm (row norms  dora_step.txt
+                               of W_s + s B A on MFMA, one read of W_s), the rescaling arm
+                               of lora_up, dora_bwd + dora_dm (one pass over dY and y per
+                               layer, split partials summed in order); ``lib``: the composite
 NF4 frozen base (QLoRA)        csrc/nf4.hip (``nf4`` = fused): the 4-bit codes expanded to      nf4_gemm.txt
                                bf16 MFMA operands on the way through LDS, forward (NT; a
                                narrow tile for <= 64 decode rows) and input gradient (NN),

@@ -3,6 +3,7 @@ the library's GEMMs (``lora=lib``), and LoRA training steps against full fine-tu
 
     python tools/lora_bench.py --op            # (a) one adapted qkv projection, forward + backward
     python tools/lora_bench.py --step          # (b) whole training steps: full fine-tuning | LoRA fused | LoRA lib
+    python tools/lora_bench.py --dora          # (c) DoRA: dora_norm bytes/s, and steps DoRA fused | DoRA lib | LoRA
 
 Arms alternate inside one process, round after round, so drift of the shared machine hits every arm alike; every
 shape is warmed before its timed windows; times are device events around work that ends in a synchronise.  Reported:
@@ -159,10 +160,75 @@ def step_level(a) -> None:
         torch.cuda.empty_cache()
 
 
+def dora_level(a) -> None:
+    """(c) ``dora_norm``'s rate over the weight bytes it reads, then whole steps with three arms in one process."""
+    from distributed_llms_example_amd.parallel.env import init_distributed
+    from distributed_llms_example_amd.train.engine import TrainEngine
+    C = _ext.native()
+    for d in a.widths:
+        for r in a.ranks:
+            W = (torch.randn(3 * d, d, device="cuda") * 0.05).to(torch.bfloat16)
+            A = (torch.randn(r, d, device="cuda") * d ** -0.5).to(torch.bfloat16)
+            B = (torch.randn(d, r, device="cuda") * 0.02).to(torch.bfloat16)
+            m, c = torch.ones(d, device="cuda", dtype=torch.bfloat16), torch.empty(d, device="cuda")
+            C.dora_norm(W, 2 * d, A, B, 2.0, m, c)
+            ms = [_timed(lambda: C.dora_norm(W, 2 * d, A, B, 2.0, m, c), 50) for _ in range(a.rounds)]
+            med, spread = _summary(ms)
+            print(json.dumps({"bench": "dora_norm", "n": d, "K": d, "r": r, "ms": med, "spread": spread,
+                              "w_tb_per_s": round(2 * d * d / (med * 1e-3) / 1e12, 3)}), flush=True)
+    env = init_distributed()
+    for spec in a.models:
+        name, _, b = spec.partition(":")
+        Bsz = int(b)
+        cfg = resolve_config(name)
+        g = torch.Generator().manual_seed(1000)
+        batches = [{"input_ids": torch.randint(2, cfg.vocab_size, (Bsz, a.src_len), generator=g).cuda(),
+                    "attention_mask": torch.ones(Bsz, a.src_len, dtype=torch.long).cuda(),
+                    "labels": torch.randint(2, cfg.vocab_size, (Bsz, a.tgt_len), generator=g).cuda()} for _ in range(2)]
+        engines = {}
+        for kind in ("dora", "lora"):
+            torch.manual_seed(0)
+            mdl = build_model(cfg)
+            apply_lora(mdl, LoraConfig(r=a.step_rank, alpha=16, dropout=a.step_dropout, targets=("q", "v"),
+                                       dora=kind == "dora"))
+            manual_seed(1)
+            engines[kind] = TrainEngine(mdl, env, lr=5e-5, weight_decay=0.01, max_grad_norm=1.0, dtype=torch.bfloat16)
+            engines[kind].train()
+        arms = ("dora_fused", "dora_lib", "lora_fused")
+
+        def step(arm, i):
+            _route("lib" if arm.endswith("_lib") else "fused")
+            eng = engines[arm.split("_")[0]]
+            loss = eng.forward_backward(batches[i % 2])
+            eng.step()
+            return loss
+
+        for arm in arms:
+            step(arm, 0)
+            step(arm, 1)
+        torch.cuda.synchronize()
+        res = {k: [] for k in arms}
+        for r in range(a.rounds):
+            for arm in arms:  # alternating
+                ms = _timed(lambda: step(arm, r), a.step_iters)
+                res[arm].append(Bsz / (ms / 1e3))
+        out = {"bench": "dora_step", "model": name, "batch": Bsz, "src_len": a.src_len, "tgt_len": a.tgt_len,
+               "lora_r": a.step_rank, "lora_dropout": a.step_dropout, "device": torch.cuda.get_device_name(0),
+               "last_loss": {arm: round(float(step(arm, 0)), 4) for arm in arms}}
+        for arm in arms:
+            out[f"{arm}_samples_per_s"], out[f"{arm}_spread"] = _summary(res[arm])
+        out["dora_fused_over_lib"] = round(out["dora_fused_samples_per_s"] / out["dora_lib_samples_per_s"], 3)
+        out["dora_fused_over_lora"] = round(out["dora_fused_samples_per_s"] / out["lora_fused_samples_per_s"], 3)
+        print(json.dumps(out), flush=True)
+        del engines, batches
+        torch.cuda.empty_cache()
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", action="store_true")
     ap.add_argument("--step", action="store_true")
+    ap.add_argument("--dora", action="store_true")
     ap.add_argument("--tokens", type=lambda s: [int(v) for v in s.split(",")], default=[65536, 524288])
     ap.add_argument("--widths", type=lambda s: [int(v) for v in s.split(",")], default=[768, 1024, 2048])
     ap.add_argument("--ranks", type=lambda s: [int(v) for v in s.split(",")], default=[8, 64])
@@ -180,6 +246,9 @@ def main() -> int:
         raise SystemExit("lora_bench: needs a GPU (no fall-back)")
     if _ext.native() is None:
         raise SystemExit(f"lora_bench: native extension not loaded: {_ext.load_error()}")
+    if a.dora:
+        dora_level(a)
+        return 0
     if a.op or not a.step:
         op_level(a)
     if a.step or not a.op:
