@@ -29,6 +29,20 @@
 //            reduces over the splits in split order — no atomics, reruns are bit-identical.  A wave or split without
 //            a visible key is (m = -inf, l = 0) and weighs exp2(-inf - mu) = 0 with mu = 0 when every m is -inf.
 //
+//   FP8      K/V as OCP e4m3fn codes with one fp32 scale per (batch entry, key, K/V head) (attn_params.h; template
+//            parameter FP8, instantiations of their own): the same grid, row packing, softmax and merges on half the
+//            bytes.  K: a lane loads 16 consecutive codes (16 B) of its key row straight into registers and widens them
+//            to two bf16 A fragments there (v_cvt_pk_f32_fp8, then the high halves packed by v_perm: a code is exact in
+//            bf16); the contraction order is free, so fragment 2 l + h holds the head-dim columns 64 l + 16 g + 8 h ..
+//            + 7 and Q^T is loaded with the same permutation.  k_scale joins the score in fp32 where the lane holds
+//            it (st * (scale2 * ks[key])), next to the mask byte and the bias.  V: 16-code chunks pass through half
+//            the registers and are widened on the way into the slab, whose layout and transposed reads are those of
+//            bf16 (ds_read_b64_tr_b16 kept: a slab of codes read by ds_read_b64_tr_b8 would feed an fp8 MFMA, and the
+//            P operand would have to be rounded to fp8); v_scale multiplies P in fp32 ahead of pack8.
+//   quantise attn_kv_quant_kernel writes that row format: D / 8 lanes of a row load 16 B each, the row max is a
+//            shuffle reduction inside the lane group, the codes are v_cvt_pk_fp8_f32 of x / scale (a correctly rounded
+//            fp32 divide, clamped to +-448): bit-equal to the torch composite of ops/attention.py quantize_kv.
+//
 // exp2 softmax with log2(e) folded into the scale; the cap is tanh_ex2, before the mask (template parameter CAP).
 // Plain C++ and vector stores only.
 #include <algorithm>
@@ -46,7 +60,13 @@ constexpr int STEP = 32;        // keys of one wave step: two 16-key MFMA tiles
 constexpr int SPLIT_ALIGN = 128;  // 4 waves x STEP
 // split choice (dllm_attn_decode_plan), from the sweep of tools/attn_decode_bench.py in profiles/attn_decode.txt
 constexpr int FILL_PER_CU = 1;           // workgroups per CU to aim for
-constexpr int SPLIT_FLOOR_ELEMS = 32768;  // no split shorter than this many K elements (64 KB): keys x padded head dim
+constexpr int SPLIT_FLOOR_BYTES = 65536;  // no split shorter than this many bytes of K: keys x padded head dim x
+                                          // element size
+// FP8 K/V, from the sweep in profiles/attn_decode_fp8.txt: half the bytes per step are in flight, so the FP8 kernels
+// are fastest with every workgroup slot of a CU taken (3 / 2 / 1 at the padded head dims 64 / 128 / 256) and with
+// bf16's floor in keys, which is half its bytes
+constexpr int SPLIT_FLOOR_BYTES_FP8 = 32768;
+constexpr int fill_per_cu_fp8(int dp) { return dp == 64 ? 3 : dp == 128 ? 2 : 1; }
 
 // ordering of the wave's own LDS writes and (transposed) reads: nothing is emitted, the compiler keeps the order
 DLLM_DEVICE void wave_lds_order() {
@@ -54,9 +74,21 @@ DLLM_DEVICE void wave_lds_order() {
   __builtin_amdgcn_wave_barrier();
 }
 
-template <int DP, bool CAP>
+// 8 e4m3fn codes (two dwords, ascending bytes) as 8 bf16: the fp32 value of a code has at most 4 significant bits, so
+// its high half is the bf16 of the same value
+DLLM_DEVICE uint32_t widen2(uint32_t w, bool hi) {
+  const f32x2 f = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+  return __builtin_amdgcn_perm(__float_as_uint(f.y), __float_as_uint(f.x), 0x07060302u);  // (x >> 16) | (y & ~0xFFFF)
+}
+DLLM_DEVICE u32x4 widen8(uint32_t lo, uint32_t hi) {
+  return u32x4{widen2(lo, false), widen2(lo, true), widen2(hi, false), widen2(hi, true)};
+}
+
+template <int DP, bool CAP, bool FP8>
 __global__ __launch_bounds__(NT) void attn_decode_kernel(AttnDecodeParams P) {
   constexpr int KS = DP / 32, DT = DP / 16, LD = Img<DP>::LD, CPR = Img<DP>::CPR, VPL = DP / 16;
+  constexpr int KL = DP / 64;                 // FP8: 16-code loads of a lane per key row, two K fragments each
+  constexpr int CPR8 = DP / 16, VPL8 = DP / 32;  // FP8: 16-code chunks per V row, and per lane and step
   constexpr int SLAB = STEP * LD;  // bf16 elements of a wave's V slab; as floats 16 DP + 128 >= the merge's 16 DP + 32
   __shared__ __attribute__((aligned(16))) uint16_t Vs[4 * SLAB];
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
@@ -67,7 +99,18 @@ __global__ __launch_bounds__(NT) void attn_decode_kernel(AttnDecodeParams P) {
   const int qi = row_ok ? c / G : 0, hq = hk * G + (row_ok ? c % G : 0);  // the lane's query index and query head
 
   bf16x8v qf[KS];
-  load_row_frags<DP>(P.q + (long)b * P.q_sb + (long)qi * P.q_ss + (long)hq * P.q_sh, g, P.D, qf);
+  const uint16_t* qrow = P.q + (long)b * P.q_sb + (long)qi * P.q_ss + (long)hq * P.q_sh;
+  if constexpr (FP8) {  // the K fragments' column order: fragment 2 l + h = columns 64 l + 16 g + 8 h .. + 7
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int d0 = 64 * (ks >> 1) + 16 * g + 8 * (ks & 1);
+      u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (d0 < P.D) v = *reinterpret_cast<const u16x8*>(qrow + d0);
+      qf[ks] = __builtin_bit_cast(bf16x8v, v);
+    }
+  } else {
+    load_row_frags<DP>(qrow, g, P.D, qf);
+  }
   if (!row_ok) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(bf16x8v, u16x8{0, 0, 0, 0, 0, 0, 0, 0});
@@ -83,23 +126,52 @@ __global__ __launch_bounds__(NT) void attn_decode_kernel(AttnDecodeParams P) {
   // bias of (row, key j): lutp[j]
   const float* lutp = P.lut && row_ok ? P.lut + (long)hq * ((long)P.Sq + P.Sk - 1) + (P.Sq - 1 - qi) : nullptr;
   uint16_t* slab = Vs + w * SLAB;
+  // FP8: the code bytes (strides in bytes) and the scales of the (batch entry, K/V head)
+  const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(P.k) + (long)b * P.k_sb + (long)hk * P.k_sh;
+  const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(P.v) + (long)b * P.v_sb + (long)hk * P.v_sh;
+  const float* ksp = FP8 ? P.k_scale + (long)b * P.ks_sb + (long)hk * P.ks_sh : nullptr;
+  const float* vsp = FP8 ? P.v_scale + (long)b * P.vs_sb + (long)hk * P.vs_sh : nullptr;
 
   bf16x8v kf[2][KS];  // the step's two K tiles: key k0 + 16 t + c, columns 32 ks + 8 g ..
   u16x8 vr[VPL];      // the step's V slab on its way to LDS: chunk lane + 64 j
+  u32x4 kc[2][KL];    // FP8: the two K tiles as codes, columns 64 l + 16 g ..
+  u32x4 vc[VPL8];     // FP8: the V slab as codes, 16-code chunk lane + 64 j
   uint8_t kp[2][4];   // visibility of the lane's keys k0 + 16 t + 4 g + i
   float lb[2][4];     // their bias, in log2 units
+  float kq[2][4], vq[2][4];  // FP8: their k_scale and v_scale
   auto load_step = [&](int k0) {
+    if constexpr (FP8) {
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int key = min(k0 + 16 * t + c, P.Sk - 1);  // past the end: a valid row, its score is masked below
-      load_row_frags<DP>(kb + (long)key * P.k_ss, g, P.D, kf[t]);
-    }
+      for (int t = 0; t < 2; ++t) {
+        const int key = min(k0 + 16 * t + c, P.Sk - 1);  // past the end: a valid row, its score is masked below
 #pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-      const int idx = lane + 64 * j, r = idx / CPR, ch = idx % CPR;
-      u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};  // rows past the end and columns past D as zeros: 0 * P = 0
-      if (k0 + r < kend && 8 * ch < P.D) v = *reinterpret_cast<const u16x8*>(vb + (long)(k0 + r) * P.v_ss + 8 * ch);
-      vr[j] = v;
+        for (int l = 0; l < KL; ++l) {
+          const int d0 = 64 * l + 16 * g;
+          u32x4 v = {0u, 0u, 0u, 0u};  // code 0 is +0
+          if (d0 < P.D) v = *reinterpret_cast<const u32x4*>(kb8 + (long)key * P.k_ss + d0);
+          kc[t][l] = v;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < VPL8; ++j) {
+        const int idx = lane + 64 * j, r = idx / CPR8, ch = idx % CPR8;
+        u32x4 v = {0u, 0u, 0u, 0u};  // rows past the end and columns past D as zeros: 0 * P = 0
+        if (k0 + r < kend && 16 * ch < P.D) v = *reinterpret_cast<const u32x4*>(vb8 + (long)(k0 + r) * P.v_ss + 16 * ch);
+        vc[j] = v;
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int key = min(k0 + 16 * t + c, P.Sk - 1);  // past the end: a valid row, its score is masked below
+        load_row_frags<DP>(kb + (long)key * P.k_ss, g, P.D, kf[t]);
+      }
+#pragma unroll
+      for (int j = 0; j < VPL; ++j) {
+        const int idx = lane + 64 * j, r = idx / CPR, ch = idx % CPR;
+        u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};  // rows past the end and columns past D as zeros: 0 * P = 0
+        if (k0 + r < kend && 8 * ch < P.D) v = *reinterpret_cast<const u16x8*>(vb + (long)(k0 + r) * P.v_ss + 8 * ch);
+        vr[j] = v;
+      }
     }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -109,6 +181,10 @@ __global__ __launch_bounds__(NT) void attn_decode_kernel(AttnDecodeParams P) {
         const bool in = key < kend;
         kp[t][i] = in ? (kpm ? kpm[key] : (uint8_t)1) : (uint8_t)0;
         lb[t][i] = in && lutp ? lutp[key] * LOG2E : 0.f;
+        if constexpr (FP8) {
+          kq[t][i] = in ? ksp[(long)key * P.ks_ss] : 0.f;
+          vq[t][i] = in ? vsp[(long)key * P.vs_ss] : 0.f;
+        }
       }
     }
   };
@@ -122,28 +198,49 @@ __global__ __launch_bounds__(NT) void attn_decode_kernel(AttnDecodeParams P) {
   if (k0 < kend) load_step(k0);
   for (; k0 < kend; k0 += 4 * STEP) {
     wave_lds_order();  // the previous step's slab reads come first
+    if constexpr (FP8) {
 #pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-      const int idx = lane + 64 * j, r = idx / CPR, ch = idx % CPR;
-      *reinterpret_cast<u16x8*>(slab + r * LD + 8 * ch) = vr[j];
+      for (int j = 0; j < VPL8; ++j) {  // widened here: the slab is the bf16 one
+        const int idx = lane + 64 * j, r = idx / CPR8, ch = idx % CPR8;
+        *reinterpret_cast<u32x4*>(slab + r * LD + 16 * ch) = widen8(vc[j].x, vc[j].y);
+        *reinterpret_cast<u32x4*>(slab + r * LD + 16 * ch + 8) = widen8(vc[j].z, vc[j].w);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < VPL; ++j) {
+        const int idx = lane + 64 * j, r = idx / CPR, ch = idx % CPR;
+        *reinterpret_cast<u16x8*>(slab + r * LD + 8 * ch) = vr[j];
+      }
     }
     wave_lds_order();
     f32x4 st[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (FP8) {
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) st[t] = mma(kf[t][ks], qf[ks], st[t]);
+        for (int l = 0; l < KL; ++l) {
+          st[t] = mma(__builtin_bit_cast(bf16x8v, widen8(kc[t][l].x, kc[t][l].y)), qf[2 * l], st[t]);
+          st[t] = mma(__builtin_bit_cast(bf16x8v, widen8(kc[t][l].z, kc[t][l].w)), qf[2 * l + 1], st[t]);
+        }
+      } else {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) st[t] = mma(kf[t][ks], qf[ks], st[t]);
+      }
     }
     // st[t][i] = S[row c][key k0 + 16 t + 4 g + i]
     uint8_t vis[2][4];
-    float bias[2][4];
+    float bias[2][4], ksc[2][4], vsc[2][4];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         vis[t][i] = kp[t][i];
         bias[t][i] = lb[t][i];
+        if constexpr (FP8) {
+          ksc[t][i] = kq[t][i];
+          vsc[t][i] = vq[t][i];
+        }
       }
     }
     if (k0 + 4 * STEP < kend) load_step(k0 + 4 * STEP);  // in flight under the softmax and P V
@@ -153,7 +250,9 @@ __global__ __launch_bounds__(NT) void attn_decode_kernel(AttnDecodeParams P) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float x;
-        if constexpr (CAP) x = capc2 * tanh_ex2(st[t][i] * capz2);  // c tanh(scale s / c), in log2 units
+        if constexpr (CAP && FP8) x = capc2 * tanh_ex2(st[t][i] * (capz2 * ksc[t][i]));
+        else if constexpr (CAP) x = capc2 * tanh_ex2(st[t][i] * capz2);  // c tanh(scale s / c), in log2 units
+        else if constexpr (FP8) x = st[t][i] * (scale2 * ksc[t][i]) + bias[t][i];
         else x = st[t][i] * scale2 + bias[t][i];
         if (!vis[t][i]) x = -INFINITY;
         st[t][i] = x;
@@ -171,7 +270,8 @@ __global__ __launch_bounds__(NT) void attn_decode_kernel(AttnDecodeParams P) {
       for (int i = 0; i < 4; ++i) {
         const float pr = ex2(st[t][i] - mu);
         ls += pr;
-        st[t][i] = pr;
+        if constexpr (FP8) st[t][i] = pr * vsc[t][i];  // V's scale rides on P: the row sum stays that of P
+        else st[t][i] = pr;
       }
     }
     ls = grp_sum(ls);
@@ -262,18 +362,60 @@ int cu_count() {
   return n;
 }
 
+template <int DP, bool FP8>
+void launch_as(const AttnDecodeParams& P, hipStream_t st) {
+  const dim3 grid(P.splits, P.Hkv, P.B);
+  if (P.softcap > 0.f) hipLaunchKernelGGL((attn_decode_kernel<DP, true, FP8>), grid, dim3(NT), 0, st, P);
+  else hipLaunchKernelGGL((attn_decode_kernel<DP, false, FP8>), grid, dim3(NT), 0, st, P);
+}
 template <int DP>
 void launch(const AttnDecodeParams& P, hipStream_t st) {
-  const dim3 grid(P.splits, P.Hkv, P.B);
-  if (P.softcap > 0.f) hipLaunchKernelGGL((attn_decode_kernel<DP, true>), grid, dim3(NT), 0, st, P);
-  else hipLaunchKernelGGL((attn_decode_kernel<DP, false>), grid, dim3(NT), 0, st, P);
+  if (P.k_scale != nullptr) launch_as<DP, true>(P, st);
+  else launch_as<DP, false>(P, st);
+}
+
+// Rows of D bf16 to D e4m3fn codes and one fp32 scale (attn_params.h AttnDecodeParams, FP8 K/V).  LG lanes serve a row
+// (LG: D / 8 rounded up to a power of two; the lanes past D / 8 idle), 64 / LG rows a wave: one 16-B load, the row's
+// max by xor shuffles inside the group, four v_cvt_pk_fp8_f32, one 8-B store per lane and one scale store per row.
+__global__ __launch_bounds__(NT) void attn_kv_quant_kernel(const uint16_t* kv, long row_stride, uint8_t* codes,
+                                                           float* scales, long rows, int D, int LG) {
+  const int sub = threadIdx.x % LG;
+  const long row = ((long)blockIdx.x * NT + threadIdx.x) / LG;
+  const bool on = row < rows && 8 * sub < D;  // a group is never split over two waves: the shuffles below stay inside
+  float x[8];
+  float amax = 0.f;
+  if (on) {
+    const u16x8 v = *reinterpret_cast<const u16x8*>(kv + row * row_stride + 8 * sub);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      x[i] = bf2f(v[i]);
+      amax = fmaxf(amax, fabsf(x[i]));
+    }
+  }
+  for (int m = LG >> 1; m >= 1; m >>= 1) amax = fmaxf(amax, __shfl_xor(amax, m, 64));
+  if (!on) return;
+  const float scale = amax == 0.f ? 1.f : amax / 448.f;  // IEEE divide (no fast-math): the composite's bits
+  uint32_t w[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    float y[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y[j] = fminf(fmaxf(x[4 * i + j] / scale, -448.f), 448.f);
+    int c = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+    c = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], c, true);
+    w[i] = (uint32_t)c;
+  }
+  *reinterpret_cast<uint2*>(codes + row * D + 8 * sub) = make_uint2(w[0], w[1]);
+  if (sub == 0) scales[row] = scale;
 }
 
 }  // namespace
 
 extern "C" int dllm_attn_decode_plan(AttnDecodeParams* pp) {
   AttnDecodeParams& P = *pp;
-  if (P.D < 32 || P.D > 256 || P.D % 8) return -1;
+  const bool fp8 = P.k_scale != nullptr;
+  if (P.D < 32 || P.D > 256 || P.D % (fp8 ? 16 : 8)) return -1;
+  if (fp8 != (P.v_scale != nullptr)) return -9;
   if (P.Hkv <= 0 || P.H % P.Hkv) return -2;
   if (P.B <= 0 || P.Sq <= 0 || P.Sk <= 0 || P.B > 65535 || P.Hkv > 65535) return -3;
   P.G = P.H / P.Hkv;
@@ -283,9 +425,10 @@ extern "C" int dllm_attn_decode_plan(AttnDecodeParams* pp) {
   long want = P.splits;
   if (want == 0) {
     // enough workgroups to fill the chip, no split below the floor; 1 once B * Hkv alone fills it
-    const long bh = (long)P.B * P.Hkv, target = (long)FILL_PER_CU * cu_count();
     const int dp = P.D <= 64 ? 64 : P.D <= 128 ? 128 : 256;
-    want = std::max(1L, std::min((target + bh - 1) / bh, (long)P.Sk / (SPLIT_FLOOR_ELEMS / dp)));
+    const long bh = (long)P.B * P.Hkv, target = (long)(fp8 ? fill_per_cu_fp8(dp) : FILL_PER_CU) * cu_count();
+    const long floor_keys = fp8 ? SPLIT_FLOOR_BYTES_FP8 / dp : SPLIT_FLOOR_BYTES / (dp * 2);
+    want = std::max(1L, std::min((target + bh - 1) / bh, (long)P.Sk / floor_keys));
   }
   const long per = (P.Sk + want - 1) / want;
   const long L = std::min<long>((per + SPLIT_ALIGN - 1) / SPLIT_ALIGN * SPLIT_ALIGN, 0x40000000L);
@@ -298,6 +441,7 @@ extern "C" int dllm_attn_decode(const AttnDecodeParams* pp, hipStream_t st) {
   const AttnDecodeParams P = *pp;
   if (P.L <= 0 || P.L % SPLIT_ALIGN || P.G <= 0 || P.splits != (P.Sk + P.L - 1) / P.L) return -7;  // not planned
   if (P.splits > 1 && (P.part_o == nullptr || P.part_ml == nullptr)) return -8;
+  if ((P.k_scale != nullptr) != (P.v_scale != nullptr) || (P.k_scale != nullptr && P.D % 16)) return -9;
   if (P.D <= 64) launch<64>(P, st);
   else if (P.D <= 128) launch<128>(P, st);
   else launch<256>(P, st);
@@ -305,6 +449,20 @@ extern "C" int dllm_attn_decode(const AttnDecodeParams* pp, hipStream_t st) {
     const long n = (long)P.B * P.Hkv * P.Sq * P.G * (P.D / 4);
     hipLaunchKernelGGL(attn_decode_merge_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, st, P);
   }
+  DLLM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dllm_kv_quant_fp8(const void* kv, long row_stride, uint8_t* codes, float* scales, long rows, int D,
+                                 hipStream_t st) {
+  if (D < 32 || D > 256 || D % 16 || rows < 0 || row_stride < D || row_stride % 8) return -1;
+  if (rows == 0) return 0;
+  int LG = 4;
+  while (LG < D / 8) LG *= 2;  // 4 .. 32: a divisor of 64
+  const long blocks = (rows * LG + NT - 1) / NT;
+  if (blocks > 0x7FFFFFFFL) return -2;
+  hipLaunchKernelGGL(attn_kv_quant_kernel, dim3((unsigned)blocks), dim3(NT), 0, st, static_cast<const uint16_t*>(kv),
+                     row_stride, codes, scales, rows, D, LG);
   DLLM_CHECK_LAUNCH();
   return 0;
 }

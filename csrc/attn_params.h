@@ -202,6 +202,12 @@ struct AttnWideParams {
 // lut[h][(j - i) + Sq - 1] when given (never with a cap).  A row without a visible key is an output row of zeros.
 // The key axis is cut into `splits` ranges of L keys (L % 128 == 0), one workgroup each; with splits > 1 they write
 // unnormalised fp32 partials that a second kernel merges in split order (no atomics).
+// FP8 K/V (k_scale and v_scale given, both or neither): k and v point at OCP e4m3fn codes, one byte per element, with
+// their strides in bytes, every code row 16-byte aligned and D % 16 == 0; k_scale / v_scale are fp32 [B, Sk, Hkv] views
+// (any strides, in elements) and the value of an element is float(code) * scale[b][key][head] — the row format
+// dllm_kv_quant_fp8 writes (scale = absmax / 448, or 1 for a row of zeros).  q and o stay bf16.  The kernels fold
+// k_scale into the fp32 score and v_scale into the fp32 probability, never into an element.  Null scales: bf16 K/V, the
+// instantiations and the code they ran before.
 struct AttnDecodeParams {
   typedef uint16_t elem;
   const uint16_t* q;
@@ -224,4 +230,9 @@ struct AttnDecodeParams {
   // filled by dllm_attn_decode_plan
   int L;               // keys per split, a multiple of 128
   int G;               // H / Hkv
+  // FP8 K/V, after everything else: the fields above keep their offsets
+  const float* k_scale;  // [B, Sk, Hkv] fp32; nullptr: k / v are bf16
+  const float* v_scale;
+  long ks_sb, ks_ss, ks_sh;
+  long vs_sb, vs_ss, vs_sh;
 };

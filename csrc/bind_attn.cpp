@@ -445,12 +445,37 @@ std::vector<Tensor> attn_wide_bwd(const Tensor& dout, const Tensor& q, const Ten
 const AttnFamily<AttnDecodeParams> kAttnDecode{at::kBFloat16, "attn_decode takes bf16", nullptr, nullptr,
                                                "attn_decode", nullptr};  // forward only, one launcher pair of its own
 
+// FP8 K/V: float8_e4m3fn codes, one byte per element (check_bshd then asks for 16-byte code rows)
+struct AttnDecodeCodes { typedef uint8_t elem; };
+const AttnFamily<AttnDecodeCodes> kAttnDecodeFp8{at::kFloat8_e4m3fn, "attn_decode: fp8 k / v are float8_e4m3fn codes",
+                                                 nullptr, nullptr, "attn_decode", nullptr};
+
+// a scale of FP8 K/V: fp32 [B, Sk, Hkv] on q's device, any strides (read one float at a time)
+void set_scale(const Tensor& t, const Tensor& q, const char* n, int64_t B, int64_t Sk, int64_t Hkv, const float*& ptr,
+               long& sb, long& ss, long& sh) {
+  const std::string where = residency_fault(t, q);
+  TORCH_CHECK(where.empty(), n, " ", where);
+  TORCH_CHECK(t.scalar_type() == at::kFloat, n, ": scales are fp32, got ", dtype_name(t.scalar_type()));
+  TORCH_CHECK(t.dim() == 3 && t.size(0) == B && t.size(1) == Sk && t.size(2) == Hkv, n, ": expected [B, Sk, Hkv] = [",
+              B, ", ", Sk, ", ", Hkv, "], got ", t.sizes());
+  ptr = t.data_ptr<float>();
+  sb = t.stride(0); ss = t.stride(1); sh = t.stride(2);
+}
+
 Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& kpm,
-                   const optional<Tensor>& lut, double scale, double softcap, int64_t splits, bool causal) {
+                   const optional<Tensor>& lut, double scale, double softcap, int64_t splits, bool causal,
+                   const optional<Tensor>& k_scale, const optional<Tensor>& v_scale) {
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "attn_decode: q / k / v must be [B, S, H, D]");
   const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3), Sk = k.size(1), Hkv = k.size(2);
   TORCH_CHECK(D >= 32 && D <= 256 && D % 8 == 0,
               "attn_decode: head dim must be in 32 .. 256 and a multiple of 8, got ", D);
+  const bool fp8 = k.scalar_type() == at::kFloat8_e4m3fn || v.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(k.scalar_type() == v.scalar_type(), "attn_decode: k and v must have one dtype, got ", k.scalar_type(),
+              " and ", v.scalar_type());
+  TORCH_CHECK(!fp8 || (has(k_scale) && has(v_scale)), "attn_decode: float8_e4m3fn k / v need k_scale and v_scale");
+  TORCH_CHECK(fp8 || (!has(k_scale) && !has(v_scale)),
+              "attn_decode: k_scale / v_scale come with float8_e4m3fn k / v only, got ", k.scalar_type());
+  TORCH_CHECK(!fp8 || D % 16 == 0, "attn_decode: fp8 k / v need a head dim that is a multiple of 16, got ", D);
   TORCH_CHECK(Hkv > 0 && H % Hkv == 0, "attn_decode: the ", H, " query heads are no multiple of the ", Hkv,
               " K/V heads");
   TORCH_CHECK(Sq * (H / Hkv) <= 16, "attn_decode: R = Sq * (H / Hkv) = ", Sq * (H / Hkv),
@@ -463,9 +488,16 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const opti
   TORCH_CHECK(B > 0 && Sq > 0 && Sk > 0, "attn_decode: empty attention");
   TORCH_CHECK(B <= 65535 && Hkv <= 65535 && Sk < (1 << 30), "attn_decode: B or Hkv > 65535 or Sk >= 2^30 unsupported");
   check_bshd(q, q, "q", B, Sq, H, D, kAttnDecode);
-  check_bshd(k, q, "k", B, Sk, Hkv, D, kAttnDecode);
-  check_bshd(v, q, "v", B, Sk, Hkv, D, kAttnDecode);
   AttnDecodeParams p{};
+  if (fp8) {  // code rows: strides in bytes
+    check_bshd(k, q, "k", B, Sk, Hkv, D, kAttnDecodeFp8);
+    check_bshd(v, q, "v", B, Sk, Hkv, D, kAttnDecodeFp8);
+    set_scale(*k_scale, q, "k_scale", B, Sk, Hkv, p.k_scale, p.ks_sb, p.ks_ss, p.ks_sh);
+    set_scale(*v_scale, q, "v_scale", B, Sk, Hkv, p.v_scale, p.vs_sb, p.vs_ss, p.vs_sh);
+  } else {
+    check_bshd(k, q, "k", B, Sk, Hkv, D, kAttnDecode);
+    check_bshd(v, q, "v", B, Sk, Hkv, D, kAttnDecode);
+  }
   set_view(q, p.q, p.q_sb, p.q_ss, p.q_sh);
   set_view(k, p.k, p.k_sb, p.k_ss, p.k_sh);
   set_view(v, p.v, p.v_sb, p.v_ss, p.v_sh);
@@ -494,6 +526,31 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const opti
   }
   check_rc(dllm_attn_decode(&p, stream()), "attn_decode");
   return o;
+}
+
+// kv [..., D] bf16 -> (float8_e4m3fn codes of kv's shape, dense; fp32 scales kv.shape[:-1]): the FP8 K/V row format of
+// csrc/attn_params.h.  The rows must lie one row stride apart (a dense tensor, or a slice of the last axis of one).
+std::vector<Tensor> kv_quant_fp8(const Tensor& kv) {
+  TORCH_CHECK(kv.is_cuda(), "kv_quant_fp8: kv must be a GPU tensor");
+  TORCH_CHECK(kv.scalar_type() == at::kBFloat16, "kv_quant_fp8: kv must be bf16, got ", dtype_name(kv.scalar_type()));
+  TORCH_CHECK(kv.dim() >= 2, "kv_quant_fp8: kv must be [..., D] with at least 2 axes, got ", kv.sizes());
+  const int64_t n = kv.dim(), D = kv.size(n - 1);
+  TORCH_CHECK(D >= 32 && D <= 256 && D % 16 == 0,
+              "kv_quant_fp8: the last axis must be in 32 .. 256 and a multiple of 16, got ", D);
+  TORCH_CHECK(kv.stride(n - 1) == 1, "kv_quant_fp8: the last axis must be contiguous");
+  const int64_t ld = kv.stride(n - 2);
+  for (int64_t i = n - 3; i >= 0; --i)
+    TORCH_CHECK(kv.size(i) == 1 || kv.stride(i) == kv.stride(i + 1) * kv.size(i + 1),
+                "kv_quant_fp8: the rows must lie one row stride apart (axis ", i, " of strides ", kv.strides(), ")");
+  TORCH_CHECK(ld >= D && ld % 8 == 0, "kv_quant_fp8: the row stride must be >= D and a multiple of 8 elements, got ", ld);
+  const std::string al = align_fault(kv, 16);
+  TORCH_CHECK(al.empty(), "kv_quant_fp8: kv ", al);
+  Tensor codes = at::empty(kv.sizes(), kv.options().dtype(at::kFloat8_e4m3fn));
+  Tensor scales = at::empty(kv.sizes().slice(0, n - 1), kv.options().dtype(at::kFloat));
+  check_rc(dllm_kv_quant_fp8(kv.data_ptr(), ld, static_cast<uint8_t*>(codes.data_ptr()), scales.data_ptr<float>(),
+                             kv.numel() / D, (int)D, stream()),
+           "kv_quant_fp8");
+  return {codes, scales};
 }
 
 // ---- csrc/attn.hip: the same helpers, plus its extras (dropout bit planes, saturated-bias ranges, rowrec, column sums)
@@ -647,7 +704,9 @@ void bind_attn(pybind11::module& m) {
         py::arg("kl_idx") = py::none(), py::arg("ql_ptr") = py::none(), py::arg("ql_idx") = py::none(),
         py::arg("softcap") = 0.0);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kpm"), py::arg("lut"),
-        py::arg("scale"), py::arg("softcap"), py::arg("splits") = 0, py::arg("causal") = false);
+        py::arg("scale"), py::arg("softcap"), py::arg("splits") = 0, py::arg("causal") = false,
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+  m.def("kv_quant_fp8", &kv_quant_fp8, py::arg("kv"));
 }
 
 }  // namespace dllm

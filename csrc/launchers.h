@@ -127,6 +127,9 @@ int dllm_attn_wide_bwd(AttnWideParams* pp, hipStream_t st);
 // partials for splits > 1 and calls dllm_attn_decode with the planned block
 int dllm_attn_decode_plan(AttnDecodeParams* pp);
 int dllm_attn_decode(const AttnDecodeParams* pp, hipStream_t st);
+// the FP8 K/V row format of AttnDecodeParams: `rows` rows of D bf16 (row_stride elements apart, 16-byte aligned;
+// D % 16 == 0 in 32 .. 256) to D e4m3fn codes each (dense, [rows, D]) and one fp32 scale per row
+int dllm_kv_quant_fp8(const void* kv, long row_stride, uint8_t* codes, float* scales, long rows, int D, hipStream_t st);
 
 // ---- csrc/rope.hip: rotate the `n` listed slots of x [B, S, *, H, D] in place (x_sn: the slot stride; strides in
 // elements); pos [B, S] (pos_sb = S) or [S] (pos_sb = 0); cos / sin fp32 [max_pos, D / 2]; sign -1: the backward

@@ -114,6 +114,12 @@ class BartAttention(nn.Module):
                 q = q.view(B, S, H, D)
             else:
                 q = self.q_proj(x).view(B, S, H, D)
+            if isinstance(kv, attn_ops.QuantKV):  # generate()'s FP8 cross K/V: attention_decode owns the fallback
+                o = attn_ops.attention_decode(q.reshape(kv.codes.shape[0], -1, H, D), kv.codes[:, :, 0],
+                                              kv.codes[:, :, 1], scale=self.scaling, key_padding_mask=mask,
+                                              k_scale=kv.scales[:, :, 0], v_scale=kv.scales[:, :, 1])
+                out = self.out_proj(o.reshape(B, S, H * D))
+                return (out, res) if residual else out
             kv = kv if kv is not None else self.project_kv(kv_in)
             if kv.shape[0] != B:  # beam search: the nb hypotheses of a batch entry share its encoder K/V (read once)
                 q = q.reshape(kv.shape[0], (B // kv.shape[0]) * S, H, D)

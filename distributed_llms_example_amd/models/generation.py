@@ -21,6 +21,7 @@ from __future__ import annotations
 import torch
 
 from ..ops import routing
+from ..ops.attention import QuantKV, quantize_kv
 from ..ops.attention import relative_bias_lut  # noqa: F401  (documented dependency)
 
 
@@ -75,6 +76,23 @@ class KVCache:
         if last:  # the last layer of the step advances the shared length
             st.len = n
         return kb[:, :n], vb[:, :n]
+
+
+def _quantize_cross(cross):
+    """Every decoder layer's projected cross-attention K/V ``[B, S, 2, H, D]`` as a QuantKV (ops/attention.py).  The
+    views ops/linear.py ``stacked_linear`` returns are feature slices of one GEMM output: that buffer is quantised by
+    one launch and sliced again; any other list is quantised layer by layer."""
+    first, L = cross[0], len(cross)
+    st, n = first.stride(), first[0, 0].numel()
+    if (L > 1 and first.dim() == 5 and st[1] == L * n and first[0, 0].is_contiguous()
+            and all(c.shape == first.shape and c.stride() == st
+                    and c.untyped_storage().data_ptr() == first.untyped_storage().data_ptr()
+                    and c.storage_offset() == first.storage_offset() + i * n for i, c in enumerate(cross))):
+        B, S = first.shape[:2]
+        whole = first.as_strided((B, S, L) + tuple(first.shape[2:]), (st[0], st[1], n) + tuple(st[2:]))
+        q = quantize_kv(whole)
+        return [QuantKV(q.codes[:, :, i], q.scales[:, :, i]) for i in range(L)]
+    return [quantize_kv(c) for c in cross]
 
 
 def _head_geom(model):
@@ -372,7 +390,8 @@ def generate(model, input_ids, attention_mask=None, max_length: int | None = Non
              early_stopping=None, forced_bos_token_id=None, forced_eos_token_id=None, max_new_tokens=None,
              global_attention_mask=None, global_index=None, do_sample: bool | None = None,
              temperature: float | None = None, top_k: int | None = None, top_p: float | None = None,
-             repetition_penalty: float | None = None, seed: int | None = None, **_unused):
+             repetition_penalty: float | None = None, seed: int | None = None, cross_kv_dtype: str | None = None,
+             **_unused):
     """Greedy search, beam search or multinomial sampling with a KV cache.
 
     Every option resolves as: the explicit argument, then ``model.config.generation``, then the default of the
@@ -388,7 +407,12 @@ def generate(model, input_ids, attention_mask=None, max_length: int | None = Non
     softmax mass of the strictly larger scores is < ``top_p``; >= 1: off), then a Gumbel-max draw from the
     counter-based uniforms of ops/rng.py ``sample_uniform(seed, step, rows, row, token)``: the same ``seed`` gives the
     same tokens (None: the next seed of the default seed stream).  Beam sampling is not implemented.  Keys of
-    transformers' generation config that are not implemented are ignored with a one-time warning that names them."""
+    transformers' generation config that are not implemented are ignored with a one-time warning that names them.
+
+    ``cross_kv_dtype`` (the argument, then the route key ``gen_cross_kv``; ``"bf16"`` | ``"fp8"``): ``"fp8"`` holds the
+    projected cross-attention K/V as ``float8_e4m3fn`` codes with one fp32 scale per (batch entry, key, K/V head)
+    (ops/attention.py ``quantize_kv``, once per call) — half the bytes every decode step reads and the call holds,
+    lossy, so opt-in.  The decoder self-attention cache stays in the model's dtype."""
     cfg = model.config
     gen = dict(cfg.generation)
     _warn_ignored({**{k: v for k, v in gen.items() if k in _IGNORED_KEYS}, **_unused})
@@ -421,6 +445,9 @@ def generate(model, input_ids, attention_mask=None, max_length: int | None = Non
             from ..ops import rng
             seed = rng.default_rng().next_seed()
         seed = int(seed) & 0xFFFFFFFF
+    cross_kv_dtype = cross_kv_dtype if cross_kv_dtype is not None else routing.get("gen_cross_kv")
+    if cross_kv_dtype not in ("bf16", "fp8"):
+        raise ValueError(f"cross_kv_dtype must be 'bf16' or 'fp8', got {cross_kv_dtype!r}")
     eos, pad, start = cfg.eos_token_id, cfg.pad_token_id, cfg.decoder_start_token_id
     was_training = model.training
     model.eval()
@@ -440,6 +467,8 @@ def generate(model, input_ids, attention_mask=None, max_length: int | None = Non
             enc = enc.repeat_interleave(nb, 0)
             attention_mask = attention_mask.repeat_interleave(nb, 0) if attention_mask is not None else None
             cross = model.project_cross_kv(enc)
+        if cross_kv_dtype == "fp8":
+            cross = _quantize_cross(cross)
         N = B * nb
         H, D = _head_geom(model)
         dtype = next(model.parameters()).dtype

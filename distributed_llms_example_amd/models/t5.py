@@ -97,6 +97,11 @@ class T5Attention(nn.Module):
             kw["q_segments"], kw["k_segments"] = seg
         if self.cross:
             q = self.q(x).view(B, S, H, D)
+            if isinstance(kv, attn_ops.QuantKV):  # generate()'s FP8 cross K/V: attention_decode owns the fallback
+                o = attn_ops.attention_decode(q.reshape(kv.codes.shape[0], -1, H, D), kv.codes[:, :, 0],
+                                              kv.codes[:, :, 1], scale=1.0, key_padding_mask=mask,
+                                              k_scale=kv.scales[:, :, 0], v_scale=kv.scales[:, :, 1])
+                return self.o(o.reshape(B, S, H * D))
             kv = kv if kv is not None else self.project_kv(kv_in)
             if kv.shape[0] != B:  # beam search: the nb hypotheses of a batch entry share its encoder K/V (read once)
                 q = q.reshape(kv.shape[0], (B // kv.shape[0]) * S, H, D)

@@ -98,6 +98,13 @@ class T5GemmaAttention(nn.Module):
         kw = dict(scale=self.scale, causal=causal, key_padding_mask=mask, dropout_p=p, seed=seed, softcap=self.softcap)
         if self.cross:
             q = self.q_proj(x).view(B, S, H, D)
+            if isinstance(kv, attn_ops.QuantKV):
+                # generate()'s FP8 cross K/V, at every head dim (136 .. 256 included): attention_decode owns the fallback
+                o = attn_ops.attention_decode(q.reshape(kv.codes.shape[0], -1, H, D), kv.codes[:, :, 0],
+                                              kv.codes[:, :, 1], scale=self.scale, key_padding_mask=mask,
+                                              softcap=self.softcap, k_scale=kv.scales[:, :, 0],
+                                              v_scale=kv.scales[:, :, 1])
+                return self.o_proj(o.reshape(B, S, H * D))
             kv = kv if kv is not None else self.project_kv(kv_in)
             if kv.shape[0] != B:  # beam search: the nb hypotheses of a batch entry share its encoder K/V (read once)
                 q = q.reshape(kv.shape[0], (B // kv.shape[0]) * S, H, D)

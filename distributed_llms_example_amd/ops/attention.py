@@ -61,6 +61,7 @@ a capped call takes the composite.
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -821,16 +822,69 @@ def attention_grouped(q, k, v, *, scale: float = 1.0, causal: bool = False, key_
 # --------------------------------------------------------------------------- decode steps (csrc/attn_decode.hip)
 
 
+class QuantKV(NamedTuple):
+    """FP8 K/V (the row format of csrc/attn_params.h AttnDecodeParams): ``codes`` ``[..., D]`` ``float8_e4m3fn`` and
+    ``scales`` ``[...]`` fp32, one per row of ``D`` codes; the value of an element is ``float(code) * scale``."""
+    codes: torch.Tensor
+    scales: torch.Tensor
+
+    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
+        return (self.codes.float() * self.scales.unsqueeze(-1)).to(dtype)
+
+
+FP8_MAX = 448.0  # the largest finite float8_e4m3fn
+
+
+def _quantize_kv_ref(kv) -> QuantKV:
+    """The contract as a torch composite, per row ``x`` of the last axis widened to fp32: ``scale = max|x| / 448`` (a
+    true fp32 division; 1 for a row of zeros), ``code = e4m3fn_rne(clamp(x / scale, -448, 448))``."""
+    x = kv.float()
+    absmax = x.abs().amax(-1, keepdim=True)
+    # divided by a tensor: torch turns a division by a Python scalar into a multiplication by its reciprocal
+    scale = torch.where(absmax == 0, torch.ones_like(absmax), absmax / torch.full_like(absmax, FP8_MAX))
+    codes = (x / scale).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return QuantKV(codes, scale.squeeze(-1))
+
+
+def _quant_served(kv) -> bool:
+    """csrc/attn_decode.hip's quantise kernel takes ``kv``: bf16 on the GPU, ``D % 16 == 0`` in 32 .. 256."""
+    D = kv.shape[-1]
+    return kv.dim() >= 2 and kv.dtype == torch.bfloat16 and 32 <= D <= 256 and D % 16 == 0 and _ext.use_native(kv)
+
+
+def quantize_kv(kv) -> QuantKV:
+    """K/V ``[..., D]`` to :class:`QuantKV`: ``codes`` of ``kv``'s shape in ``float8_e4m3fn`` and fp32 ``scales`` of
+    ``kv.shape[:-1]``, one per (…, key, K/V head) row of ``D`` elements.  bf16 on the GPU at ``D % 16 == 0`` in
+    32 .. 256 is one launch of the quantise kernel of csrc/attn_decode.hip over all rows (every decoder layer's stacked
+    projection at once); anything else — CPU tensors, ``DLLM_REFERENCE_OPS=1``, other dtypes or head dims — is the torch
+    composite of the same contract, and the kernel's codes and scales are bit-equal to it."""
+    if not _quant_served(kv) or kv.numel() == 0:
+        return _quantize_kv_ref(kv)
+    rows_apart = kv.stride(-1) == 1 and all(kv.size(i) == 1 or kv.stride(i) == kv.stride(i + 1) * kv.size(i + 1)
+                                            for i in range(kv.dim() - 2))
+    if not (rows_apart and kv.stride(-2) % 8 == 0 and kv.stride(-2) >= kv.shape[-1] and kv.data_ptr() % 16 == 0):
+        kv = kv.contiguous()
+    return QuantKV(*_ext.native().kv_quant_fp8(kv))
+
+
+def _aligned_codes(t) -> bool:
+    """Row starts of a ``[..., D]`` view of codes on 16 bytes: last dim contiguous, every other stride % 16."""
+    return t.stride(-1) == 1 and all(s % 16 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
+
+
 def decode_served(q, k, *, causal: bool = False, bias_lut=None, softcap=None) -> bool:
     """csrc/attn_decode.hip serves an :func:`attention_decode` call with this ``q`` ``[B,Sq,H,D]`` and ``k``
     ``[B,Sk,H_kv,D]``: bf16 on the GPU, ``attn_decode`` = 1 (ops/routing.py), ``D % 8 == 0`` in 32 .. 256, at most 16
     query rows per K/V head (``Sq * H / H_kv``), no causal mask over more than one query row (with one row and ``Sk``
-    the cache length it hides nothing) and no soft cap together with a bias LUT."""
+    the cache length it hides nothing) and no soft cap together with a bias LUT.  ``k`` may be ``float8_e4m3fn`` codes
+    (:class:`QuantKV`, with bf16 ``q``): then ``D % 16 == 0``."""
     if q.dim() != 4 or k.dim() != 4 or not _ext.use_native(q) or not routing.get("attn_decode"):
         return False
     Sq, H, D = q.shape[1:]
     Hkv = k.shape[2]
-    return (q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 and 32 <= D <= 256 and D % 8 == 0 and Hkv > 0
+    fp8 = k.dtype == torch.float8_e4m3fn
+    return (q.dtype == torch.bfloat16 and (fp8 or k.dtype == torch.bfloat16) and 32 <= D <= 256
+            and D % (16 if fp8 else 8) == 0 and Hkv > 0
             and H % Hkv == 0 and Sq * (H // Hkv) <= 16 and not (causal and Sq > 1)
             and not (softcap is not None and bias_lut is not None) and q.shape[0] <= 65535)
 
@@ -843,7 +897,7 @@ def decode_step(q, k, p: float = 0.0, **kw) -> bool:
 
 
 def attention_decode(q, k, v, *, scale: float = 1.0, causal: bool = False, key_padding_mask=None, bias_lut=None,
-                     softcap: float | None = None):
+                     softcap: float | None = None, k_scale=None, v_scale=None):
     """Attention of a generation step, forward only: q ``[B,Sq,H,D]`` (``Sq`` = 1, or the beams of a batch entry
     against its shared encoder K/V), k / v ``[B,Sk,H_kv,D]`` as they are — views of the KV cache, slices of a fused
     projection — with ``H % H_kv == 0`` (query head ``h`` reads K/V head ``h // (H // H_kv)``).  Where
@@ -851,7 +905,12 @@ def attention_decode(q, k, v, *, scale: float = 1.0, causal: bool = False, key_p
     merges the splits): K/V are read once per K/V head for all its query heads and beams.  Anything else — CPU
     tensors, ``DLLM_REFERENCE_OPS=1``, ``attn_decode`` = 0, fp32, more than 16 rows per K/V head, unaligned rows —
     computes what :func:`attention` / :func:`attention_grouped` compute for the call, K / V repeat included.
-    No autograd: an input that requires grad while grad is enabled raises."""
+    No autograd: an input that requires grad while grad is enabled raises.
+
+    FP8 K/V (:func:`quantize_kv`): ``k`` / ``v`` are ``float8_e4m3fn`` codes and ``k_scale`` / ``v_scale`` their fp32
+    ``[B,Sk,H_kv]`` scales (views of a :class:`QuantKV`'s ``scales``).  Served (``D % 16 == 0``, 16-byte aligned code
+    rows) it is the FP8 instantiation of the same kernel, which reads half the bytes; not served, K / V are
+    dequantised in fp32, cast to ``q``'s dtype and take the path above."""
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, bias_lut)):
         raise RuntimeError("attention_decode is forward only: call it under torch.no_grad() (generate does), or "
                            "attention / attention_grouped for a call that needs gradients")
@@ -859,6 +918,18 @@ def attention_decode(q, k, v, *, scale: float = 1.0, causal: bool = False, key_p
     H, Hkv = q.shape[2], k.shape[2]
     if Hkv <= 0 or H % Hkv or v.shape[2] != Hkv:
         raise ValueError(f"attention_decode: {H} query heads over k / v with {Hkv} / {v.shape[2]} heads")
+    fp8 = torch.float8_e4m3fn in (k.dtype, v.dtype)
+    if fp8 != (k_scale is not None) or fp8 != (v_scale is not None) or (fp8 and k.dtype != v.dtype):
+        raise ValueError("attention_decode: float8_e4m3fn k and v come with k_scale and v_scale, other dtypes without")
+    if fp8:
+        if k_scale.shape != k.shape[:-1] or v_scale.shape != v.shape[:-1]:
+            raise ValueError(f"attention_decode: k_scale / v_scale must be [B, Sk, H_kv] = {tuple(k.shape[:-1])}, got "
+                             f"{tuple(k_scale.shape)} and {tuple(v_scale.shape)}")
+        if (decode_served(q, k, causal=causal, bias_lut=bias_lut, softcap=softcap) and _aligned(q)
+                and _aligned_codes(k) and _aligned_codes(v)):
+            return _ext.native().attn_decode(q, k, v, _prep_kpm(key_padding_mask), bias_lut, float(scale),
+                                             softcap or 0.0, 0, bool(causal), k_scale.float(), v_scale.float())
+        k, v = QuantKV(k, k_scale).dequantize(q.dtype), QuantKV(v, v_scale).dequantize(q.dtype)
     if (decode_served(q, k, causal=causal, bias_lut=bias_lut, softcap=softcap) and v.dtype == q.dtype
             and all(_aligned(x) for x in (q, k, v))):
         return _ext.native().attn_decode(q, k, v, _prep_kpm(key_padding_mask), bias_lut, float(scale),

@@ -90,6 +90,17 @@ decode-step attention          ``attention_decode`` (cached self-attention, cros
                                (``attn_decode`` = 1), the rows in one MFMA tile, the key
                                axis split over workgroups, splits merged in fixed order;
                                0 and anything else: ``attention`` / ``attention_grouped``
+FP8 cross-attention K/V        ``gen_cross_kv`` = bf16 | fp8 (or ``generate(cross_kv_dtype=)``):  attn_decode_fp8.txt
+(generate(), opt-in, lossy)    fp8 quantises the projected encoder K/V once per call to
+                               e4m3 codes + one fp32 scale per (entry, key, K/V head)
+                               (``quantize_kv``, one launch for all layers) and every step
+                               reads them through the FP8 instantiation of
+                               csrc/attn_decode.hip (head dims % 16 == 0; else dequantised
+                               to the bf16 path); the self-attention cache stays bf16.
+                               Measured: 1.2 - 1.5x per launch at head dim 256, 1.7x at head
+                               dim 64 with 16384 keys and batch 8, level at batch 256, but
+                               16 - 20 % SLOWER than bf16 at head dim 64 with 512 / 1024
+                               keys and batch 8 / 64; generate() end to end is level
 segment-masked attention       as the window: bf16 (head dim 64 included) on                 attn_segments_vs_masked.txt
 (sequence packing)             csrc/attn_hd.hip, fp32 at head dim 64 on csrc/attn_f32.hip;
                                blocks of other segments are skipped by per-block (min,
@@ -194,6 +205,7 @@ DEFAULTS: dict = {
     "gen_fused_beam": 1,
     "gen_fused_sample": 1,        # sampling step on csrc/sample.hip (0: the torch composite)
     "gen_shared_cross": 1,
+    "gen_cross_kv": "bf16",       # bf16 | fp8: generate()'s cross-attention K/V (fp8: e4m3 codes + per-row scales, lossy)
     "gen_check_every": 8,
     "gen_host": 0,
     # data-parallel runtime (parallel/reducer.py, train/graph.py)

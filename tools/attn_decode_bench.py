@@ -1,12 +1,15 @@
 """Time one decode-step attention call: csrc/attn_decode.hip (``attention_decode``) against the training forward
 kernels the same call took before (DLLM_ROUTE attn_decode=0), interleaved in one process.
 
-    python tools/attn_decode_bench.py [--shapes B,nb,H,Hkv,Sk,D,splits ...] [--sweep] [--iters 200]
+    python tools/attn_decode_bench.py [--shapes B,nb,H,Hkv,Sk,D,splits ...] [--sweep] [--iters 200] [--kv fp8]
 ``nb`` query rows per batch entry (1: self-attention on the cache, 2 / 4: the beams of a shared cross-attention),
 ``splits`` 0 = the launcher's choice.  ``--sweep`` times every shape at splits 1, 2, 4, ... instead (the sweep that set
 FILL_PER_CU and SPLIT_FLOOR in csrc/attn_decode.hip).  One JSON line per measurement: microseconds per call (device
 events around ``iters`` calls after a warm-up) and the K/V bytes per second, 2 * B * Sk * Hkv * D * 2 bytes over that
-time — the bytes the op has to read, whatever a kernel reads more.
+time — the bytes the op has to read, whatever a kernel reads more.  ``--kv fp8``: the FP8 K/V instantiation (e4m3 codes
+and per-row scales from ``quantize_kv``) against the bf16 arm of the same kernel instead, interleaved alike, each arm
+with its own bytes (``2 * D + 8`` per key and K/V head against ``4 * D``), after one line for the quantise kernel; with
+``--sweep`` the split sweep of the FP8 arm.
 """
 import argparse
 import json
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--shapes", nargs="*", default=None)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--kv", choices=("bf16", "fp8"), default="bf16")
     a = ap.parse_args()
     shapes = [tuple(int(x) for x in s.split(",")) for s in a.shapes] if a.shapes else DEFAULT
     C = _ext.native()
@@ -58,9 +62,31 @@ def main():
         scale, nbytes = D ** -0.5, 2 * B * Sk * Hkv * D * 2
         rec = dict(B=B, nb=nb, H=H, Hkv=Hkv, Sk=Sk, D=D)
 
-        def emit(arm, us, **kw):
+        def emit(arm, us, nbytes=nbytes, **kw):
             print(json.dumps(dict(rec, arm=arm, us=round(us, 2), kv_TBps=round(nbytes / us * 1e-6, 3), **kw)), flush=True)
 
+        if a.kv == "fp8":
+            kv = torch.stack((k, v), 2)  # [B, Sk, 2, Hkv, D]: a projection's layout
+            qk = A.quantize_kv(kv)
+            k8, v8, ks, vs = qk.codes[:, :, 0], qk.codes[:, :, 1], qk.scales[:, :, 0], qk.scales[:, :, 1]
+            n8 = B * Sk * Hkv * (2 * D + 8)
+
+            def fp8(n):
+                return C.attn_decode(q, k8, v8, None, None, scale, 0.0, n, False, ks, vs)
+
+            if a.sweep:
+                n = 1
+                while n == 1 or Sk // n >= 128:
+                    emit("decode-fp8", timed(lambda: fp8(n), a.iters), n8, splits=n)
+                    n *= 2
+                continue
+            # the quantiser reads the bf16 rows and writes codes + scales
+            emit("quantise", timed(lambda: C.kv_quant_fp8(kv), a.iters), nbytes + n8)
+            for rep in range(2):
+                emit("decode-fp8", timed(lambda: fp8(splits), a.iters), n8, splits=splits, rep=rep)
+                emit("decode-bf16", timed(lambda: C.attn_decode(q, kv[:, :, 0], kv[:, :, 1], None, None, scale, 0.0,
+                                                                splits), a.iters), splits=splits, rep=rep)
+            continue
         if a.sweep:
             n = 1
             while n == 1 or Sk // n >= 128:

@@ -2,7 +2,9 @@
 (ref/train-accelerator.py:239-249).  Modes: ``fused`` = device-side beam bookkeeping with the one-kernel beam step
 (csrc/beam.hip), ``device`` = the same with the torch composite step (DLLM_ROUTE gen_fused_beam=0), ``host`` = the
 per-step host loop (gen_host=1), ``nodecode`` = ``fused`` with the decode steps' attention on the training forward
-kernels (attn_decode=0; ``fused`` runs csrc/attn_decode.hip).  ``--repeat N`` runs the mode list N times, interleaved.
+kernels (attn_decode=0; ``fused`` runs csrc/attn_decode.hip), ``fp8kv`` = ``fused`` with the cross-attention K/V held as
+FP8 codes (gen_cross_kv=fp8).  ``--repeat N`` runs the mode list N times, interleaved.  ``peak_GB``: the mode's peak
+allocated device memory.
 
     python tools/eval_bench.py [--model t5-base] [--batch 64] [--src-len 512] [--n 818] [--modes fused,device,host]
 Synthetic prompts (random ids, ragged attention masks) and random-init weights; prints one JSON line per mode.
@@ -39,10 +41,12 @@ def main():
     am = (torch.arange(a.src_len)[None, :] < lens[:, None]).long()
     for mode in a.modes.split(",") * a.repeat:
         os.environ["DLLM_ROUTE"] = (f"gen_host={1 if mode == 'host' else 0},"
-                                    f"gen_fused_beam={1 if mode in ('fused', 'nodecode') else 0},"
-                                    f"attn_decode={0 if mode == 'nodecode' else 1}")
+                                    f"gen_fused_beam={1 if mode in ('fused', 'nodecode', 'fp8kv') else 0},"
+                                    f"attn_decode={0 if mode == 'nodecode' else 1},"
+                                    f"gen_cross_kv={'fp8' if mode == 'fp8kv' else 'bf16'}")
         m.generate(ids[:a.batch].cuda(), attention_mask=am[:a.batch].cuda(), max_length=8, num_beams=a.beams)
         torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
         toks = 0
         for i in range(0, a.n, a.batch):
@@ -53,7 +57,8 @@ def main():
         dt = time.perf_counter() - t0
         print(json.dumps({"mode": mode, "model": a.model, "samples": a.n, "batch": a.batch, "num_beams": a.beams,
                           "max_length": a.max_length, "src_len": a.src_len, "seconds": round(dt, 3),
-                          "samples_per_s": round(a.n / dt, 2), "gen_tokens": toks}), flush=True)
+                          "samples_per_s": round(a.n / dt, 2), "gen_tokens": toks,
+                          "peak_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 3)}), flush=True)
 
 
 if __name__ == "__main__":
